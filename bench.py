@@ -1,7 +1,19 @@
 """Benchmark: vectorised Optimize-v0 env-steps/s on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--precision f64|f32]
-                  [--workload optimize|multi|mlp|nn] [--no-gather]
+                  [--workload optimize|multi|mlp|nn] [--no-gather] [--full]
+                  [--dump-outputs DIR]
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line
+with the headline figure (``value``, ``ms_per_step``) and what describes it.
+``--full`` adds everything measured beside it, each in runs of its own: the
+CPU baseline, the one-launch-per-step form (``value_per_step_launch``), the
+other gather schedules, the roofline with its per-kernel times and HBM
+traffic, and the host-loop rate.  ``--dump-outputs DIR`` writes the outputs
+of the last timed step (obs, reward, done, ...) as ``DIR/<name>.npy`` and,
+where one launch runs K steps, the records of the last launch as
+``DIR/rollout_<name>.npy``; seeds and actions are fixed, so two builds can
+be compared array for array.
 
 One "step" = one VecEnv.step of every env: the fused HIP kernel advances
 E = 4096 envs per GPU (weak scaling: N GPUs own N*4096 envs, contiguous
@@ -61,6 +73,10 @@ MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 HBM_COPY_GBS = 6290.0         # MI355X_MICROARCH.md: measured device-to-device copy rate
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md chip table (spec)
 F64_VALU_PEAK_TFLOPS = 78.6
+# --dump-outputs, per array: no engine has more than 7 outputs, each written
+# at most twice (last step, last launch), which stays under 64 MB in all
+DUMP_ARRAY_BYTES = 4 << 20
+DUMP_SAMPLE_SEED = 20240    # the sample of a larger output: the same elements every run
 
 
 def algorithmic_bytes_per_env_step(n_params, precision):
@@ -142,8 +158,16 @@ def parse(argv=None):
                    help='N > 1: no per-step all-gather in the headline value')
     p.add_argument('--gather', action='store_true',
                    help='all-gather every step also for the multi workload')
+    p.add_argument('--full', action='store_true',
+                   help='also run everything beside the headline figure: the CPU baseline, the '
+                        'other launch forms and gather schedules, the per-kernel and roofline '
+                        'figures, the HBM traffic and the host-loop rate')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write the outputs of the last timed step as '
+                        'DIR/<name>.npy (float32 / float64; a fixed seeded sample of an output '
+                        'larger than %d MB)' % (DUMP_ARRAY_BYTES >> 20))
     p.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU baseline budget per leg')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU legs')
     p.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--force-gather', action='store_true',
                    help='run the gather modes at world 1 too (a real 1-rank RCCL collective)')
@@ -156,7 +180,7 @@ def parse(argv=None):
     p.add_argument('--profile-only', action='store_true',
                    help='run the timed steps only (for rocprofv3)')
     p.add_argument('--measure-traffic', action='store_true', default=None,
-                   help='rank 0 at N = 1: measure roofline.traffic in this run (two rocprofv3 '
+                   help='--full, rank 0 at N = 1: measure roofline.traffic in this run (two rocprofv3 '
                         '--pmc passes of this workload as child processes, scripts/traffic.py); '
                         'the default when rocprofv3 is on PATH')
     p.add_argument('--timed-events', action='store_true',
@@ -172,7 +196,11 @@ def parse(argv=None):
                         'profiles/<round>_traffic_<workload>.json instead')
     args = p.parse_args(argv)
     args.hidden = tuple(int(h) for h in str(args.hidden).split(',') if h)
-    if args.measure_traffic is None:
+    if not args.full:
+        if args.measure_traffic:
+            p.error('--measure-traffic belongs to a --full run')
+        args.measure_traffic = False
+    elif args.measure_traffic is None:
         import shutil
         args.measure_traffic = shutil.which('rocprofv3') is not None and not args.profile_only
     if args.workload == 'mnist' and '--steps' not in (argv or sys.argv):
@@ -610,8 +638,12 @@ def main():
     if args.dry_run:
         dry_run(args, world, rank)
         return 0
+    if args.dump_outputs and (world > 1 or args.force_gather):
+        print('bench: --dump-outputs writes the outputs of the one-process run (--gpus 1, no '
+              'gather schedule)', file=sys.stderr)
+        return 2
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and not args.profile_only:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not args.profile_only:
         # every N: the reference path on the same box's host cores, in the
         # same run (north_star); a child process started before this rank
         # touches the GPU, while the other ranks wait in the rendezvous
@@ -786,13 +818,19 @@ def main():
         def gchunks(k):
             return [gg_chunk] * (k // gg_chunk) + ([k % gg_chunk] if k % gg_chunk else [])
 
-        run_gather_pipelined(max(args.warmup, 4))     # communicators up before capture
-        run_gather_serial(2)
-        kinds = [('pipelined', run_gather_pipelined), ('serial', run_gather_serial)]
+        # (schedule, its loop, the eager steps that bring the communicators up
+        # before capture)
+        first = [('pipelined', run_gather_pipelined, max(args.warmup, 4)),
+                 ('serial', run_gather_serial, 2)]
         if C > 1:
-            run_chunk_pipelined(2 * C + 1)
-            run_chunk_serial(C + 1)
-            kinds += [('chunk_pipelined', run_chunk_pipelined), ('chunk_serial', run_chunk_serial)]
+            first += [('chunk_pipelined', run_chunk_pipelined, 2 * C + 1),
+                      ('chunk_serial', run_chunk_serial, C + 1)]
+        gather_mode = 'chunk_pipelined' if C > 1 else 'serial'
+        if not args.full:                # the schedule `value` reports, alone
+            first = [f for f in first if f[0] == gather_mode]
+        for _, fn, n in first:
+            fn(n)
+        kinds = [(kind, fn) for kind, fn, _ in first]
         torch.cuda.synchronize()
         graphs = {}
         try:
@@ -835,8 +873,9 @@ def main():
             run = replayer(kind, fn)
             run(args.warmup)
             modes[kind] = _timed(torch, dist, run, args.steps)
-        run_graph(args.warmup)
-        modes['no_gather'] = _timed(torch, dist, run_graph, args.steps)
+        if args.full:
+            run_graph(args.warmup)
+            modes['no_gather'] = _timed(torch, dist, run_graph, args.steps)
         # every schedule runs every step AND the all-gather of its outputs
         # inside the timed region.  `value`: the chunk schedule where the
         # engine has the K-step launch (the actions of a chunk are device-
@@ -844,7 +883,6 @@ def main():
         # launch serves; the gather of chunk c overlaps chunk c + 1), else
         # the per-step serial schedule (a closed-loop learner acting on step
         # t's outputs before step t + 1), which rides along either way
-        gather_mode = 'chunk_pipelined' if C > 1 else 'serial'
         elapsed = modes[gather_mode]
     else:
         primary = run_graph
@@ -871,6 +909,20 @@ def main():
         record_events[0] = args.timed_events or len(chunks(args.steps)) >= 4
         elapsed = _timed(torch, dist, primary, args.steps)
         record_events[0] = False
+        if args.dump_outputs and rank == 0:
+            # the last timed step's record: the last launch wrote its steps
+            # into the slab's leading records; those are written too, as
+            # rollout_<name> (at a step where every env resets, the last
+            # step's obs alone is all zeros)
+            last = chunks(args.steps)[-1] - 1
+            arrays = dict(out)
+            if slab is not None:
+                records = {k: v for k, v in slab[0].items() if k != '_buffer'}
+                arrays = {k: v[last] for k, v in records.items()}
+                arrays.update({'rollout_' + k: v[:last + 1] for k, v in records.items()})
+            dump_outputs(torch, args.dump_outputs, arrays)
+        if not args.full:
+            timed_events.clear()
         if timed_events:
             per = [a.elapsed_time(b) / n for a, b, n in timed_events]
             modes['timed_region_kernel_ms'] = float(np.median(per))
@@ -878,7 +930,7 @@ def main():
         if args.repeat_timed > 0:
             modes['timed_repeats'] = [_timed(torch, dist, primary, args.steps)
                                       for _ in range(args.repeat_timed)]
-        if slab is not None:
+        if slab is not None and args.full:
             # the same steps as one launch per step (the one-step kernel,
             # what a closed-loop caller gets), timed the same way: the A/B
             # beside `value`
@@ -893,6 +945,36 @@ def main():
             runners.clear()
             run_graph(args.warmup)
             torch.cuda.synchronize()
+
+    def result_line(kernel_ms, kernel_ms_mean, phase_ms):
+        if mlp and eng.step_kernel.startswith('net<'):
+            return net_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard)
+        if mlp:
+            return mlp_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard,
+                            phase_ms)
+        if nn:
+            return nn_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard)
+        if mnist:
+            return mnist_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean)
+        return (multi_line if multi else optimize_line)(args, eng, world, E, S, elapsed,
+                                                        kernel_ms, kernel_ms_mean, shard)
+
+    if not args.full:
+        # the plain run ends here: the headline figure and what describes it;
+        # the roofline needs kernel times that take launches of their own
+        if rank == 0:
+            step_ms = elapsed / args.steps * 1e3
+            line = result_line(step_ms, step_ms, {})
+            del line['roofline']
+            if 'timed_repeats' in modes:
+                line['timed_repeats_ms'] = [round(t * 1e3, 5) for t in modes['timed_repeats']]
+            if args.one_gpu_rehearsal:
+                line['rehearsal'] = '%d ranks on one GPU, collectives on gloo: not an N-GPU rate' % world
+            print(json.dumps(line))
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return 0
 
     # live kernel duration: HIP events on the engine's stream (= torch's
     # current stream) around graph replays of S back-to-back step launches,
@@ -937,18 +1019,7 @@ def main():
         host_rate = host_loop_rate(args, device, E)
 
     if rank == 0:
-        if mlp and eng.step_kernel.startswith('net<'):
-            line = net_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard)
-        elif mlp:
-            line = mlp_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard,
-                            phase_ms)
-        elif nn:
-            line = nn_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean, shard)
-        elif mnist:
-            line = mnist_line(args, eng, world, E, S, elapsed, kernel_ms, kernel_ms_mean)
-        else:
-            line = (multi_line if multi else optimize_line)(args, eng, world, E, S, elapsed,
-                                                            kernel_ms, kernel_ms_mean, shard)
+        line = result_line(kernel_ms, kernel_ms_mean, phase_ms)
         if 'timed_region_kernel_ms' in modes:
             line['roofline']['kernel_ms_source'] = ('HIP events around every launch of the timed '
                                                     'region (median / mean per step)')
@@ -993,6 +1064,23 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(torch, path, outputs):
+    """--dump-outputs: every output tensor of the last timed step as
+    <path>/<name>.npy.  float32 / float64 outputs keep their type, the
+    integer and flag outputs (done, episode_len) are written as float64.  An
+    output above DUMP_ARRAY_BYTES is written as a 1-D sample of its flattened
+    elements at sorted RandomState(DUMP_SAMPLE_SEED) indices, which depend on
+    its size alone."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in sorted(outputs.items()):
+        keep = torch.float32 if t.dtype == torch.float32 else torch.float64
+        cap = DUMP_ARRAY_BYTES // (4 if keep == torch.float32 else 8)
+        if t.numel() > cap:
+            idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).randint(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.to(keep).cpu().numpy())
 
 
 def launch_events(torch, stream, fn, steps, n_ev=8):

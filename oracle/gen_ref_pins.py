@@ -312,6 +312,42 @@ def reference_load_data(mods):
     return ns['load_data'], img['resize_array_many']
 
 
+def function_vectors(mods, resize_many):
+    """Outputs of the reference's small functions on the inputs the tests
+    rebuild from the same seeds: History (tests/test_multi_host.py),
+    compute_rosenbrock (same), shuffle / to_onehot (tests/test_oracle.py,
+    tests/test_multinn_host.py), resize_array_many (tests/test_ref_pins.py)."""
+    from oracle.seeding import np_random
+    vec = {}
+    rs = np.random.RandomState(0)
+    hist = mods.common['History'](4, weights=(3,), losses=(), gradients=(3,))
+    for i in range(6):
+        hist.append(weights=rs.rand(3), losses=rs.rand(), gradients=rs.rand(3))
+        for key in ('weights', 'losses', 'gradients'):
+            vec['history_%s_%d' % (key, i)] = np.array(hist[key])
+        vec['history_multistate_%d' % i] = np.array(hist.build_multistate())
+    rs = np.random.RandomState(11)
+    for i, scale in enumerate((0.5, 2.0, 30.0)):
+        p = (rs.normal(size=8) * scale).astype(np.float32)
+        vec['rosenbrock_%d' % i] = mods.funcs['compute_rosenbrock'](p[0::2], p[1::2])
+    for seed in range(3):
+        npr.seed(seed)
+        a, b = mods.common['shuffle'](np.arange(25, 0, -1), np.arange(25))
+        vec['shuffle_a_%d' % seed], vec['shuffle_b_%d' % seed] = a, b
+    for seed in (0, 5, 123456):
+        rng, _ = np_random(seed)
+        (vec['shuffle_150_%d' % seed],) = mods.common['shuffle'](np.arange(150), np_random=rng)
+    to_onehot = load('custom_envs/utils/utils_common.py', ['to_onehot'], {'np': np})['to_onehot']
+    onehot, n = to_onehot(np.array([3, 1, 3, 2, 1, 0, 2]))
+    vec['onehot'], vec['onehot_classes'] = onehot, np.array(n)
+    rs = np.random.RandomState(0)
+    for i, (h, w, shape) in enumerate(((28, 28, (7, 7)), (28, 28, (13, 6)), (17, 23, (7, 11)),
+                                       (9, 9, (20, 4)))):
+        images = rs.randint(0, 256, (4, h, w)).astype(np.uint8)
+        vec['resize_%d' % i] = np.stack(resize_many(images, shape))
+    return vec
+
+
 def main():
     from oracle.data import gaussians
     os.makedirs(GOLDEN, exist_ok=True)
@@ -344,6 +380,8 @@ def main():
     for shape in ((7, 7), (5, 9), (14, 3)):
         out['resize_%dx%d' % shape] = np.stack(resize_many(imgs, shape))
     np.savez_compressed(os.path.join(GOLDEN, 'ref_load_data.npz'), **out)
+    np.savez_compressed(os.path.join(GOLDEN, 'ref_functions.npz'),
+                        **function_vectors(mods, resize_many))
 
 
 if __name__ == '__main__':

@@ -6,13 +6,11 @@ against PIL itself here (Pillow is importable in this image) and against the
 reference's utils_image in tests/test_ref_pins.py."""
 import gzip
 import lzma
-import os
 import struct
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE
 from custom_envs_amd.data import load_data, normalize, to_onehot
 from custom_envs_amd.data.files import resize_nearest
 
@@ -75,13 +73,21 @@ def test_iris_and_skin_tables(tmp_path):
     assert ds.targets.shape == (25, 3)
 
 
-def test_reference_lfs_pointers_are_refused():
-    data_dir = os.path.join(REFERENCE, 'custom_envs', 'data')
-    if not os.path.isdir(data_dir):
-        pytest.skip('reference checkout not present')
+def test_reference_lfs_pointers_are_refused(tmp_path):
+    """A data directory as the reference ships it: every file a git-LFS
+    pointer (the three-line text of the LFS spec) under the data file's name."""
+    pointer = ('version https://git-lfs.github.com/spec/v1\n'
+               'oid sha256:%s\nsize 9912422\n' % ('0123456789abcdef' * 4))
+    files = ['iris.npz', 'skin.txt']
+    for sub in ('mnist', 'fashion'):
+        (tmp_path / sub).mkdir()
+        files += ['%s/%s-%s-ubyte.xz' % (sub, prefix, kind) for prefix in ('train', 't10k')
+                  for kind in ('images-idx3', 'labels-idx1')]
+    for name in files:
+        (tmp_path / name).write_text(pointer)
     for name in ('mnist', 'iris', 'skin', 'fashion'):
-        with pytest.raises(RuntimeError, match='LFS|not found'):
-            load_data(name, data_dir=data_dir)
+        with pytest.raises(RuntimeError, match='LFS'):
+            load_data(name, data_dir=str(tmp_path))
 
 
 def test_file_sets_need_a_directory():

@@ -284,7 +284,7 @@ def test_bench_n_ranks_rehearsal_on_one_gpu():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--one-gpu-rehearsal',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--one-gpu-rehearsal',
            '--steps', '10', '--warmup', '2', '--chunk-steps', '4', '--no-cpu-baseline',
            '--no-measure-traffic', '--envs', '512']
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root)

@@ -1,70 +1,53 @@
 """Multi-agent path on the CPU: oracle pins, host facades, wrappers, Monitor.
 
 Pins: the restated ``History`` / ``build_multistate`` agree
-with the reference's importable ``custom_envs/utils/utils_common.py``
-(when /root/reference exists); committed MultiOptLRs rollouts regenerate
+with the reference's ``custom_envs/utils/utils_common.py`` (its outputs are
+recorded in tests/golden/ref_functions.npz); committed MultiOptLRs rollouts regenerate
 bit for bit.  The host surface (OptVecEnv's reference path, Monitor CSV
 chunks, History/SubSet wrappers) runs on stub envs, as the reference tests do
 (tests/vectorize/test_optvecenv.py:11-59, tests/wrappers/*).
 """
 import functools
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, golden
+from conftest import golden
 from custom_envs_amd.spaces import Box, Dict
-
-
-def _ref_utils_common():
-    path = os.path.join(REFERENCE, 'custom_envs', 'utils', 'utils_common.py')
-    if not os.path.exists(path):
-        pytest.skip('reference checkout not present')
-    spec = importlib.util.spec_from_file_location('ref_utils_common_m', path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.parametrize('impl', ['oracle', 'package'])
 def test_history_matches_reference(impl):
-    ref = _ref_utils_common()
+    """Against the reference's own History on the same appends, recorded in
+    tests/golden/ref_functions.npz (oracle/gen_ref_pins.py)."""
+    ref = golden('ref_functions.npz')
     if impl == 'oracle':
         from oracle.multioptlrs import History
     else:
         from custom_envs_amd.utils.utils_common import History
     rs = np.random.RandomState(0)
-    a = ref.History(4, weights=(3,), losses=(), gradients=(3,))
     b = History(4, weights=(3,), losses=(), gradients=(3,))
-    for _ in range(6):
-        item = dict(weights=rs.rand(3), losses=rs.rand(), gradients=rs.rand(3))
-        a.append(**item)
-        b.append(**item)
+    for i in range(6):
+        b.append(weights=rs.rand(3), losses=rs.rand(), gradients=rs.rand(3))
         for key in ('weights', 'losses', 'gradients'):
-            assert np.array_equal(a[key], b[key])
-        assert a.build_multistate() == b.build_multistate()
+            assert np.array_equal(ref['history_%s_%d' % (key, i)], b[key])
+        assert np.array_equal(ref['history_multistate_%d' % i], np.array(b.build_multistate()))
 
 
 def test_rosenbrock_terms_match_reference_function():
     """The oracle's float32 Rosenbrock pair terms are bit-identical to the
-    reference's own ``compute_rosenbrock`` (utils_functions.py:4-6, imported
-    by path) on float32 inputs: numpy evaluates 100*(y - x**2)**2 + (1 - x)**2
-    in the same float32 operation order (x**2 is x*x)."""
-    path = os.path.join(REFERENCE, 'custom_envs', 'utils', 'utils_functions.py')
-    if not os.path.exists(path):
-        pytest.skip('reference checkout not present')
-    spec = importlib.util.spec_from_file_location('ref_utils_functions', path)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    reference's own ``compute_rosenbrock`` (utils_functions.py:4-6, its
+    outputs recorded in tests/golden/ref_functions.npz) on float32 inputs:
+    numpy evaluates 100*(y - x**2)**2 + (1 - x)**2 in the same float32
+    operation order (x**2 is x*x)."""
+    ref = golden('ref_functions.npz')
     from oracle.multioptlrs import RosenbrockPairs
     rs = np.random.RandomState(11)
     prob = RosenbrockPairs(ndims=8)
-    for scale in (0.5, 2.0, 30.0):
+    for i, scale in enumerate((0.5, 2.0, 30.0)):
         p = (rs.normal(size=8) * scale).astype(np.float32)
         x, y = p[0::2], p[1::2]
-        ref_terms = ref.compute_rosenbrock(x, y)
+        ref_terms = ref['rosenbrock_%d' % i]
         assert ref_terms.dtype == np.float32
         one, c100 = np.float32(1), np.float32(100)
         d = y - x * x

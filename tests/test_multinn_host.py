@@ -2,20 +2,18 @@
 
 Pins: the row order the oracle composes (reset shuffle, then
 one shuffle per finished epoch) uses the reference's own
-``utils_common.shuffle`` (imported by path when /root/reference exists);
+``utils_common.shuffle`` (its outputs in tests/golden/ref_functions.npz);
 the oracle's backward pass matches central differences of its forward pass
 in float64; the native seeding (``ce_nn_seed_draws``) reproduces the
 oracle's draws bit for bit.  TensorFlow is absent, so the float32 network
 values themselves are "parity unpinned" against TF (oracle/multinn.py).
 """
 import ctypes
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE
+from conftest import golden
 from custom_envs_amd import _native
 from oracle.multinn import MultiOptLRsNN, OptimizeNN, nn_draws
 
@@ -124,18 +122,12 @@ def test_batch_cycling_and_order_composition():
 
 
 def test_order_composition_uses_the_reference_shuffle():
-    """The reference's own utils_common.shuffle (imported by path) under a
-    copy of the env RandomState reproduces the oracle's epoch permutation."""
-    path = os.path.join(REFERENCE, 'custom_envs', 'utils', 'utils_common.py')
-    if not os.path.exists(path):
-        pytest.skip('reference checkout not present')
-    spec = importlib.util.spec_from_file_location('ref_utils_common_nn', path)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    from oracle.seeding import np_random
+    """The reference's own utils_common.shuffle under a copy of the env
+    RandomState (its outputs recorded in tests/golden/ref_functions.npz by
+    oracle/gen_ref_pins.py) reproduces the oracle's epoch permutation."""
+    pins = golden('ref_functions.npz')
     for seed in (0, 5, 123456):
-        rng, _ = np_random(seed)
-        (shuffled,) = ref.shuffle(np.arange(150), np_random=rng)
+        shuffled = pins['shuffle_150_%d' % seed]
         assert np.array_equal(shuffled, nn_draws(seed, (4, 32, 3), 150)[2])
 
 
