@@ -43,6 +43,8 @@ EXPORTS = (
     'ce_nn_create', 'ce_nn_destroy', 'ce_nn_set_stream', 'ce_nn_n_params', 'ce_nn_seed',
     'ce_nn_seed_draws', 'ce_nn_reset', 'ce_nn_step', 'ce_nn_step_async', 'ce_nn_wait',
     'ce_nn_step_many', 'ce_nn_step_many_prepare', 'ce_nn_host_outputs', 'ce_nn_get_state',
+    'ce_policy_n_params', 'ce_policy_create', 'ce_policy_destroy', 'ce_policy_set_params',
+    'ce_policy_set_bounds', 'ce_policy_forward', 'ce_rollout_policy', 'ce_multi_rollout_policy',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -89,6 +91,16 @@ class CeNnConfig(ctypes.Structure):
         'abi_version', 'device', 'num_envs', 'n_rows', 'n_features', 'n_classes',
         'batch_size', 'n_hidden')] + [('hidden', ctypes.c_int32 * CE_NN_MAX_HIDDEN)] +
         [(name, ctypes.c_int32) for name in ('max_history', 'max_batches', 'auto_reset')])
+
+
+class CePolicyConfig(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'abi_version', 'device', 'obs_dim', 'act_dim', 'n_hidden')] + [('hidden', ctypes.c_int32 * 4)]
+
+
+class CePolicyOutputs(ctypes.Structure):
+    _fields_ = [('action', ctypes.c_void_p), ('env_action', ctypes.c_void_p),
+                ('neglogp', ctypes.c_void_p), ('value', ctypes.c_void_p)]
 
 
 class CeState(ctypes.Structure):
@@ -161,6 +173,16 @@ def _declare(lib):
                                     ctypes.c_int),
         'ce_nn_host_outputs': ([vp, ctypes.POINTER(CeMultiOutputs)], ctypes.c_int),
         'ce_nn_get_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_policy_n_params': ([ctypes.POINTER(CePolicyConfig)], ctypes.c_int),
+        'ce_policy_create': ([ctypes.POINTER(CePolicyConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_policy_destroy': ([vp], None),
+        'ce_policy_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_policy_set_bounds': ([vp, vp, vp], ctypes.c_int),
+        'ce_policy_forward': ([vp, vp, vp, i64, ctypes.POINTER(CePolicyOutputs), vp], ctypes.c_int),
+        'ce_rollout_policy': ([vp, vp, i32, vp, vp, i64, ctypes.POINTER(CeOutputs), i64,
+                               ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
+        'ce_multi_rollout_policy': ([vp, vp, i32, vp, vp, i64, ctypes.POINTER(CeMultiOutputs), i64,
+                                     ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

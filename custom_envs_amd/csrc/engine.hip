@@ -26,6 +26,7 @@
 #include "optimize_kernels.h"
 #include "optimize_mfma.h"
 #include "optimize_pair_kernel.h"
+#include "policy_engine.h"
 #include "seeding.h"
 
 namespace {
@@ -1011,6 +1012,32 @@ int ce_step_many_strided(ce_engine *e, int32_t k, const float *actions, int64_t 
     rc = use_persist(e, *out) ? launch_persist(e, k, actions, stride, *out, out_step)
                               : launch_steps(e, k, actions, stride, *out, out_step);
     if (rc != CE_OK) return rc;
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_rollout_policy(ce_engine *e, const ce_policy *p, int32_t k, const float *obs0,
+                      const float *noise, int64_t noise_stride, const ce_outputs *out,
+                      int64_t out_step, const ce_policy_outputs *pout, int64_t pout_step) {
+    if (!e) return fail(CE_EINVAL, "ce_rollout_policy: null engine");
+    if (!out || !complete(out)) return fail(CE_EINVAL, "ce_rollout_policy: device outputs must all be set");
+    if (e->compact)
+        return fail(CE_EINVAL, "ce_rollout_policy: needs the full output form (compact outputs are on)");
+    int rc = ce::policy_rollout_args_ok("ce_rollout_policy", p, e->obs_dim, e->P, k, obs0, noise,
+                                        noise_stride, e->cfg.num_envs, out->obs, out_step, pout,
+                                        pout_step);
+    if (rc != CE_OK) return rc;
+    if (!e->was_reset) return fail(CE_ESTATE, "ce_rollout_policy before the first reset()");
+    CE_CLEAR_STALE_ERROR();
+    const float *obs = obs0;
+    for (int s = 0; s < k; ++s) {
+        const ce_policy_outputs po = ce::policy_advance(*pout, s * pout_step);
+        const ce_outputs eo = advance(*out, s * out_step);
+        ce::policy_launch(p, obs, noise ? noise + s * noise_stride : nullptr, e->cfg.num_envs, po,
+                          e->stream);
+        if ((rc = launch(e, false, po.env_action, eo, e->stream)) != CE_OK) return rc;
+        obs = eo.obs;
+    }
     CE_HIP(hipGetLastError());
     return CE_OK;
 }

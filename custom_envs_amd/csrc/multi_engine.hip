@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "multiopt_kernels.h"
+#include "policy_engine.h"
 
 namespace {
 
@@ -446,6 +447,36 @@ int ce_multi_step_many_strided(ce_multi_engine *e, int32_t k, const float *actio
             o.episode_len = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(o.episode_len) + b);
             e->kern->step(make_args(e, actions + s * stride, o), grid_of(e), e->stream);
         }
+    }
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_multi_rollout_policy(ce_multi_engine *e, const ce_policy *p, int32_t k, const float *obs0,
+                            const float *noise, int64_t noise_stride, const ce_multi_outputs *out,
+                            int64_t out_step, const ce_policy_outputs *pout, int64_t pout_step) {
+    if (!e) return fail(CE_EINVAL, "ce_multi_rollout_policy: null engine");
+    if (!complete(out)) return fail(CE_EINVAL, "ce_multi_rollout_policy: device outputs must all be set");
+    const int64_t rows = static_cast<int64_t>(e->cfg.num_envs) * e->cfg.n_params;
+    const int rc = ce::policy_rollout_args_ok("ce_multi_rollout_policy", p, 3 * e->cfg.max_history, 1,
+                                              k, obs0, noise, noise_stride, rows, out->obs, out_step,
+                                              pout, pout_step);
+    if (rc != CE_OK) return rc;
+    if (!e->was_reset) return fail(CE_ESTATE, "ce_multi_rollout_policy before the first reset()");
+    CE_CLEAR_STALE_ERROR();
+    const float *obs = obs0;
+    for (int s = 0; s < k; ++s) {
+        const ce_policy_outputs po = ce::policy_advance(*pout, s * pout_step);
+        ce_multi_outputs o = *out;
+        const int64_t b = s * out_step;
+        o.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(o.obs) + b);
+        o.reward = reinterpret_cast<float *>(reinterpret_cast<char *>(o.reward) + b);
+        o.done = o.done + b;
+        o.info = reinterpret_cast<float *>(reinterpret_cast<char *>(o.info) + b);
+        o.episode_len = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(o.episode_len) + b);
+        ce::policy_launch(p, obs, noise ? noise + s * noise_stride : nullptr, rows, po, e->stream);
+        e->kern->step(make_args(e, po.env_action, o), grid_of(e), e->stream);
+        obs = o.obs;
     }
     CE_HIP(hipGetLastError());
     return CE_OK;

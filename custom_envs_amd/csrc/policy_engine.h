@@ -1,0 +1,32 @@
+// The device-side MLP policy (ce_policy_* in include/custom_envs_amd.h) as the
+// engines see it: ce_rollout_policy (engine.hip) and ce_multi_rollout_policy
+// (multi_engine.hip) enqueue [policy, env step] x K through these.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/custom_envs_amd.h"
+
+namespace ce {
+
+// obs_dim / act_dim of a policy (no HIP call)
+void policy_dims(const ce_policy *p, int *obs_dim, int *act_dim);
+
+// Enqueue one policy_mlp_kernel launch: every pointer a device pointer, all
+// four outputs set, rows >= 1.  Arguments are NOT validated here.
+void policy_launch(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+                   const ce_policy_outputs &out, hipStream_t stream);
+
+// The argument checks the two rollout entry points share (before any HIP
+// call): null pointers, k, strides, alignment, the policy's shape against the
+// engine's.  CE_OK or a failed status with ce_last_error set.
+int policy_rollout_args_ok(const char *who, const ce_policy *p, int engine_obs_dim,
+                           int engine_act_dim, int32_t k, const float *obs0, const float *noise,
+                           int64_t noise_stride, int64_t rows, const void *env_obs,
+                           int64_t out_step_bytes, const ce_policy_outputs *pout,
+                           int64_t pout_step_bytes);
+
+// the policy outputs of step t of a rollout
+ce_policy_outputs policy_advance(const ce_policy_outputs &o, int64_t bytes);
+
+}  // namespace ce

@@ -1,0 +1,283 @@
+// C-ABI implementation of the device-side MLP policy (ce_policy_* in
+// include/custom_envs_amd.h): owns the parameter image policy_mlp_kernel
+// stages from (policy_kernels.h), repacks a caller's flat parameter vector
+// into it with one launch, and enqueues the fused forward.  Every argument
+// check precedes the first HIP call, so the checks run without a device.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "policy_engine.h"
+#include "policy_kernels.h"
+
+struct ce_policy {
+    ce_policy_config cfg{};
+    ce::PolicyArgs args{};       // shape, offsets and img filled at create
+    ce::PolicyPack pack{};
+    int n_params = 0, img_floats = 0;
+    size_t lds_bytes = 0;
+    float *img = nullptr;        // the padded parameter image + logstd, low, high
+    float *d_flat = nullptr;     // staging of a host-pointer set_params
+};
+
+namespace {
+
+using ce::fail;
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// shape limits (no HIP call); `who` prefixes the message
+int shape_ok(const char *who, const ce_policy_config *cfg) {
+    const std::string w(who);
+    if (!cfg) return fail(CE_EINVAL, w + ": null config");
+    if (cfg->abi_version != CE_ABI_VERSION) return fail(CE_EINVAL, w + ": ABI version mismatch");
+    if (cfg->obs_dim <= 0 || cfg->act_dim <= 0 || cfg->n_hidden <= 0)
+        return fail(CE_EINVAL, w + ": obs_dim, act_dim and n_hidden must be positive");
+    if (cfg->n_hidden > ce::kPolMaxHidden)
+        return fail(CE_EUNSUPPORTED, w + ": the policy takes 1 to 3 hidden layers, got " +
+                                         std::to_string(cfg->n_hidden));
+    if (cfg->obs_dim > ce::kPolMaxD)
+        return fail(CE_EUNSUPPORTED, w + ": obs_dim " + std::to_string(cfg->obs_dim) +
+                                         " exceeds the limit of 128");
+    if (cfg->act_dim > ce::kPolMaxA)
+        return fail(CE_EUNSUPPORTED, w + ": act_dim " + std::to_string(cfg->act_dim) +
+                                         " exceeds the limit of 64");
+    for (int l = 0; l < cfg->n_hidden; ++l) {
+        const int h = cfg->hidden[l];
+        if (h <= 0) return fail(CE_EINVAL, w + ": hidden widths must be positive");
+        if (h % 32 != 0 || h > ce::kPolMaxWidth)
+            return fail(CE_EUNSUPPORTED, w + ": hidden width " + std::to_string(h) +
+                                             " is not a multiple of 32 up to 128");
+    }
+    return CE_OK;
+}
+
+int count_params(const ce_policy_config *cfg) {
+    int n = 0;
+    for (int net = 0; net < 2; ++net) {
+        int in = cfg->obs_dim;
+        for (int l = 0; l <= cfg->n_hidden; ++l) {
+            const int out = l < cfg->n_hidden ? cfg->hidden[l] : (net == 0 ? cfg->act_dim : 1);
+            n += in * out + out;
+            in = out;
+        }
+    }
+    return n + cfg->act_dim;
+}
+
+// the image layout, the pack table and the kernel's shape arguments
+void plan(ce_policy *p) {
+    const ce_policy_config &c = p->cfg;
+    ce::PolicyArgs &a = p->args;
+    ce::PolicyPack &k = p->pack;
+    a.D = c.obs_dim;
+    a.A = c.act_dim;
+    a.n_hidden = c.n_hidden;
+    int img = 0, src = 0, seg = 0, wmax = 0, kmax = 0;
+    auto add = [&](int rows, int cols, int rows_pad, int cols_pad) {
+        k.dst[seg] = img;
+        k.src[seg] = src;
+        k.rows[seg] = rows;
+        k.cols[seg] = cols;
+        k.rows_pad[seg] = rows_pad;
+        k.cols_pad[seg] = cols_pad;
+        ++seg;
+        src += rows * cols;
+        const int at = img;
+        img += rows_pad * cols_pad;
+        return at;
+    };
+    for (int net = 0; net < 2; ++net) {
+        int in = c.obs_dim;
+        for (int l = 0; l <= c.n_hidden; ++l) {
+            const int out = l < c.n_hidden ? c.hidden[l] : (net == 0 ? c.act_dim : 1);
+            const int ip = round_up(in, 4), op = round_up(out, 32);
+            a.in_pad[l] = ip;
+            a.out_pad[net][l] = op;
+            a.off_w[net][l] = add(in, out, ip, op);
+            a.off_b[net][l] = add(1, out, 1, op);
+            wmax = std::max(wmax, ip * op);
+            kmax = std::max(kmax, ip);
+            in = out;
+        }
+    }
+    a.off_logstd = add(1, c.act_dim, 1, round_up(c.act_dim, 4));
+    k.n = seg;
+    a.off_low = img;
+    img += round_up(c.act_dim, 4);
+    a.off_high = img;
+    img += round_up(c.act_dim, 4);
+    p->n_params = src;
+    p->img_floats = img;
+    a.w_floats = wmax;
+    a.act_floats = kmax * ce::kPolLd;
+    p->lds_bytes = static_cast<size_t>(wmax + 2 * a.act_floats) * sizeof(float);
+}
+
+bool complete(const ce_policy_outputs *o) {
+    return o && o->action && o->env_action && o->neglogp && o->value;
+}
+
+}  // namespace
+
+namespace ce {
+
+void policy_dims(const ce_policy *p, int *obs_dim, int *act_dim) {
+    *obs_dim = p->cfg.obs_dim;
+    *act_dim = p->cfg.act_dim;
+}
+
+void policy_launch(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+                   const ce_policy_outputs &out, hipStream_t stream) {
+    PolicyArgs a = p->args;
+    a.rows = static_cast<int>(rows);
+    a.obs = obs;
+    a.noise = noise;
+    a.action = out.action;
+    a.env_action = out.env_action;
+    a.neglogp = out.neglogp;
+    a.value = out.value;
+    const dim3 grid(static_cast<unsigned>((rows + kPolTile - 1) / kPolTile), 2);
+    hipLaunchKernelGGL(policy_mlp_kernel, grid, dim3(kPolBlock), p->lds_bytes, stream, a);
+}
+
+ce_policy_outputs policy_advance(const ce_policy_outputs &o, int64_t bytes) {
+    auto adv = [bytes](float *q) { return reinterpret_cast<float *>(reinterpret_cast<char *>(q) + bytes); };
+    return ce_policy_outputs{adv(o.action), adv(o.env_action), adv(o.neglogp), adv(o.value)};
+}
+
+int policy_rollout_args_ok(const char *who, const ce_policy *p, int engine_obs_dim,
+                           int engine_act_dim, int32_t k, const float *obs0, const float *noise,
+                           int64_t noise_stride, int64_t rows, const void *env_obs,
+                           int64_t out_step_bytes, const ce_policy_outputs *pout,
+                           int64_t pout_step_bytes) {
+    const std::string w(who);
+    if (!p) return fail(CE_EINVAL, w + ": null policy");
+    if (k <= 0 || !obs0) return fail(CE_EINVAL, w + ": k must be positive and obs0 set");
+    if (!complete(pout)) return fail(CE_EINVAL, w + ": policy outputs must all be set");
+    if (p->cfg.obs_dim != engine_obs_dim || p->cfg.act_dim != engine_act_dim)
+        return fail(CE_EINVAL, w + ": the policy maps " + std::to_string(p->cfg.obs_dim) + " -> " +
+                                   std::to_string(p->cfg.act_dim) + ", the engine's rows are " +
+                                   std::to_string(engine_obs_dim) + " -> " +
+                                   std::to_string(engine_act_dim));
+    if (noise && (noise_stride < 0 || (k > 1 && noise_stride != 0 &&
+                                       noise_stride < rows * p->cfg.act_dim)))
+        return fail(CE_EINVAL, w + ": noise_stride must be 0 or at least rows * act_dim");
+    if (out_step_bytes < 0 || out_step_bytes % 16 != 0 ||
+        (reinterpret_cast<uintptr_t>(env_obs) & 15) != 0)
+        return fail(CE_EINVAL, w + ": obs must be 16-byte aligned and out_step_bytes a "
+                                   "non-negative multiple of 16");
+    if (pout_step_bytes < 0 || pout_step_bytes % 16 != 0)
+        return fail(CE_EINVAL, w + ": pout_step_bytes must be a non-negative multiple of 16");
+    return CE_OK;
+}
+
+}  // namespace ce
+
+extern "C" {
+
+int ce_policy_n_params(const ce_policy_config *cfg) {
+    const int rc = shape_ok("ce_policy_n_params", cfg);
+    return rc != CE_OK ? rc : count_params(cfg);
+}
+
+int ce_policy_create(const ce_policy_config *cfg, ce_policy **out) {
+    if (!cfg || !out) return fail(CE_EINVAL, "ce_policy_create: null argument");
+    *out = nullptr;
+    int rc = shape_ok("ce_policy_create", cfg);
+    if (rc != CE_OK) return rc;
+    ce_policy *p = new (std::nothrow) ce_policy();
+    if (!p) return fail(CE_ENOMEM, "ce_policy_create: host allocation failed");
+    p->cfg = *cfg;
+    plan(p);
+    auto bail = [&](int code) {
+        ce_policy_destroy(p);
+        return code;
+    };
+#define CE_TRY(call)                                                           \
+    do {                                                                       \
+        hipError_t err_ = (call);                                              \
+        if (err_ != hipSuccess)                                                \
+            return bail(fail(CE_EHIP, std::string(#call " failed: ") +         \
+                                          hipGetErrorString(err_)));           \
+    } while (0)
+    CE_TRY(hipSetDevice(cfg->device));
+    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>((ce::kPolMaxWidth * ce::kPolMaxWidth +
+                                                 2 * ce::kPolMaxWidth * ce::kPolLd) * sizeof(float))));
+    CE_TRY(hipMalloc(&p->img, p->img_floats * sizeof(float)));
+    CE_TRY(hipMalloc(&p->d_flat, p->n_params * sizeof(float)));
+    // zero parameters, unbounded actions
+    std::vector<float> init(p->img_floats, 0.0f);
+    for (int c = 0; c < cfg->act_dim; ++c) {
+        init[p->args.off_low + c] = -INFINITY;
+        init[p->args.off_high + c] = INFINITY;
+    }
+    CE_TRY(hipMemcpy(p->img, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+#undef CE_TRY
+    p->args.img = p->img;
+    *out = p;
+    return CE_OK;
+}
+
+void ce_policy_destroy(ce_policy *p) {
+    if (!p) return;
+    if (p->img) (void)hipFree(p->img);
+    if (p->d_flat) (void)hipFree(p->d_flat);
+    delete p;
+}
+
+int ce_policy_set_params(ce_policy *p, const float *flat, int64_t n, uint32_t flags,
+                         void *hip_stream) {
+    if (!p || !flat) return fail(CE_EINVAL, "ce_policy_set_params: null argument");
+    if (n != p->n_params)
+        return fail(CE_EINVAL, "ce_policy_set_params: got " + std::to_string(n) +
+                                   " parameters, the policy has " + std::to_string(p->n_params));
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    if (!dev) {
+        CE_HIP(hipMemcpyAsync(p->d_flat, flat, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        CE_HIP(hipStreamSynchronize(stream));   // `flat` may be pageable
+    }
+    hipLaunchKernelGGL(ce::policy_pack_kernel, dim3(p->pack.n), dim3(256), 0, stream, p->pack,
+                       dev ? flat : p->d_flat, p->img);
+    CE_HIP(hipGetLastError());
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));
+    return CE_OK;
+}
+
+int ce_policy_set_bounds(ce_policy *p, const float *low, const float *high) {
+    if (!p) return fail(CE_EINVAL, "ce_policy_set_bounds: null policy");
+    const int A = p->cfg.act_dim;
+    std::vector<float> lo(A, -INFINITY), hi(A, INFINITY);
+    for (int c = 0; c < A; ++c) {
+        if (low) lo[c] = low[c];
+        if (high) hi[c] = high[c];
+        if (!(lo[c] <= hi[c])) return fail(CE_EINVAL, "ce_policy_set_bounds: low must be <= high");
+    }
+    CE_CLEAR_STALE_ERROR();
+    CE_HIP(hipMemcpy(p->img + p->args.off_low, lo.data(), A * sizeof(float), hipMemcpyHostToDevice));
+    CE_HIP(hipMemcpy(p->img + p->args.off_high, hi.data(), A * sizeof(float), hipMemcpyHostToDevice));
+    return CE_OK;
+}
+
+int ce_policy_forward(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+                      const ce_policy_outputs *out, void *hip_stream) {
+    if (!p || !obs) return fail(CE_EINVAL, "ce_policy_forward: null argument");
+    if (!complete(out)) return fail(CE_EINVAL, "ce_policy_forward: policy outputs must all be set");
+    if (rows < 1 || rows > (int64_t(1) << 24))
+        return fail(CE_EINVAL, "ce_policy_forward: rows must be in [1, 2^24]");
+    CE_CLEAR_STALE_ERROR();
+    ce::policy_launch(p, obs, noise, rows, *out, static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+}  // extern "C"

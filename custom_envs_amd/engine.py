@@ -391,6 +391,41 @@ class OptimizeEngine:
                                              ctypes.byref(o), int(record_bytes)),
               'ce_step_many_strided')
 
+    # ------------------------------------------- closed loop: policy + env x K
+    def alloc_policy_rollout(self, k, policy):
+        """The buffers of ``rollout_policy``: (fields, record_bytes) as
+        ``alloc_rollout`` and (policy_fields, policy_record_bytes) as
+        ``policy.alloc_outputs(rows, k)``, returned as one 4-tuple."""
+        fields, rec = self.alloc_rollout(k)
+        pfields, prec = policy.alloc_outputs(self.num_envs, k)
+        return fields, rec, pfields, prec
+
+    def rollout_policy(self, k, policy, obs0, noise, fields, record_bytes, policy_fields,
+                       policy_record_bytes=None):
+        """A K-step closed-loop rollout as ONE foreign call
+        (``ce_rollout_policy``): for t < k, on the engine's stream, the policy
+        (``custom_envs_amd.policy.MlpPolicy``) reads ``obs0`` (t = 0) or
+        ``fields['obs'][t - 1]`` and writes ``policy_fields[...][t]``, then the
+        env steps with ``policy_fields['env_action'][t]`` -- the kernel
+        ``step_device`` launches -- and writes ``fields[...][t]``.  ``noise``:
+        ``[>= k][E][A]`` N(0,1) draws, or None for the deterministic policy.
+        Needs the full output form.  Every tensor is validated first
+        (``policy.validate_rollout``)."""
+        from custom_envs_amd.policy import validate_rollout
+        if self.compact:
+            raise ValueError('rollout_policy needs the full output form (compact outputs are on)')
+        first, prec = validate_rollout(self.output_fields(), self.num_envs, self.num_envs,
+                                       self.obs_dim, self.act_dim, self.device, k, policy, obs0,
+                                       noise, fields, record_bytes, policy_fields,
+                                       policy_record_bytes)
+        o = self._outputs(first)
+        po = policy.outputs_struct({n: policy_fields[n][0] for n in
+                                    ('action', 'env_action', 'neglogp', 'value')})
+        check(self._lib.ce_rollout_policy(
+            self._h, policy._h, int(k), obs0.data_ptr(),
+            None if noise is None else noise.data_ptr(), self.num_envs * self.act_dim,
+            ctypes.byref(o), int(record_bytes), ctypes.byref(po), prec), 'ce_rollout_policy')
+
     def rollout_runner(self, k, actions, fields, record_bytes, per_step_actions=True):
         """rollout_device bound once (see many_runner)."""
         first = check_rollout(self.output_fields(), self.num_envs, k, actions, self.num_envs * self.act_dim,

@@ -65,6 +65,7 @@ class MultiOptEngine:
                              'agent, an env within one wave); got %d'
                              % (_native.CE_MULTI_MAX_PARAMS, ndims))
         self.num_envs, self.n_params = int(num_envs), ndims
+        self.device = int(device)
         self.max_history, self.max_batches = int(max_history), int(max_batches)
         cfg = CeMultiConfig(abi_version=_native.ABI_VERSION, device=int(device),
                             num_envs=self.num_envs, n_params=ndims,
@@ -112,6 +113,31 @@ class MultiOptEngine:
         stride = self.rows if per_step_actions else 0
         self._call('step_many_strided', int(k), actions.data_ptr(), stride, ctypes.byref(o),
                    int(record_bytes))
+
+    def alloc_policy_rollout(self, k, policy):
+        """(fields, record_bytes, policy_fields, policy_record_bytes) for
+        ``rollout_policy`` (``alloc_rollout`` + ``policy.alloc_outputs``)."""
+        import torch
+        fields, rec = self.alloc_rollout(k, torch.device('cuda', getattr(self, 'device', 0)))
+        pfields, prec = policy.alloc_outputs(self.rows, k)
+        return fields, rec, pfields, prec
+
+    def rollout_policy(self, k, policy, obs0, noise, fields, record_bytes, policy_fields,
+                       policy_record_bytes=None):
+        """K closed-loop steps as one foreign call (``ce_multi_rollout_policy``):
+        the policy maps every (env, agent) row ``[3 max_history] -> [1]``; see
+        ``OptimizeEngine.rollout_policy``."""
+        from custom_envs_amd.policy import validate_rollout
+        first, prec = validate_rollout(self.output_fields(), self.num_envs, self.rows,
+                                       3 * self.max_history, 1, getattr(self, 'device', 0), k,
+                                       policy, obs0, noise, fields, record_bytes, policy_fields,
+                                       policy_record_bytes)
+        o = self._outputs(first)
+        po = policy.outputs_struct({n: policy_fields[n][0] for n in
+                                    ('action', 'env_action', 'neglogp', 'value')})
+        self._call('rollout_policy', policy._h, int(k), obs0.data_ptr(),
+                   None if noise is None else noise.data_ptr(), self.rows, ctypes.byref(o),
+                   int(record_bytes), ctypes.byref(po), prec)
 
     def rollout_runner(self, k, actions, fields, record_bytes, per_step_actions=True):
         """rollout_device bound once."""
@@ -310,6 +336,12 @@ class NNMultiEngine(MultiOptEngine):
         raise _native.NativeEngineError('the network problem has no strided K-step form')
 
     rollout_runner = rollout_device
+
+    def rollout_policy(self, *args, **kwargs):
+        raise _native.NativeEngineError('the network problem has no K-step closed-loop form '
+                                        '(MlpPolicy.forward_device + step_device per step)')
+
+    alloc_policy_rollout = rollout_policy
 
     @property
     def dims(self):

@@ -85,6 +85,7 @@ class GPUVecEnv:
         self.current_step = np.zeros(self.num_envs, np.int64)
         self.waiting = False
         self.closed = False
+        self._last_obs = None      # what collect() starts from
         self.seed(seed)
 
     # ----------------------------------------------------------- VecEnv API
@@ -107,7 +108,8 @@ class GPUVecEnv:
         self.current_step[:] = 0
         if self.monitor is not None:
             self.monitor.reset()
-        return self.engine.reset()
+        self._last_obs = self.engine.reset()
+        return self._last_obs
 
     def step_async(self, actions):
         if self.monitor is not None:
@@ -126,11 +128,47 @@ class GPUVecEnv:
         obs = out['obs'].copy()
         if self.monitor is not None:
             infos.episodes.update(self.monitor.step(reward, dones, infos, obs))
+        self._last_obs = obs
         return obs, reward, dones, infos
 
     def step(self, actions):
         self.step_async(actions)
         return self.step_wait()
+
+    def collect(self, policy, n_steps, noise=None):
+        """``n_steps`` closed-loop steps on the device as one engine call
+        (``OptimizeEngine.rollout_policy``): ``policy`` (a
+        ``custom_envs_amd.policy.MlpPolicy``) picks every action from the
+        previous observation, starting from the one this env last returned
+        (reset, step or a previous collect).  ``noise``: ``[K][E][A]`` N(0,1)
+        device tensor; None draws it (one ``torch.randn``); False runs the
+        deterministic policy.  Returns device tensors: ``obs [K][E][D]`` (the
+        observation each action was chosen from), ``actions``,
+        ``env_actions`` (clipped, what the env read), ``values``,
+        ``neglogps``, ``rewards``, ``dones``, ``last_obs``, ``last_values``
+        (one extra forward, for bootstrapping) and the info fields
+        ``objective``, ``accuracy``, ``episode_len``.  An attached monitor
+        sees the K records in order afterwards (one device-to-host copy)."""
+        from custom_envs_amd.vectorize.collect import host_records, run_collect
+        if self.monitor is not None:
+            self.monitor.check_step()
+        result, fields = run_collect(self.engine, policy, n_steps, self._last_obs, noise,
+                                     self.num_envs)
+        self._last_obs = result['last_obs']
+        k = int(n_steps)
+        if self.monitor is not None:
+            host = host_records(fields)
+            for t in range(k):
+                infos = LazyInfos(host['objective'][t], host['accuracy'][t], host['reward'][t],
+                                  host['episode_len'][t])
+                self.monitor.step(host['reward'][t], host['done'][t].astype(bool), infos,
+                                  host['obs'][t])
+            dones, ep_len = host['done'][k - 1].astype(bool), host['episode_len'][k - 1]
+        else:
+            dones = result['dones'][k - 1].cpu().numpy().astype(bool)
+            ep_len = result['episode_len'][k - 1].cpu().numpy()
+        self.current_step[:] = np.where(dones, 0, ep_len)
+        return result
 
     def close(self):
         if not self.closed:

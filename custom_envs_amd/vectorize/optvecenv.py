@@ -147,6 +147,7 @@ class OptVecEnv:
         self.waiting = False
         request = _batch_request(environment_fns)
         self._engine = self._host = self.monitor = None
+        self._last_obs = None      # what collect() starts from (engine path)
         if request is not None:
             from custom_envs_amd.multi_engine import create_engine
             from custom_envs_amd.utils.utils_logging import VecMonitor
@@ -219,6 +220,7 @@ class OptVecEnv:
             infos = [i for group in infos for i in group]
         for callback in self.callbacks:
             callback(states, rewards, terminals, infos)
+        self._last_obs = states
         return states, rewards, terminals, infos
 
     def step(self, actions):
@@ -229,9 +231,38 @@ class OptVecEnv:
         if self._engine is not None:
             if self.monitor is not None:
                 self.monitor.reset()
-            return self._engine.reset()
+            self._last_obs = self._engine.reset()
+            return self._last_obs
         groups = self._host._broadcast('reset', None)
         return np.stack([o for group in groups for o in group])
+
+    def collect(self, policy, n_steps, noise=None):
+        """``n_steps`` closed-loop steps on the device as one engine call
+        (``MultiOptEngine.rollout_policy``), one policy row per (env, agent)
+        row, starting from the observation last returned; see
+        ``GPUVecEnv.collect``.  Returns device tensors ``obs [K][rows][3H]``,
+        ``actions``, ``env_actions``, ``values``, ``neglogps``, ``rewards``,
+        ``dones``, ``last_obs``, ``last_values``, ``info [K][E][14]`` and
+        ``episode_len``.  An attached monitor sees the K records in order
+        afterwards; the step callbacks are not called.  The host path (envs
+        that do not batch onto the engine) raises ``NotImplementedError``."""
+        if self._engine is None:
+            raise NotImplementedError('collect() needs the engine-backed OptVecEnv (every factory '
+                                      'the same MultiOptLRs-v0 spec)')
+        from custom_envs_amd.vectorize.collect import host_records, run_collect
+        if self.monitor is not None:
+            self.monitor.check_step()
+        result, fields = run_collect(self._engine, policy, n_steps, self._last_obs, noise,
+                                     self._engine.rows)
+        self._last_obs = result['last_obs']
+        if self.monitor is not None:
+            host, P = host_records(fields), self._engine.n_params
+            for t in range(int(n_steps)):
+                env_rewards, env_dones = host['reward'][t][::P], host['done'][t][::P].astype(bool)
+                infos = _RowInfos(host['info'][t], env_rewards, env_dones, host['episode_len'][t],
+                                  P, {})
+                self.monitor.step(env_rewards, env_dones, infos.per_env())
+        return result
 
     def get_attr(self, attr_name, indices=None):
         if self._engine is None:

@@ -68,6 +68,15 @@
  *   ce_nn_get_state / ce_nn_set_stream / ce_nn_destroy / ce_nn_n_params:
  *                    as for ce_multi_*.
  *
+ * The agent's policy on the device (stable-baselines MlpPolicy as PPO2 / A2C run
+ * it, run_multiagent_exp_single.py:37-49):
+ *   ce_policy_create / _destroy / _n_params / _set_params / _set_bounds
+ *                    the actor-critic network, its flat parameters and bounds
+ *   ce_policy_forward  one fused launch: action, env_action, neglogp, value
+ *   ce_rollout_policy / ce_multi_rollout_policy
+ *                    K x (policy forward, VecEnv.step) from one call, the
+ *                    runner's inner loop with no host work between steps
+ *
  * Conventions
  *   - Every function returns CE_OK (0) or a negative ce_status; nothing
  *     throws across the ABI.  ce_last_error() returns a thread-local message.
@@ -377,6 +386,85 @@ int ce_nn_host_outputs(ce_nn_engine *eng, ce_multi_outputs *view);
    of each current row); any pointer may be NULL */
 int ce_nn_get_state(ce_nn_engine *eng, float *theta, float *gprev, int32_t *step,
                     int32_t *cursor, int32_t *order);
+
+/* ------------------------------------------------------------------------
+ * The agent's policy on the device: stable-baselines' MlpPolicy as PPO2 / A2C
+ * run it (run_multiagent_exp_single.py:37-49; net_arch = [dict(pi=[...],
+ * vf=[...])], tanh), one fused launch per forward (policy_kernels.h):
+ *   mean    = tanh-MLP_pi(obs) . Wmu + bmu            [A]
+ *   value   = tanh-MLP_vf(obs) . Wv + bv              (a separate network of
+ *                                                      the same hidden widths)
+ *   action  = mean + exp(logstd) * noise              (noise: caller-supplied
+ *             N(0,1) block, or NULL: action = mean; there is no device RNG)
+ *   env_action = min(max(action, low), high)          (what the env step reads;
+ *             action stays unclipped, as SB's runner stores it)
+ *   neglogp = 0.5 sum noise^2 + sum logstd + 0.5 A log(2 pi)   (from the noise
+ *             itself, not from (action - mean) / std; sum noise^2 = 0 for NULL)
+ * Limits: 1..3 hidden layers, each width a multiple of 32 up to 128,
+ * obs_dim <= 128, act_dim <= 64; anything else is CE_EUNSUPPORTED (the
+ * reference's default 7x7-image Optimize shape, obs_dim 981, is out of scope).
+ * Every argument check of every ce_policy_* / ce_*rollout_policy call happens
+ * before its first HIP call.
+ */
+typedef struct ce_policy ce_policy;
+
+typedef struct ce_policy_config {
+    int32_t abi_version; /* CE_ABI_VERSION                                   */
+    int32_t device;      /* HIP device ordinal                               */
+    int32_t obs_dim;     /* D <= 128                                         */
+    int32_t act_dim;     /* A <= 64                                          */
+    int32_t n_hidden;    /* hidden layers per network, 1..3                  */
+    int32_t hidden[4];   /* their widths (multiples of 32, <= 128)           */
+} ce_policy_config;
+
+/* Device pointers; all four must be set. */
+typedef struct ce_policy_outputs {
+    float *action;     /* [rows][A] unclipped sample                        */
+    float *env_action; /* [rows][A] clipped to the bounds                   */
+    float *neglogp;    /* [rows]                                            */
+    float *value;      /* [rows]                                            */
+} ce_policy_outputs;
+
+/* Host-only: the length of the flat float32 parameter vector
+ *   pi network [W1[D][h1], b1, ..., Wmu[h][A], bmu],
+ *   vf network [W1, b1, ..., Wv[h][1], bv], logstd[A]
+ * (kernels row-major [in][out]), or a negative ce_status.  No GPU. */
+int ce_policy_n_params(const ce_policy_config *cfg);
+int ce_policy_create(const ce_policy_config *cfg, ce_policy **out);
+void ce_policy_destroy(ce_policy *p);
+/* n must equal ce_policy_n_params.  Host pointer: synchronises before
+ * returning.  CE_PTR_DEVICE: `flat` is a device pointer and the refresh is
+ * stream-ordered on hip_stream (one repacking launch, no host round trip);
+ * forwards that must see it run on the same stream or after a sync. */
+int ce_policy_set_params(ce_policy *p, const float *flat, int64_t n, uint32_t flags,
+                         void *hip_stream);
+/* Host pointers low[A], high[A] (NULL: unbounded on that side; the default).
+ * Synchronous. */
+int ce_policy_set_bounds(ce_policy *p, const float *low, const float *high);
+/* One stream-ordered launch over `rows` observation rows [rows][D] (device
+ * pointers; noise [rows][A] or NULL); any rows >= 1, any engine's obs. */
+int ce_policy_forward(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+                      const ce_policy_outputs *out, void *hip_stream);
+/* A K-step closed-loop rollout as one call: for t = 0..k-1, on the engine's
+ * stream, (1) the policy reads obs0 (t = 0) or env record t-1's obs and
+ * writes policy record t (pout advanced by t * pout_step_bytes; noise block
+ * t at noise + t * noise_stride elements, noise may be NULL); (2) the env
+ * steps with record t's env_action -- the same per-step kernel ce_step_async
+ * launches, bit-equal to the unfused sequence -- and writes env record t
+ * (out advanced by t * out_step_bytes; obs is the observation after the step,
+ * on done the auto-reset observation).  No host work between steps.
+ * CE_ESTATE before the first reset; CE_EINVAL with compact outputs on, for a
+ * policy whose obs_dim / act_dim are not the engine's (ce_obs_dim /
+ * ce_act_dim; 3 * max_history / 1 for the multi engine), for an obs that is
+ * not 16-byte aligned or step bytes that are not non-negative multiples of 16. */
+int ce_rollout_policy(ce_engine *eng, const ce_policy *p, int32_t k, const float *obs0,
+                      const float *noise, int64_t noise_stride, const ce_outputs *out,
+                      int64_t out_step_bytes, const ce_policy_outputs *pout,
+                      int64_t pout_step_bytes);
+int ce_multi_rollout_policy(ce_multi_engine *eng, const ce_policy *p, int32_t k,
+                            const float *obs0, const float *noise, int64_t noise_stride,
+                            const ce_multi_outputs *out, int64_t out_step_bytes,
+                            const ce_policy_outputs *pout, int64_t pout_step_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,332 @@
+"""The device-side MLP policy, host side: the NumPy statement of its
+semantics, the flat parameter layout, the C ABI's argument checks (all of
+which precede the first HIP call) and the Python validation of
+``rollout_policy`` arguments.  No test here needs a GPU."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from custom_envs_amd import _native
+from custom_envs_amd import policy as pol
+from custom_envs_amd.policy import MlpPolicy, forward_numpy, params_layout
+
+
+def _cfg(obs_dim=5, act_dim=2, hidden=(32,), abi=_native.ABI_VERSION):
+    cfg = _native.CePolicyConfig(abi_version=abi, device=0, obs_dim=obs_dim, act_dim=act_dim,
+                                 n_hidden=len(hidden))
+    for i, h in enumerate(hidden):
+        cfg.hidden[i] = h
+    return cfg
+
+
+def _random_params(rs, layout):
+    return {name: rs.normal(0, 0.5, shape) for name, (_, shape) in layout.items()}
+
+
+# ---------------------------------------------------------------- forward_numpy
+def test_forward_numpy_matches_an_independent_mlp():
+    rs = np.random.RandomState(0)
+    D, H, A, rows = 5, 32, 2, 7
+    layout = params_layout(D, A, (H,))
+    p = _random_params(rs, layout)
+    obs, noise = rs.normal(0, 2, (rows, D)), rs.normal(0, 1, (rows, A))
+    low, high = np.full(A, -0.5), np.full(A, 0.5)
+    got = forward_numpy(obs, noise, p, hidden=(H,), low=low, high=high)
+    # the few-line restatement, written out per row
+    for r in range(rows):
+        mean = np.tanh(obs[r] @ p['pi/w0'] + p['pi/b0']) @ p['pi/w_out'] + p['pi/b_out']
+        value = (np.tanh(obs[r] @ p['vf/w0'] + p['vf/b0']) @ p['vf/w_out'] + p['vf/b_out'])[0]
+        action = mean + np.exp(p['logstd']) * noise[r]
+        neglogp = 0.5 * np.sum(noise[r] ** 2) + p['logstd'].sum() + 0.5 * A * np.log(2 * np.pi)
+        np.testing.assert_allclose(got['mean'][r], mean, rtol=1e-13, atol=1e-13)
+        np.testing.assert_allclose(got['action'][r], action, rtol=1e-13, atol=1e-13)
+        np.testing.assert_allclose(got['env_action'][r], np.clip(action, low, high), rtol=1e-13)
+        np.testing.assert_allclose(got['value'][r], value, rtol=1e-13, atol=1e-13)
+        np.testing.assert_allclose(got['neglogp'][r], neglogp, rtol=1e-13)
+    # neglogp is the Gaussian's: (action - mean) / std gives the same number
+    z = (got['action'] - got['mean']) / np.exp(p['logstd'])
+    np.testing.assert_allclose(got['neglogp'], 0.5 * np.sum(z * z, axis=1) + p['logstd'].sum()
+                               + 0.5 * A * np.log(2 * np.pi), rtol=1e-12)
+    # without noise: the mean, and the constant
+    det = forward_numpy(obs, None, p, hidden=(H,))
+    assert np.array_equal(det['action'], det['mean'])
+    np.testing.assert_allclose(det['neglogp'], p['logstd'].sum() + 0.5 * A * np.log(2 * np.pi))
+    # the flat vector is the same parameters
+    flat = pol.dict_to_flat(p, layout, np.float64)
+    again = forward_numpy(obs, noise, flat, hidden=(H,), low=low, high=high)
+    for key in got:
+        assert np.array_equal(got[key], again[key]), key
+
+
+# ----------------------------------------------------------------------- layout
+@pytest.mark.parametrize('shape', [(5, 2, (32,)), (41, 20, (64, 64)), (128, 64, (128, 128, 128)),
+                                   (15, 1, (64, 32))])
+def test_layout_round_trips_and_matches_the_library(shape):
+    D, A, hidden = shape
+    layout = params_layout(D, A, hidden)
+    n = pol.layout_size(layout)
+    flat = np.arange(n, dtype=np.float32)
+    d = pol.flat_to_dict(flat, layout)
+    assert list(d) == list(layout)
+    assert d['pi/w0'].shape == (D, hidden[0]) and d['vf/w_out'].shape == (hidden[-1], 1)
+    assert d['logstd'].shape == (A,) and d['logstd'][-1] == n - 1        # logstd is last
+    assert d['pi/w0'][1, 0] == hidden[0]                                 # row-major [in][out]
+    assert np.array_equal(pol.dict_to_flat(d, layout), flat)
+    offsets = [off for off, _ in layout.values()]
+    assert offsets == sorted(offsets) and offsets[0] == 0
+    lib = _native.load()
+    cfg = _cfg(D, A, hidden)
+    assert lib.ce_policy_n_params(ctypes.byref(cfg)) == n
+    spec = MlpPolicy(D, A, hidden, device=None)      # shape only: no GPU
+    assert spec.n_params == n and spec.params_layout() == layout
+
+
+# ------------------------------------------------------------- C ABI, no device
+def test_bad_abi_version_is_einval():
+    lib = _native.load()
+    handle = ctypes.c_void_p()
+    cfg = _cfg(abi=999)
+    assert lib.ce_policy_create(ctypes.byref(cfg), ctypes.byref(handle)) == _native.CE_EINVAL
+    assert b'ABI' in lib.ce_last_error()
+    assert lib.ce_policy_n_params(ctypes.byref(cfg)) == _native.CE_EINVAL
+    assert not handle.value
+
+
+@pytest.mark.parametrize('change, names', [
+    (dict(hidden=(48,)), (b'48', b'multiple of 32')),
+    (dict(hidden=(160,)), (b'160', b'128')),
+    (dict(obs_dim=129), (b'obs_dim', b'129', b'128')),
+    (dict(act_dim=65), (b'act_dim', b'65', b'64')),
+    (dict(hidden=(32, 32, 32, 32)), (b'hidden layers', b'3')),
+])
+def test_unsupported_shapes_name_the_limit(change, names):
+    lib = _native.load()
+    handle = ctypes.c_void_p()
+    cfg = _cfg(**change)
+    assert lib.ce_policy_create(ctypes.byref(cfg), ctypes.byref(handle)) == _native.CE_EUNSUPPORTED
+    msg = lib.ce_last_error()
+    for name in names:
+        assert name in msg, msg
+    assert not handle.value
+    assert lib.ce_policy_n_params(ctypes.byref(cfg)) == _native.CE_EUNSUPPORTED
+    with pytest.raises(_native.NativeEngineError, match='CE_EUNSUPPORTED'):
+        MlpPolicy(change.get('obs_dim', 5), change.get('act_dim', 2), change.get('hidden', (32,)),
+                  device=None)
+
+
+def test_null_pointers_are_einval():
+    lib = _native.load()
+    handle = ctypes.c_void_p()
+    cfg = _cfg()
+    E = _native.CE_EINVAL
+    assert lib.ce_policy_create(None, ctypes.byref(handle)) == E
+    assert lib.ce_policy_create(ctypes.byref(cfg), None) == E
+    assert lib.ce_policy_n_params(None) == E
+    buf = np.zeros(4, np.float32)
+    outs = _native.CePolicyOutputs(action=buf.ctypes.data, env_action=buf.ctypes.data,
+                                   neglogp=buf.ctypes.data, value=buf.ctypes.data)
+    assert lib.ce_policy_set_params(None, buf.ctypes.data, 4, 0, None) == E
+    assert lib.ce_policy_set_bounds(None, None, None) == E
+    assert lib.ce_policy_forward(None, buf.ctypes.data, None, 1, ctypes.byref(outs), None) == E
+    assert b'null' in lib.ce_last_error()
+    eo, mo = _native.CeOutputs(), _native.CeMultiOutputs()
+    assert lib.ce_rollout_policy(None, None, 1, buf.ctypes.data, None, 0, ctypes.byref(eo), 0,
+                                 ctypes.byref(outs), 0) == E
+    assert lib.ce_multi_rollout_policy(None, None, 1, buf.ctypes.data, None, 0, ctypes.byref(mo),
+                                       0, ctypes.byref(outs), 0) == E
+    lib.ce_policy_destroy(None)      # a no-op
+
+
+# ----------------------------------------- Python validation of rollout_policy
+E_ENVS, P_ACT, K_STEPS = 3, 8, 4
+OBS_DIM = 2 * P_ACT + 1
+
+
+def _spec():
+    """OptimizeEngine.output_fields() of an engine with act_dim 8."""
+    return [('obs', torch.float32, 1, (OBS_DIM,)), ('reward', torch.float32, 1, ()),
+            ('done', torch.uint8, 1, ()), ('objective', torch.float32, 1, ()),
+            ('accuracy', torch.float32, 1, ()), ('episode_len', torch.int32, 1, ())]
+
+
+def _records(spec, k, rec=2048):
+    """[k] records in one CPU byte buffer, laid out as alloc_rollout does."""
+    buf = torch.zeros(k * rec, dtype=torch.uint8)
+    fields, off = {}, 0
+    for name, dtype, rows, tail in spec:
+        size = torch.empty((), dtype=dtype).element_size()
+        inner = (E_ENVS * rows,) + tuple(tail)
+        strides = [1] * len(inner)
+        for i in range(len(inner) - 2, -1, -1):
+            strides[i] = strides[i + 1] * inner[i + 1]
+        fields[name] = buf.view(dtype).as_strided((k,) + inner, (rec // size,) + tuple(strides),
+                                                  off // size)
+        off += -(-int(np.prod(inner)) * size // 256) * 256
+    assert off <= rec
+    return fields
+
+
+def _policy_records(k, rec=512):
+    buf = torch.zeros(k * rec // 4, dtype=torch.float32)
+    return {'action': buf.as_strided((k, E_ENVS, P_ACT), (rec // 4, P_ACT, 1), 0),
+            'env_action': buf.as_strided((k, E_ENVS, P_ACT), (rec // 4, P_ACT, 1), 32),
+            'neglogp': buf.as_strided((k, E_ENVS), (rec // 4, 1), 64),
+            'value': buf.as_strided((k, E_ENVS), (rec // 4, 1), 96)}
+
+
+def _validate(policy=None, k=K_STEPS, obs0=None, noise='default', fields=None, rec=2048,
+              pfields=None, prec=512):
+    policy = policy or MlpPolicy(OBS_DIM, P_ACT, (32,), device=None)
+    obs0 = torch.zeros(E_ENVS, OBS_DIM) if obs0 is None else obs0
+    if isinstance(noise, str):
+        noise = torch.zeros(K_STEPS, E_ENVS, P_ACT)
+    fields = _records(_spec(), K_STEPS) if fields is None else fields
+    pfields = _policy_records(K_STEPS) if pfields is None else pfields
+    return pol.validate_rollout(_spec(), E_ENVS, E_ENVS, OBS_DIM, P_ACT, 0, k, policy, obs0,
+                                noise, fields, rec, pfields, prec)
+
+
+def test_rollout_validation_reaches_the_device_check_last():
+    """Well-formed CPU tensors pass every check but the last one, the device's
+    (so the rejections below are each the named fault, not this one)."""
+    with pytest.raises(ValueError, match='must be on device cuda:0'):
+        _validate()
+
+
+def test_rollout_validation_rejects_wrong_dtype():
+    fields = _records(_spec(), K_STEPS)
+    fields['reward'] = fields['reward'].to(torch.float64)
+    with pytest.raises(ValueError, match='reward must have dtype torch.float32'):
+        _validate(fields=fields)
+    pfields = _policy_records(K_STEPS)
+    pfields['value'] = pfields['value'].to(torch.float16)
+    with pytest.raises(ValueError, match='value must have dtype float32'):
+        _validate(pfields=pfields)
+    with pytest.raises(ValueError, match='obs0 must have dtype float32'):
+        _validate(obs0=torch.zeros(E_ENVS, OBS_DIM, dtype=torch.float64))
+    with pytest.raises(ValueError, match='noise must have dtype float32'):
+        _validate(noise=torch.zeros(K_STEPS, E_ENVS, P_ACT, dtype=torch.int32))
+
+
+def test_rollout_validation_rejects_non_contiguous():
+    fields = _records(_spec(), K_STEPS)
+    wide = torch.zeros(K_STEPS, E_ENVS, 2 * OBS_DIM)
+    fields['obs'] = wide[:, :, ::2]                      # right shape, strided rows
+    assert fields['obs'].shape == (K_STEPS, E_ENVS, OBS_DIM)
+    with pytest.raises(ValueError, match='record'):
+        _validate(fields=fields)
+    fields = _records(_spec(), K_STEPS)
+    base = fields['obs']
+    fields['obs'] = base.as_strided(base.shape, (base.stride(0), 1, E_ENVS), base.storage_offset())
+    with pytest.raises(ValueError, match='obs: every record must be contiguous'):
+        _validate(fields=fields)
+    with pytest.raises(ValueError, match='obs0 must be contiguous'):
+        _validate(obs0=torch.zeros(OBS_DIM, E_ENVS).t())
+    with pytest.raises(ValueError, match='noise must be contiguous'):
+        _validate(noise=torch.zeros(K_STEPS, P_ACT, E_ENVS).transpose(1, 2))
+    pfields = _policy_records(K_STEPS)
+    a = pfields['action']
+    pfields['action'] = a.as_strided(a.shape, (a.stride(0), 1, E_ENVS), 0)
+    with pytest.raises(ValueError, match='action: every record must be contiguous'):
+        _validate(pfields=pfields)
+
+
+def test_rollout_validation_rejects_too_few_records():
+    with pytest.raises(ValueError, match='holds 3 records, the call writes 4'):
+        _validate(fields=_records(_spec(), K_STEPS - 1))
+    with pytest.raises(ValueError, match='policy output action holds 3 records'):
+        _validate(pfields=_policy_records(K_STEPS - 1))
+    with pytest.raises(ValueError, match='noise must be'):
+        _validate(noise=torch.zeros(K_STEPS - 1, E_ENVS, P_ACT))
+    with pytest.raises(ValueError, match='k must be >= 1'):
+        _validate(k=0)
+
+
+def test_rollout_validation_rejects_wrong_record_stride():
+    with pytest.raises(ValueError, match="record_bytes 4096 is not field obs's record stride"):
+        _validate(rec=4096)
+    with pytest.raises(ValueError, match="policy record_bytes 1024 is not output action's record"):
+        _validate(prec=1024)
+    with pytest.raises(ValueError, match='multiple of 16'):
+        _validate(prec=1000)
+
+
+def test_rollout_validation_rejects_mismatched_dims():
+    with pytest.raises(ValueError, match='the policy maps obs_dim 16 -> act_dim 8'):
+        _validate(policy=MlpPolicy(OBS_DIM - 1, P_ACT, (32,), device=None))
+    with pytest.raises(ValueError, match='act_dim 7'):
+        _validate(policy=MlpPolicy(OBS_DIM, P_ACT - 1, (32,), device=None))
+    with pytest.raises(TypeError):
+        _validate(policy=object())
+    with pytest.raises(ValueError, match='obs0 must have shape'):
+        _validate(obs0=torch.zeros(E_ENVS, OBS_DIM + 1))
+    with pytest.raises(ValueError, match='records have shape'):
+        _validate(fields=_records([(n, d, r, (OBS_DIM + 2,) if n == 'obs' else t)
+                                   for n, d, r, t in _spec()], K_STEPS))
+
+
+def test_nn_engine_and_host_path_refuse():
+    """NNMultiEngine has no K-step closed-loop form; the host-path OptVecEnv
+    has no engine to collect on."""
+    from custom_envs_amd.multi_engine import NNMultiEngine
+    with pytest.raises(_native.NativeEngineError):
+        NNMultiEngine.rollout_policy(object.__new__(NNMultiEngine), 1, None, None, None, None, 0, None)
+    from custom_envs_amd.vectorize.optvecenv import OptVecEnv
+    env = object.__new__(OptVecEnv)
+    env._engine = None
+    with pytest.raises(NotImplementedError):
+        env.collect(None, 4)
+
+
+# ------------------------------------- the closed-loop test shapes stay finite
+@pytest.mark.parametrize('name', sorted(__import__('policy_cases').ROLLOUT_SHAPES))
+def test_rollout_shapes_stay_finite_on_the_oracle(name):
+    """The GPU closed-loop tests (test_gpu_policy.py) assert finite
+    observations; here the same seeds, policies and noise drive the CPU oracle
+    envs through forward_numpy for the same 10 steps."""
+    import policy_cases as pc
+    kind, kw = pc.ROLLOUT_SHAPES[name]
+    rows, D, A = pc.rollout_dims(name)
+    params, noise = pc.rollout_policy_inputs(name)
+    if kind == 'optimize':
+        from oracle.optimize import Optimize
+        features, targets = pc.rollout_dataset(name)
+        envs = []
+        for seed in kw['seeds']:
+            env = Optimize(features, targets, batch_size=kw['batch_size'], max_steps=4)
+            env.seed(seed)
+            envs.append(env)
+        obs = np.stack([env.reset() for env in envs])
+        resets = 0
+        for t in range(pc.ROLLOUT_K):
+            out = forward_numpy(obs.astype(np.float32), noise[t], params, hidden=pc.ROLLOUT_HIDDEN)
+            nxt = []
+            for env, a in zip(envs, out['env_action'].astype(np.float32)):
+                o, reward, done, _ = env.step(a)
+                assert np.isfinite(reward)
+                if done:
+                    o = env.reset()
+                    resets += 1
+                nxt.append(o)
+            obs = np.stack(nxt)
+            assert obs.shape == (rows, D) and np.isfinite(obs).all(), t
+        assert resets == 2 * len(envs)
+    else:
+        from oracle.multioptlrs import MultiOptLRs, OptEnvRunner
+        P = rows // kw['num_envs']
+        runners = [OptEnvRunner(MultiOptLRs(P, max_batches=4)) for _ in range(kw['num_envs'])]
+        obs = np.concatenate([np.stack(r.reset()) for r in runners])
+        for t in range(pc.ROLLOUT_K):
+            out = forward_numpy(obs.astype(np.float32), noise[t], params, hidden=pc.ROLLOUT_HIDDEN)
+            acts = out['env_action'].astype(np.float32).reshape(kw['num_envs'], P, 1)
+            nxt = []
+            for runner, a in zip(runners, acts):
+                states, rewards, dones, _ = runner.step(list(a))
+                assert np.isfinite(rewards[0])
+                if dones[0]:
+                    states = runner.reset()
+                nxt.append(np.stack(states))
+            obs = np.concatenate(nxt)
+            assert obs.shape == (rows, D) and np.isfinite(obs).all(), t
