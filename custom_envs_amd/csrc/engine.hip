@@ -3,11 +3,12 @@
 // Host responsibilities: own the device copy of the dataset and the per-env
 // state (struct-of-arrays, one contiguous [E][P] slab per quantity so a
 // wave's P values are one coalesced segment), stage host actions/outputs
-// through pinned buffers, and launch one fused step kernel per VecEnv.step
-// (optimize_kernels.h).  The env RNG is native (seeding.cpp): W0 and the
-// reset permutation are drawn once per seed and uploaded, because
-// use_random_state never advances the env RNG (custom_envs/utils/
-// utils_math.py:9-22), so every reset replays the same draws.
+// through pinned buffers (engine_host.h, shared with the other engines), and
+// launch one fused step kernel per VecEnv.step (optimize_kernels.h).  The
+// env RNG is native (seeding.cpp): W0 and the reset permutation are drawn
+// once per seed and uploaded, because use_random_state never advances the
+// env RNG (custom_envs/utils/utils_math.py:9-22), so every reset replays the
+// same draws.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -20,13 +21,12 @@
 #include <algorithm>
 #include <thread>
 
-#include "common.h"
+#include "engine_host.h"
 #include "mlp_kernels.h"
 #include "net_engine.h"
 #include "optimize_kernels.h"
 #include "optimize_mfma.h"
 #include "optimize_pair_kernel.h"
-#include "policy_engine.h"
 #include "seeding.h"
 
 namespace {
@@ -101,8 +101,10 @@ struct ce_engine {
     size_t tsize = 8;  // element size of W / W0
     size_t gsize = 8;  // element size of G (grad_hist)
     const KernelEntry *kern = nullptr;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    // stream, staging buffers, step_many bookkeeping; host.compact:
+    // ce_set_compact_outputs; host.persist: the persistent K-step kernel
+    // (optimize_lr_persist.h) is available for the shape
+    ce::Host<ce_outputs> host;
     // device state
     void *X = nullptr;
     float *Xs = nullptr;   // MLP: dataset in MFMA operand order (mlp_kernels.h)
@@ -111,49 +113,21 @@ struct ce_engine {
     double *L = nullptr;
     int32_t *step = nullptr;
     int32_t *perm = nullptr, *order = nullptr, *order_sel = nullptr;
-    float *d_act = nullptr;
-    // outputs: one region on the device, a pinned mirror on the host
-    size_t off[6] = {0};
-    size_t out_bytes = 0;
-    char *d_out = nullptr;
-    char *h_out = nullptr;
-    float *h_act = nullptr;
-    bool was_reset = false;
     bool staged = false;      // dataset fits the per-block LDS stage
     StepFn pair = nullptr;    // two-envs-per-wave step kernel, when the shape has one
     int gen_ft = 0;           // > 0: the runtime-shape MFMA kernel with this many feature tiles
     bool lr_mfma = false;     // two-class full-batch MFMA kernel (optimize_lr_mfma.h)
     std::string kernel_name;  // what ce_step_kernel reports
     size_t stage_bytes = 0;
-    ce::GraphCache graphs;   // ce_step_many
-    // ce_step_many: k <= many_direct steps are plain launches, longer runs a
-    // cached hipGraph.  Measured (4096 envs, pair kernel): 20 steps 7.7 us
-    // per step direct vs 8.0 graph; 100 and 2000 steps equal.
-    int many_direct = 32;
     int lr_waves = 0;         // CE_LR_WAVES: force the two-class MFMA kernel's wave count
     int gen_tail = 1;         // CE_GEN_TAIL=0: the runtime-shape kernel's last feature on MFMA too
     int gen_cat = 1;          // CE_GEN_CAT=0: full batch on the one-env-per-wave kernel
     int lr_mode_cap = 3;      // CE_LR_MODE: cap on the two-class MFMA kernel's row-loop mode
-    bool compact = false;     // ce_set_compact_outputs: device-pointer calls write the compact form
-    // the persistent K-step kernel (optimize_lr_persist.h): available for the
-    // shape, and chosen (ce_set_persistent; CE_PERSIST=0 at create turns it off)
-    bool persist = false, persist_on = true;
     std::string many_name;    // what ce_step_many_kernel reports when persistent
     unsigned long long *diag = nullptr;   // CE_DIAG builds: per-wave phase stamps
 };
 
 namespace {
-
-ce_outputs region_view(const ce_engine *e, char *base) {
-    ce_outputs o;
-    o.obs = reinterpret_cast<float *>(base + e->off[0]);
-    o.reward = reinterpret_cast<float *>(base + e->off[1]);
-    o.objective = reinterpret_cast<float *>(base + e->off[2]);
-    o.accuracy = reinterpret_cast<float *>(base + e->off[3]);
-    o.episode_len = reinterpret_cast<int32_t *>(base + e->off[4]);
-    o.done = reinterpret_cast<uint8_t *>(base + e->off[5]);
-    return o;
-}
 
 template <typename T>
 ce::StepArgs<T> make_args(const ce_engine *e, const float *act, const ce_outputs &o,
@@ -230,8 +204,6 @@ ce::MlpArgs make_mlp_args(const ce_engine *e, const float *act, const ce_outputs
     return a;
 }
 
-// compact: the caller's device outputs are in the compact form
-// (ce_set_compact_outputs; only the two-class MFMA path writes it)
 ce::NetArgs make_net_args(const ce_engine *e, const float *act, const ce_outputs &o) {
     ce::NetArgs a{};
     a.E = e->cfg.num_envs;
@@ -264,6 +236,8 @@ ce::NetArgs make_net_args(const ce_engine *e, const float *act, const ce_outputs
     return a;
 }
 
+// compact: the caller's device outputs are in the compact form
+// (ce_set_compact_outputs; only the two-class MFMA path writes it)
 int launch(const ce_engine *e, bool reset, const float *act, const ce_outputs &o,
            hipStream_t stream, bool compact = false) {
     if (e->net) {
@@ -319,62 +293,52 @@ int launch(const ce_engine *e, bool reset, const float *act, const ce_outputs &o
     return CE_OK;
 }
 
-// The outputs of step s of a strided run: every pointer out_step bytes per step.
-ce_outputs advance(const ce_outputs &o, int64_t bytes) {
-    auto adv = [bytes](auto *p) { return p ? reinterpret_cast<decltype(p)>(reinterpret_cast<char *>(p) + bytes) : p; };
-    ce_outputs r;
-    r.obs = adv(o.obs);
-    r.reward = adv(o.reward);
-    r.done = adv(o.done);
-    r.objective = adv(o.objective);
-    r.accuracy = adv(o.accuracy);
-    r.episode_len = adv(o.episode_len);
-    return r;
-}
-
-// k steps of every env, actions s * stride apart, outputs s * out_step bytes
-// apart (one launch per step).
-int launch_steps(const ce_engine *e, int k, const float *actions, int64_t stride,
-                 const ce_outputs &o, int64_t out_step = 0) {
-    for (int s = 0; s < k; ++s) {
-        const int rc = launch(e, false, actions + s * stride, out_step ? advance(o, s * out_step) : o,
-                              e->stream, e->compact);
-        if (rc != CE_OK) return rc;
+// what this engine launches (engine_host.h)
+struct OptOps {
+    static int step(ce_engine *e, const float *act, const ce_outputs &o, bool device_form) {
+        return launch(e, false, act, o, e->host.stream, device_form && e->host.compact);
     }
-    return CE_OK;
-}
-
-// The k steps as ONE launch of the persistent kernel (optimize_lr_persist.h).
-int launch_persist(const ce_engine *e, int k, const float *actions, int64_t stride,
-                   const ce_outputs &o, int64_t out_step) {
-    const auto a = make_args<double>(e, actions, o, e->compact);
-    ce::lr_launch_persist(a, k, stride, out_step, e->stream);
-    return CE_OK;
-}
+    static int reset(ce_engine *e, const ce_outputs &o, bool device_form) {
+        return launch(e, true, nullptr, o, e->host.stream, device_form && e->host.compact);
+    }
+    // The k steps as ONE launch of the persistent kernel (optimize_lr_persist.h).
+    static int persist(ce_engine *e, int k, const float *act, int64_t stride, const ce_outputs &o,
+                       int64_t out_step) {
+        ce::lr_launch_persist(make_args<double>(e, act, o, e->host.compact), k, stride, out_step,
+                              e->host.stream);
+        return CE_OK;
+    }
+    // one policy row per env
+    static void policy_shape(const ce_engine *e, int *obs_dim, int *act_dim, int64_t *rows) {
+        *obs_dim = e->obs_dim;
+        *act_dim = e->P;
+        *rows = e->cfg.num_envs;
+    }
+};
 
 // Convert host float64 values to a device array of `elem`-byte floats.
 int upload_typed(ce_engine *e, void *dst, const double *src, size_t count, size_t elem) {
     if (elem == sizeof(double)) {
-        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, e->host.stream));
     } else {
         std::vector<float> tmp(count);
         for (size_t i = 0; i < count; ++i) tmp[i] = static_cast<float>(src[i]);
         CE_HIP(hipMemcpyAsync(dst, tmp.data(), count * sizeof(float), hipMemcpyHostToDevice,
-                              e->stream));
-        CE_HIP(hipStreamSynchronize(e->stream));
+                              e->host.stream));
+        CE_HIP(hipStreamSynchronize(e->host.stream));
     }
     return CE_OK;
 }
 
 int download_typed(ce_engine *e, double *dst, const void *src, size_t count, size_t elem) {
     if (elem == sizeof(double)) {
-        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        CE_HIP(hipStreamSynchronize(e->stream));
+        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, e->host.stream));
+        CE_HIP(hipStreamSynchronize(e->host.stream));
     } else {
         std::vector<float> tmp(count);
         CE_HIP(hipMemcpyAsync(tmp.data(), src, count * sizeof(float), hipMemcpyDeviceToHost,
-                              e->stream));
-        CE_HIP(hipStreamSynchronize(e->stream));
+                              e->host.stream));
+        CE_HIP(hipStreamSynchronize(e->host.stream));
         for (size_t i = 0; i < count; ++i) dst[i] = tmp[i];
     }
     return CE_OK;
@@ -384,8 +348,8 @@ int download_typed(ce_engine *e, double *dst, const void *src, size_t count, siz
 int net_download(ce_engine *e, double *dst, const void *img) {
     const size_t E = e->cfg.num_envs, P = e->P, PI = static_cast<size_t>(e->net_geo.Pimg);
     std::vector<float> tmp(E * PI), flat(P);
-    CE_HIP(hipMemcpyAsync(tmp.data(), img, E * PI * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipMemcpyAsync(tmp.data(), img, E * PI * sizeof(float), hipMemcpyDeviceToHost, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     for (size_t i = 0; i < E; ++i) {
         ce::net_image_to_flat(e->net_geo, &tmp[i * PI], flat.data());
         for (size_t p = 0; p < P; ++p) dst[i * P + p] = flat[p];
@@ -400,58 +364,8 @@ int net_upload(ce_engine *e, void *img, const double *src) {
         for (size_t p = 0; p < P; ++p) flat[p] = static_cast<float>(src[i * P + p]);
         ce::net_flat_to_image(e->net_geo, flat.data(), &tmp[i * PI]);
     }
-    CE_HIP(hipMemcpyAsync(img, tmp.data(), E * PI * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
-    return CE_OK;
-}
-
-void copy_out(const ce_engine *e, const ce_outputs &src, const ce_outputs *dst) {
-    const size_t E = e->cfg.num_envs;
-    if (!dst) return;
-    if (dst->obs) std::memcpy(dst->obs, src.obs, E * e->obs_dim * sizeof(float));
-    if (dst->reward) std::memcpy(dst->reward, src.reward, E * sizeof(float));
-    if (dst->done) std::memcpy(dst->done, src.done, E);
-    if (dst->objective) std::memcpy(dst->objective, src.objective, E * sizeof(float));
-    if (dst->accuracy) std::memcpy(dst->accuracy, src.accuracy, E * sizeof(float));
-    if (dst->episode_len) std::memcpy(dst->episode_len, src.episode_len, E * sizeof(int32_t));
-}
-
-// every output pointer set (the compact form may leave done null)
-bool complete(const ce_outputs *o, bool compact = false) {
-    // the compact form has no done (episode_len >= max_steps) and no reward
-    // (-objective: B = N)
-    return o && o->obs && (o->reward || compact) && (o->done || compact) && o->objective &&
-           o->accuracy && o->episode_len;
-}
-
-int do_step(ce_engine *e, const float *actions, const ce_outputs *out, uint32_t flags,
-            bool sync) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_CLEAR_STALE_ERROR();
-    if (!e->was_reset) return fail(CE_ESTATE, "step() before the first reset()");
-    if (!actions) return fail(CE_EINVAL, "null actions");
-    const size_t E = e->cfg.num_envs;
-    if (flags & CE_PTR_DEVICE) {
-        if (e->compact && !out) return fail(CE_EINVAL, "compact outputs need caller buffers");
-        ce_outputs o = out ? *out : region_view(e, e->d_out);
-        if (out && !complete(out, e->compact)) return fail(CE_EINVAL, "device outputs must all be set");
-        const int rc = launch(e, false, actions, o, e->stream, e->compact);
-        if (rc != CE_OK) return rc;
-        CE_HIP(hipGetLastError());
-        if (sync) CE_HIP(hipStreamSynchronize(e->stream));
-        return CE_OK;
-    }
-    std::memcpy(e->h_act, actions, E * e->P * sizeof(float));
-    CE_HIP(hipMemcpyAsync(e->d_act, e->h_act, E * e->P * sizeof(float), hipMemcpyHostToDevice,
-                          e->stream));
-    const int rc = launch(e, false, e->d_act, region_view(e, e->d_out), e->stream);
-    if (rc != CE_OK) return rc;
-    CE_HIP(hipGetLastError());
-    CE_HIP(hipMemcpyAsync(e->h_out, e->d_out, e->out_bytes, hipMemcpyDeviceToHost, e->stream));
-    if (sync) {
-        CE_HIP(hipStreamSynchronize(e->stream));
-        copy_out(e, region_view(e, e->h_out), out);
-    }
+    CE_HIP(hipMemcpyAsync(img, tmp.data(), E * PI * sizeof(float), hipMemcpyHostToDevice, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     return CE_OK;
 }
 
@@ -562,7 +476,14 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
     e->kern = kern;
     e->mlp = mlp;
     e->dims = dims;
-    if (const char *md = std::getenv("CE_MANY_DIRECT")) e->many_direct = std::atoi(md);
+    // ce_step_many: up to 32 steps are plain launches, longer runs a cached
+    // hipGraph.  Measured (4096 envs, pair kernel): 20 steps 7.7 us per step
+    // direct vs 8.0 graph; 100 and 2000 steps equal.
+    e->host.many_direct = 32;
+    // the strided form and the K-step kernel (which stores the observation
+    // block as 16-byte units) take a 16-byte aligned obs only
+    e->host.obs_align = 16;
+    if (const char *md = std::getenv("CE_MANY_DIRECT")) e->host.many_direct = std::atoi(md);
     if (const char *lw = std::getenv("CE_LR_WAVES")) e->lr_waves = std::atoi(lw);
     if (const char *gt = std::getenv("CE_GEN_TAIL")) e->gen_tail = std::atoi(gt);
     if (const char *gc = std::getenv("CE_GEN_CAT")) e->gen_cat = std::atoi(gc);
@@ -595,18 +516,11 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
         return code;
     };
     int rc;
-#define CE_TRY(call)                                                   \
-    do {                                                               \
-        hipError_t err_ = (call);                                      \
-        if (err_ != hipSuccess)                                        \
-            return bail(fail(CE_EHIP, std::string(#call " failed: ") + \
-                                          hipGetErrorString(err_)));   \
-    } while (0)
-    CE_TRY(hipSetDevice(cfg->device));
-    CE_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    e->stream = e->own_stream;
-
     const size_t E = cfg->num_envs, N = cfg->n_rows, F = cfg->n_features, P = e->P;
+    rc = e->host.create(cfg->device, E * P * sizeof(float),
+                        {E * e->obs_dim * sizeof(float), E * sizeof(float), E * sizeof(float),
+                         E * sizeof(float), E * sizeof(int32_t), E});
+    if (rc != CE_OK) return bail(rc);
     if (mlp) {
         CE_TRY(hipMalloc(&e->X, N * F * sizeof(float)));
         if (!net_path) CE_TRY(hipMalloc(&e->Xs, N * F * sizeof(float)));
@@ -640,8 +554,6 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
     }
     CE_TRY(hipMalloc(&e->L, E * sizeof(double)));
     CE_TRY(hipMalloc(&e->step, E * sizeof(int32_t)));
-    CE_TRY(hipMalloc(&e->d_act, E * P * sizeof(float)));
-    CE_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_act), E * P * sizeof(float)));
     if (cfg->batch_size < cfg->n_rows) {
         CE_TRY(hipMalloc(&e->perm, E * N * sizeof(int32_t)));
         CE_TRY(hipMalloc(&e->order, 2 * E * N * sizeof(int32_t)));
@@ -653,21 +565,9 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
         CE_TRY(hipMemcpy(e->perm, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
         CE_TRY(hipMemset(e->order_sel, 0, E * sizeof(int32_t)));
     }
-    size_t off = 0;
-    const size_t sizes[6] = {E * e->obs_dim * sizeof(float), E * sizeof(float), E * sizeof(float),
-                             E * sizeof(float), E * sizeof(int32_t), E};
-    for (int i = 0; i < 6; ++i) {
-        e->off[i] = off;
-        off = ce::align16(off + sizes[i]);
-    }
-    e->out_bytes = off;
-    CE_TRY(hipMalloc(&e->d_out, e->out_bytes));
 #ifdef CE_DIAG
     CE_TRY(hipMalloc(&e->diag, E * ce::kStamps * sizeof(unsigned long long)));
 #endif
-    CE_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_out), e->out_bytes));
-    CE_TRY(hipMemset(e->d_out, 0, e->out_bytes));
-    std::memset(e->h_out, 0, e->out_bytes);
     CE_TRY(hipMemset(e->G, 0, E * P * e->gsize));
     CE_TRY(hipMemset(e->L, 0, E * sizeof(double)));
     CE_TRY(hipMemset(e->step, 0, E * sizeof(int32_t)));
@@ -688,7 +588,7 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
         }
         CE_TRY(hipMemcpy(e->label, labels, N * sizeof(int32_t), hipMemcpyHostToDevice));
         if (net_path) {
-            const ce::NetArgs a = make_net_args(e, nullptr, region_view(e, e->d_out));
+            const ce::NetArgs a = make_net_args(e, nullptr, e->host.region(e->host.d_out));
             if ((rc = ce::net_create(&e->net, a, cfg->device)) != CE_OK) return bail(rc);
             std::string name = "net<";
             for (size_t i = 0; i < dims.size(); ++i) name += (i ? "," : "") + std::to_string(dims[i]);
@@ -697,7 +597,6 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
             e->kernel_name = name + (e->net_geo.wide ? ">:wide" : ">:mfma");
         }
     }
-#undef CE_TRY
     if (e->lr_mfma) {
         std::vector<double> img(ce::lr_image_doubles(cfg->n_features, cfg->n_rows));
         ce::lr_build_image(cfg->n_features, cfg->n_rows, features, labels, img.data());
@@ -706,9 +605,8 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
             return bail(fail(CE_EHIP, "ce_create: dataset upload failed"));
         e->kernel_name = ce::lr_kernel_name(cfg->num_envs, cfg->n_rows, cfg->n_features,
                                             e->lr_waves, e->lr_mode_cap);
-        e->persist = ce::lr_persist_ok(cfg->n_rows);
-        if (e->persist) e->many_name = ce::lr_persist_name(cfg->n_rows, cfg->n_features);
-        if (const char *pe = std::getenv("CE_PERSIST")) e->persist_on = pe[0] != '0';
+        e->host.persist = ce::lr_persist_ok(cfg->n_rows);
+        if (e->host.persist) e->many_name = ce::lr_persist_name(cfg->n_rows, cfg->n_features);
     } else if (e->gen_ft) {
         // [Npad][RS] float64: F features, zeros to 16 FT + 1, the label as a
         // double in the last column; rows N..Npad-1 are zeros with label -1
@@ -775,7 +673,7 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
     std::vector<uint64_t> seeds(E);
     for (size_t i = 0; i < E; ++i) seeds[i] = i;
     if ((rc = ce_seed(e, seeds.data(), static_cast<int32_t>(E))) != CE_OK) return bail(rc);
-    if (hipStreamSynchronize(e->stream) != hipSuccess)
+    if (hipStreamSynchronize(e->host.stream) != hipSuccess)
         return bail(fail(CE_EHIP, "ce_create: sync failed"));
     *out = e;
     return CE_OK;
@@ -783,24 +681,14 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
 
 void ce_destroy(ce_engine *e) {
     if (!e) return;
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    e->graphs.release();
+    e->host.drain();
     ce::net_destroy(e->net);
-    void *dev[] = {e->X, e->Xs, e->label, e->W, e->G, e->W0, e->L, e->step,
-                   e->perm, e->order, e->order_sel, e->d_act, e->d_out, e->diag};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (e->h_out) (void)hipHostFree(e->h_out);
-    if (e->h_act) (void)hipHostFree(e->h_act);
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+    e->host.destroy({e->X, e->Xs, e->label, e->W, e->G, e->W0, e->L, e->step, e->perm, e->order,
+                     e->order_sel, e->diag});
     delete e;
 }
 
-int ce_set_stream(ce_engine *e, void *stream) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    e->stream = stream ? static_cast<hipStream_t>(stream) : e->own_stream;
-    return CE_OK;
-}
+int ce_set_stream(ce_engine *e, void *stream) { return ce::host_set_stream(e, stream); }
 
 int ce_set_compact_outputs(ce_engine *e, int32_t on) {
     if (!e) return fail(CE_EINVAL, "null engine");
@@ -808,8 +696,8 @@ int ce_set_compact_outputs(ce_engine *e, int32_t on) {
         return fail(CE_EUNSUPPORTED, "ce_set_compact_outputs: only the two-class full-batch "
                                      "float64 kernel (" + std::string("optimize_lr_mfma_kernel") +
                                      ") writes the compact form; this engine runs " + e->kernel_name);
-    if (e->compact != (on != 0)) e->graphs.release();   // captured launches carry the form
-    e->compact = on != 0;
+    if (e->host.compact != (on != 0)) e->host.graphs.release();   // captured launches carry the form
+    e->host.compact = on != 0;
     return CE_OK;
 }
 
@@ -841,16 +729,16 @@ int ce_seed(ce_engine *e, const uint64_t *seeds, int32_t n) {
             std::vector<float> img(E * PI);
             for (size_t i = 0; i < E; ++i) ce::net_flat_to_image(e->net_geo, &w0[i * P], &img[i * PI]);
             CE_HIP(hipMemcpyAsync(e->W0, img.data(), E * PI * sizeof(float), hipMemcpyHostToDevice,
-                                  e->stream));
-            CE_HIP(hipStreamSynchronize(e->stream));
+                                  e->host.stream));
+            CE_HIP(hipStreamSynchronize(e->host.stream));
         } else {
             CE_HIP(hipMemcpyAsync(e->W0, w0.data(), E * P * sizeof(float), hipMemcpyHostToDevice,
-                                  e->stream));
+                                  e->host.stream));
         }
         if (with_perm)
             CE_HIP(hipMemcpyAsync(e->perm, perm.data(), E * N * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, e->stream));
-        CE_HIP(hipStreamSynchronize(e->stream));
+                                  hipMemcpyHostToDevice, e->host.stream));
+        CE_HIP(hipStreamSynchronize(e->host.stream));
         return CE_OK;
     }
     std::vector<double> w0(E * P);
@@ -862,195 +750,52 @@ int ce_seed(ce_engine *e, const uint64_t *seeds, int32_t n) {
     if (rc != CE_OK) return rc;
     if (with_perm)
         CE_HIP(hipMemcpyAsync(e->perm, perm.data(), E * N * sizeof(int32_t),
-                              hipMemcpyHostToDevice, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
+                              hipMemcpyHostToDevice, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     return CE_OK;
 }
 
 int ce_reset(ce_engine *e, const ce_outputs *out, uint32_t flags) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_CLEAR_STALE_ERROR();
-    if (flags & CE_PTR_DEVICE) {
-        if (e->compact && !out) return fail(CE_EINVAL, "compact outputs need caller buffers");
-        if (out && !complete(out, e->compact)) return fail(CE_EINVAL, "device outputs must all be set");
-        ce_outputs o = out ? *out : region_view(e, e->d_out);
-        const int rc = launch(e, true, nullptr, o, e->stream, e->compact);
-        if (rc != CE_OK) return rc;
-        CE_HIP(hipGetLastError());
-        e->was_reset = true;
-        return CE_OK;
-    }
-    const int rc = launch(e, true, nullptr, region_view(e, e->d_out), e->stream);
-    if (rc != CE_OK) return rc;
-    CE_HIP(hipGetLastError());
-    CE_HIP(hipMemcpyAsync(e->h_out, e->d_out, e->out_bytes, hipMemcpyDeviceToHost, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
-    e->was_reset = true;
-    if (out && out->obs)
-        std::memcpy(out->obs, region_view(e, e->h_out).obs,
-                    static_cast<size_t>(e->cfg.num_envs) * e->obs_dim * sizeof(float));
-    return CE_OK;
+    return ce::host_reset<OptOps>(e, out, flags);
 }
 
 int ce_step(ce_engine *e, const float *actions, const ce_outputs *out, uint32_t flags) {
-    return do_step(e, actions, out, flags, true);
+    return ce::host_step<OptOps>(e, actions, out, flags, true);
 }
 
 int ce_step_async(ce_engine *e, const float *actions, const ce_outputs *out, uint32_t flags) {
-    return do_step(e, actions, out, flags, false);
+    return ce::host_step<OptOps>(e, actions, out, flags, false);
 }
 
-int ce_wait(ce_engine *e) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_HIP(hipStreamSynchronize(e->stream));
-    return CE_OK;
-}
-
-namespace {
-
-int many_graph(ce_engine *e, int32_t k, const float *actions, int64_t stride,
-               const ce_outputs *out, hipGraphExec_t *exec) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    if (!e->was_reset) return fail(CE_ESTATE, "step_many() before the first reset()");
-    if (k <= 0 || !actions || stride < 0) return fail(CE_EINVAL, "ce_step_many: bad arguments");
-    if (e->compact && !out) return fail(CE_EINVAL, "compact outputs need caller buffers");
-    if (out && !complete(out, e->compact)) return fail(CE_EINVAL, "device outputs must all be set");
-    const ce_outputs o = out ? *out : region_view(e, e->d_out);
-    return e->graphs.get(ce::graph_key(k, 0, actions, stride, e->stream, o), [&] {
-        (void)launch_steps(e, k, actions, stride, o);
-    }, exec);
-}
-
-}  // namespace
-
-namespace {
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// the arguments every k-step form checks
-int many_args_ok(const ce_engine *e, int32_t k, const float *actions, int64_t stride,
-                 const ce_outputs *out) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    if (!e->was_reset) return fail(CE_ESTATE, "step_many() before the first reset()");
-    if (k <= 0 || !actions || stride < 0) return fail(CE_EINVAL, "ce_step_many: bad arguments");
-    if (e->compact && !out) return fail(CE_EINVAL, "compact outputs need caller buffers");
-    if (out && !complete(out, e->compact)) return fail(CE_EINVAL, "device outputs must all be set");
-    return CE_OK;
-}
-
-bool use_persist(const ce_engine *e, const ce_outputs &o) {
-    return e->persist && e->persist_on && aligned16(o.obs);
-}
-
-// The persistent kernel stores the observation block as 16-B units: a
-// caller's misaligned obs is refused, never served by another form while
-// ce_step_many_kernel() names the persistent one
-int persist_obs_ok(const ce_engine *e, const ce_outputs &o) {
-    if (e->persist && e->persist_on && !aligned16(o.obs))
-        return fail(CE_EINVAL, "the persistent K-step kernel needs a 16-byte aligned obs "
-                               "(ce_set_persistent(e, 0) selects the per-step launches)");
-    return CE_OK;
-}
-
-}  // namespace
+int ce_wait(ce_engine *e) { return ce::host_wait(e); }
 
 int ce_step_many(ce_engine *e, int32_t k, const float *actions, int64_t stride,
                  const ce_outputs *out) {
-    if (e && e->persist && e->persist_on) {
-        const int rc = many_args_ok(e, k, actions, stride, out);
-        if (rc != CE_OK) return rc;
-        const ce_outputs o = out ? *out : region_view(e, e->d_out);
-        if (persist_obs_ok(e, o) != CE_OK) return CE_EINVAL;
-        if (use_persist(e, o)) {
-            CE_CLEAR_STALE_ERROR();
-            (void)launch_persist(e, k, actions, stride, o, 0);
-            CE_HIP(hipGetLastError());
-            return CE_OK;
-        }
-    }
-    if (e && k <= e->many_direct) {
-        if (!e->was_reset) return fail(CE_ESTATE, "step_many() before the first reset()");
-        if (k <= 0 || !actions || stride < 0) return fail(CE_EINVAL, "ce_step_many: bad arguments");
-        if (e->compact && !out) return fail(CE_EINVAL, "compact outputs need caller buffers");
-        if (out && !complete(out, e->compact)) return fail(CE_EINVAL, "device outputs must all be set");
-        const ce_outputs o = out ? *out : region_view(e, e->d_out);
-        CE_CLEAR_STALE_ERROR();
-        const int rc = launch_steps(e, k, actions, stride, o);
-        if (rc != CE_OK) return rc;
-        CE_HIP(hipGetLastError());
-        return CE_OK;
-    }
-    hipGraphExec_t exec;
-    const int rc = many_graph(e, k, actions, stride, out, &exec);
-    if (rc != CE_OK) return rc;
-    CE_HIP(hipGraphLaunch(exec, e->stream));
-    return CE_OK;
+    return ce::host_step_many<OptOps>(e, k, actions, stride, out, true);
 }
 
 int ce_step_many_prepare(ce_engine *e, int32_t k, const float *actions, int64_t stride,
                          const ce_outputs *out) {
-    if (e && e->persist && e->persist_on) {   // one launch: nothing to instantiate
-        const int rc = many_args_ok(e, k, actions, stride, out);
-        if (rc != CE_OK) return rc;
-        const ce_outputs o = out ? *out : region_view(e, e->d_out);
-        if (persist_obs_ok(e, o) != CE_OK) return CE_EINVAL;
-        if (use_persist(e, o)) return CE_OK;
-    }
-    hipGraphExec_t exec;
-    return many_graph(e, k, actions, stride, out, &exec);
+    return ce::host_step_many<OptOps>(e, k, actions, stride, out, false);
 }
 
 int ce_step_many_strided(ce_engine *e, int32_t k, const float *actions, int64_t stride,
                          const ce_outputs *out, int64_t out_step) {
-    int rc = many_args_ok(e, k, actions, stride, out);
-    if (rc != CE_OK) return rc;
-    if (!out) return fail(CE_EINVAL, "ce_step_many_strided: needs caller output buffers");
-    if (out_step < 0 || out_step % 16 != 0 || !aligned16(out->obs))
-        return fail(CE_EINVAL, "ce_step_many_strided: obs must be 16-byte aligned and "
-                               "out_step_bytes a non-negative multiple of 16");
-    CE_CLEAR_STALE_ERROR();
-    rc = use_persist(e, *out) ? launch_persist(e, k, actions, stride, *out, out_step)
-                              : launch_steps(e, k, actions, stride, *out, out_step);
-    if (rc != CE_OK) return rc;
-    CE_HIP(hipGetLastError());
-    return CE_OK;
+    return ce::host_step_many_strided<OptOps>(e, k, actions, stride, out, out_step);
 }
 
 int ce_rollout_policy(ce_engine *e, const ce_policy *p, int32_t k, const float *obs0,
                       const float *noise, int64_t noise_stride, const ce_outputs *out,
                       int64_t out_step, const ce_policy_outputs *pout, int64_t pout_step) {
-    if (!e) return fail(CE_EINVAL, "ce_rollout_policy: null engine");
-    if (!out || !complete(out)) return fail(CE_EINVAL, "ce_rollout_policy: device outputs must all be set");
-    if (e->compact)
-        return fail(CE_EINVAL, "ce_rollout_policy: needs the full output form (compact outputs are on)");
-    int rc = ce::policy_rollout_args_ok("ce_rollout_policy", p, e->obs_dim, e->P, k, obs0, noise,
-                                        noise_stride, e->cfg.num_envs, out->obs, out_step, pout,
-                                        pout_step);
-    if (rc != CE_OK) return rc;
-    if (!e->was_reset) return fail(CE_ESTATE, "ce_rollout_policy before the first reset()");
-    CE_CLEAR_STALE_ERROR();
-    const float *obs = obs0;
-    for (int s = 0; s < k; ++s) {
-        const ce_policy_outputs po = ce::policy_advance(*pout, s * pout_step);
-        const ce_outputs eo = advance(*out, s * out_step);
-        ce::policy_launch(p, obs, noise ? noise + s * noise_stride : nullptr, e->cfg.num_envs, po,
-                          e->stream);
-        if ((rc = launch(e, false, po.env_action, eo, e->stream)) != CE_OK) return rc;
-        obs = eo.obs;
-    }
-    CE_HIP(hipGetLastError());
-    return CE_OK;
+    return ce::host_rollout_policy<OptOps>("ce_rollout_policy", e, p, k, obs0, noise, noise_stride,
+                                           out, out_step, pout, pout_step);
 }
 
-int ce_set_persistent(ce_engine *e, int32_t on) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    e->persist_on = on != 0;
-    return CE_OK;
-}
+int ce_set_persistent(ce_engine *e, int32_t on) { return ce::host_set_persistent(e, on); }
 
 const char *ce_step_many_kernel(const ce_engine *e) {
     if (!e) return "";
-    if (e->persist && e->persist_on) return e->many_name.c_str();
+    if (e->host.persistent()) return e->many_name.c_str();
     return ce_step_kernel(e);
 }
 
@@ -1078,17 +823,13 @@ const char *ce_step_kernel(const ce_engine *e) {
     return e->kernel_name.c_str();
 }
 
-int ce_host_outputs(ce_engine *e, ce_outputs *view) {
-    if (!e || !view) return fail(CE_EINVAL, "null argument");
-    *view = region_view(e, e->h_out);
-    return CE_OK;
-}
+int ce_host_outputs(ce_engine *e, ce_outputs *view) { return ce::host_outputs(e, view); }
 
 #ifdef CE_DIAG
 // Diagnostic builds only (not part of include/custom_envs_amd.h).
 int ce_diag_stamps(ce_engine *e, unsigned long long *out) {
     if (!e || !out) return fail(CE_EINVAL, "null argument");
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     CE_HIP(hipMemcpy(out, e->diag, sizeof(unsigned long long) * e->cfg.num_envs * ce::kStamps,
                      hipMemcpyDeviceToHost));
     return CE_OK;
@@ -1099,7 +840,7 @@ int ce_get_state(ce_engine *e, const ce_state *st) {
     if (!e || !st) return fail(CE_EINVAL, "null argument");
     const size_t E = e->cfg.num_envs, P = e->P, N = e->cfg.n_rows;
     int rc;
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     if (e->net) {
         if (st->weights && (rc = net_download(e, st->weights, e->W)) != CE_OK) return rc;
         if (st->init_weights && (rc = net_download(e, st->init_weights, e->W0)) != CE_OK) return rc;
@@ -1126,7 +867,7 @@ int ce_set_state(ce_engine *e, const ce_state *st) {
     if (!e || !st) return fail(CE_EINVAL, "null argument");
     const size_t E = e->cfg.num_envs, P = e->P, N = e->cfg.n_rows;
     int rc;
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     if (e->net) {
         if (st->weights && (rc = net_upload(e, e->W, st->weights)) != CE_OK) return rc;
         if (st->init_weights && (rc = net_upload(e, e->W0, st->init_weights)) != CE_OK) return rc;
@@ -1143,8 +884,8 @@ int ce_set_state(ce_engine *e, const ce_state *st) {
         CE_HIP(hipMemcpy(e->order, st->order, E * N * sizeof(int32_t), hipMemcpyHostToDevice));
         CE_HIP(hipMemset(e->order_sel, 0, E * sizeof(int32_t)));
     }
-    CE_HIP(hipStreamSynchronize(e->stream));
-    e->was_reset = true;
+    CE_HIP(hipStreamSynchronize(e->host.stream));
+    e->host.was_reset = true;
     return CE_OK;
 }
 

@@ -2,7 +2,7 @@
 // in include/custom_envs_amd.h).  Same conventions as multi_engine.hip: the
 // engine owns the struct-of-arrays state; host mode stages actions/outputs
 // through pinned buffers and synchronises; CE_PTR_DEVICE calls are
-// stream-ordered.
+// stream-ordered (engine_host.h holds those bodies).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +14,7 @@
 #include <thread>
 #include <vector>
 
-#include "common.h"
+#include "engine_host.h"
 #include "multinn_kernels.h"
 #include "seeding.h"
 
@@ -23,7 +23,7 @@ struct ce_nn_engine {
     ce::NnArgs base{};                 // shapes, offsets and state pointers
     int P = 0;
     size_t Ps = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    ce::Host<ce_multi_outputs> host;   // stream, staging buffers, ce_nn_step_many's graphs
     float *X = nullptr;
     int32_t *label = nullptr;
     float *theta_buf[2] = {nullptr, nullptr}, *g_buf[2] = {nullptr, nullptr};
@@ -35,13 +35,8 @@ struct ce_nn_engine {
     int32_t *step = nullptr, *cursor = nullptr, *order = nullptr, *order_sel = nullptr;
     int32_t *reset_perm = nullptr, *epoch_perm = nullptr, *agent_row = nullptr;
     int32_t *row_agent = nullptr;
-    float *d_act = nullptr, *h_act = nullptr;
-    size_t off[5] = {0};
-    size_t out_bytes = 0;
-    char *d_out = nullptr, *h_out = nullptr;
     unsigned long long *diag = nullptr;    // CE_DIAG builds: [2][E][kNnStamps]
-    bool seeded = false, was_reset = false;
-    ce::GraphCache graphs;   // ce_nn_step_many
+    bool seeded = false;
 };
 
 namespace {
@@ -49,16 +44,6 @@ namespace {
 using ce::fail;
 
 int host_ld(int w) { return ((w + 31) & ~31) + ce::kNnPad; }
-
-ce_multi_outputs region(const ce_nn_engine *e, char *base) {
-    ce_multi_outputs o;
-    o.obs = reinterpret_cast<float *>(base + e->off[0]);
-    o.reward = reinterpret_cast<float *>(base + e->off[1]);
-    o.info = reinterpret_cast<float *>(base + e->off[2]);
-    o.episode_len = reinterpret_cast<int32_t *>(base + e->off[3]);
-    o.done = reinterpret_cast<uint8_t *>(base + e->off[4]);
-    return o;
-}
 
 ce::NnArgs make_args(const ce_nn_engine *e, const float *act, const ce_multi_outputs &o) {
     ce::NnArgs a = e->base;
@@ -75,10 +60,6 @@ ce::NnArgs make_args(const ce_nn_engine *e, const float *act, const ce_multi_out
     return a;
 }
 
-bool complete(const ce_multi_outputs *o) {
-    return o && o->obs && o->reward && o->done && o->info && o->episode_len;
-}
-
 // one step's five launches; the ping-pong pairs swap afterwards
 void launch_step(ce_nn_engine *e, const float *act, const ce_multi_outputs &o, hipStream_t s) {
     const ce::NnArgs a = make_args(e, act, o);
@@ -91,43 +72,19 @@ void launch_step(ce_nn_engine *e, const float *act, const ce_multi_outputs &o, h
     e->parity ^= 1;
 }
 
-void copy_out(const ce_nn_engine *e, const ce_multi_outputs &src, const ce_multi_outputs *dst) {
-    if (!dst) return;
-    const size_t E = e->cfg.num_envs, P = e->P, H = e->cfg.max_history;
-    if (dst->obs) std::memcpy(dst->obs, src.obs, E * P * 3 * H * sizeof(float));
-    if (dst->reward) std::memcpy(dst->reward, src.reward, E * P * sizeof(float));
-    if (dst->done) std::memcpy(dst->done, src.done, E * P);
-    if (dst->info) std::memcpy(dst->info, src.info, E * CE_MULTI_INFO * sizeof(float));
-    if (dst->episode_len) std::memcpy(dst->episode_len, src.episode_len, E * sizeof(int32_t));
-}
-
-int do_step(ce_nn_engine *e, const float *actions, const ce_multi_outputs *out, uint32_t flags,
-            bool sync) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_CLEAR_STALE_ERROR();
-    if (!e->was_reset) return fail(CE_ESTATE, "step() before the first reset()");
-    if (!actions) return fail(CE_EINVAL, "null actions");
-    const size_t rows = static_cast<size_t>(e->cfg.num_envs) * e->P;
-    if (flags & CE_PTR_DEVICE) {
-        if (out && !complete(out)) return fail(CE_EINVAL, "device outputs must all be set");
-        const ce_multi_outputs o = out ? *out : region(e, e->d_out);
-        launch_step(e, actions, o, e->stream);
-        CE_HIP(hipGetLastError());
-        if (sync) CE_HIP(hipStreamSynchronize(e->stream));
+// what this engine launches (engine_host.h)
+struct NnOps {
+    static int step(ce_nn_engine *e, const float *act, const ce_multi_outputs &o, bool) {
+        launch_step(e, act, o, e->host.stream);
         return CE_OK;
     }
-    std::memcpy(e->h_act, actions, rows * sizeof(float));
-    CE_HIP(hipMemcpyAsync(e->d_act, e->h_act, rows * sizeof(float), hipMemcpyHostToDevice,
-                          e->stream));
-    launch_step(e, e->d_act, region(e, e->d_out), e->stream);
-    CE_HIP(hipGetLastError());
-    CE_HIP(hipMemcpyAsync(e->h_out, e->d_out, e->out_bytes, hipMemcpyDeviceToHost, e->stream));
-    if (sync) {
-        CE_HIP(hipStreamSynchronize(e->stream));
-        copy_out(e, region(e, e->h_out), out);
+    static int reset(ce_nn_engine *e, const ce_multi_outputs &o, bool) {
+        if (!e->seeded) return fail(CE_ESTATE, "reset() before seed()");
+        const ce::NnArgs a = make_args(e, nullptr, o);
+        hipLaunchKernelGGL(ce::nn_reset_kernel, dim3(a.E), dim3(ce::kNnBlock), 0, e->host.stream, a);
+        return CE_OK;
     }
-    return CE_OK;
-}
+};
 
 }  // namespace
 
@@ -165,13 +122,6 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
         ce_nn_destroy(e);
         return code;
     };
-#define CE_TRY(call)                                                                   \
-    do {                                                                               \
-        hipError_t err_ = (call);                                                      \
-        if (err_ != hipSuccess)                                                        \
-            return bail(fail(CE_EHIP, std::string(#call " failed: ") + hipGetErrorString(err_))); \
-    } while (0)
-
     ce::NnArgs &a = e->base;
     a.E = cfg->num_envs;
     a.N = cfg->n_rows;
@@ -220,14 +170,16 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
         return bail(fail(CE_EUNSUPPORTED, "ce_nn_create: network too wide for LDS (" +
                                               std::to_string(a.lds_bytes) + " bytes)"));
 
-    CE_TRY(hipSetDevice(cfg->device));
+    const size_t E = a.E, N = a.N, Ps = e->Ps, H = a.H;
+    const int rc = e->host.create(cfg->device, E * P * sizeof(float),
+                                  {E * P * 3 * H * sizeof(float), E * P * sizeof(float),
+                                   E * CE_MULTI_INFO * sizeof(float), E * sizeof(int32_t),
+                                   E * static_cast<size_t>(P)});
+    if (rc != CE_OK) return bail(rc);
     CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::nn_grad_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes));
     CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::nn_step_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes));
-    CE_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    e->stream = e->own_stream;
-    const size_t E = a.E, N = a.N, Ps = e->Ps, H = a.H;
     CE_TRY(hipMalloc(&e->X, N * a.F * sizeof(float)));
     CE_TRY(hipMalloc(&e->label, N * sizeof(int32_t)));
     CE_TRY(hipMemcpy(e->X, features, N * a.F * sizeof(float), hipMemcpyHostToDevice));
@@ -258,8 +210,6 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
     CE_TRY(hipMalloc(&e->epoch_perm, E * N * sizeof(int32_t)));
     CE_TRY(hipMalloc(&e->agent_row, P * sizeof(int32_t)));
     CE_TRY(hipMalloc(&e->row_agent, P * sizeof(int32_t)));
-    CE_TRY(hipMalloc(&e->d_act, E * P * sizeof(float)));
-    CE_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_act), E * P * sizeof(float)));
     CE_TRY(hipMemset(e->step, 0, E * sizeof(int32_t)));
     CE_TRY(hipMemset(e->cursor, 0, E * sizeof(int32_t)));
     CE_TRY(hipMemset(e->order_sel, 0, E * sizeof(int32_t)));
@@ -283,24 +233,10 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
         CE_TRY(hipMemcpy(e->agent_row, row.data(), P * sizeof(int32_t), hipMemcpyHostToDevice));
         CE_TRY(hipMemcpy(e->row_agent, order.data(), P * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    const size_t sizes[5] = {E * P * 3 * H * sizeof(float), E * P * sizeof(float),
-                             E * CE_MULTI_INFO * sizeof(float), E * sizeof(int32_t),
-                             E * static_cast<size_t>(P)};
-    size_t off = 0;
-    for (int i = 0; i < 5; ++i) {
-        e->off[i] = off;
-        off = ce::align16(off + sizes[i]);
-    }
-    e->out_bytes = off;
-    CE_TRY(hipMalloc(&e->d_out, e->out_bytes));
 #ifdef CE_DIAG
     CE_TRY(hipMalloc(&e->diag, 2 * E * ce::kNnStamps * sizeof(unsigned long long)));
     a.diag = e->diag;
 #endif
-    CE_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_out), e->out_bytes));
-    CE_TRY(hipMemset(e->d_out, 0, e->out_bytes));
-    std::memset(e->h_out, 0, e->out_bytes);
-#undef CE_TRY
     a.X = e->X;
     a.label = e->label;
     a.theta0 = e->theta0;
@@ -329,26 +265,15 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
 
 void ce_nn_destroy(ce_nn_engine *e) {
     if (!e) return;
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    e->graphs.release();
-    void *dev[] = {e->X, e->label, e->theta_buf[0], e->theta_buf[1], e->g_buf[0], e->g_buf[1],
-                   e->theta0, e->gU, e->loss_b, e->part_u, e->part_c, e->rw, e->rg,
-                   e->al, e->sw, e->sg, e->hl, e->hsg, e->step, e->cursor,
-                   e->order, e->order_sel, e->reset_perm, e->epoch_perm, e->agent_row, e->row_agent,
-                   e->d_act, e->d_out, e->diag};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (e->h_out) (void)hipHostFree(e->h_out);
-    if (e->h_act) (void)hipHostFree(e->h_act);
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+    e->host.destroy({e->X, e->label, e->theta_buf[0], e->theta_buf[1], e->g_buf[0], e->g_buf[1],
+                     e->theta0, e->gU, e->loss_b, e->part_u, e->part_c, e->rw, e->rg,
+                     e->al, e->sw, e->sg, e->hl, e->hsg, e->step, e->cursor,
+                     e->order, e->order_sel, e->reset_perm, e->epoch_perm, e->agent_row, e->row_agent,
+                     e->diag});
     delete e;
 }
 
-int ce_nn_set_stream(ce_nn_engine *e, void *stream) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    e->stream = stream ? static_cast<hipStream_t>(stream) : e->own_stream;
-    return CE_OK;
-}
+int ce_nn_set_stream(ce_nn_engine *e, void *stream) { return ce::host_set_stream(e, stream); }
 
 int ce_nn_n_params(const ce_nn_engine *e) { return e ? e->P : fail(CE_EINVAL, "null engine"); }
 
@@ -380,70 +305,44 @@ int ce_nn_seed(ce_nn_engine *e, const uint64_t *seeds, int32_t n) {
     for (auto &t : pool) t.join();
     // stream-ordered after any step still reading theta0 / the permutations
     // (the engine stream is non-blocking, so null-stream copies would race)
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     CE_HIP(hipMemcpyAsync(e->theta0, th.data(), E * Ps * sizeof(float), hipMemcpyHostToDevice,
-                          e->stream));
+                          e->host.stream));
     CE_HIP(hipMemcpyAsync(e->reset_perm, rp.data(), E * N * sizeof(int32_t),
-                          hipMemcpyHostToDevice, e->stream));
+                          hipMemcpyHostToDevice, e->host.stream));
     CE_HIP(hipMemcpyAsync(e->epoch_perm, ep.data(), E * N * sizeof(int32_t),
-                          hipMemcpyHostToDevice, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
+                          hipMemcpyHostToDevice, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     e->seeded = true;
     return CE_OK;
 }
 
 int ce_nn_reset(ce_nn_engine *e, const ce_multi_outputs *out, uint32_t flags) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_CLEAR_STALE_ERROR();
-    if (!e->seeded) return fail(CE_ESTATE, "reset() before seed()");
-    const size_t n = static_cast<size_t>(e->cfg.num_envs) * e->P * 3 * e->cfg.max_history;
-    if (flags & CE_PTR_DEVICE) {
-        if (out && !complete(out)) return fail(CE_EINVAL, "device outputs must all be set");
-        const ce_multi_outputs o = out ? *out : region(e, e->d_out);
-        const ce::NnArgs a = make_args(e, nullptr, o);
-        hipLaunchKernelGGL(ce::nn_reset_kernel, dim3(a.E), dim3(ce::kNnBlock), 0, e->stream, a);
-        CE_HIP(hipGetLastError());
-        e->was_reset = true;
-        return CE_OK;
-    }
-    const ce::NnArgs a = make_args(e, nullptr, region(e, e->d_out));
-    hipLaunchKernelGGL(ce::nn_reset_kernel, dim3(a.E), dim3(ce::kNnBlock), 0, e->stream, a);
-    CE_HIP(hipGetLastError());
-    CE_HIP(hipMemcpyAsync(e->h_out, e->d_out, e->out_bytes, hipMemcpyDeviceToHost, e->stream));
-    CE_HIP(hipStreamSynchronize(e->stream));
-    e->was_reset = true;
-    if (out && out->obs) std::memcpy(out->obs, region(e, e->h_out).obs, n * sizeof(float));
-    return CE_OK;
+    return ce::host_reset<NnOps>(e, out, flags);
 }
 
 int ce_nn_step(ce_nn_engine *e, const float *actions, const ce_multi_outputs *out, uint32_t flags) {
-    return do_step(e, actions, out, flags, true);
+    return ce::host_step<NnOps>(e, actions, out, flags, true);
 }
 
 int ce_nn_step_async(ce_nn_engine *e, const float *actions, const ce_multi_outputs *out,
                      uint32_t flags) {
-    return do_step(e, actions, out, flags, false);
+    return ce::host_step<NnOps>(e, actions, out, flags, false);
 }
 
-int ce_nn_wait(ce_nn_engine *e) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    CE_HIP(hipStreamSynchronize(e->stream));
-    return CE_OK;
-}
+int ce_nn_wait(ce_nn_engine *e) { return ce::host_wait(e); }
 
 namespace {
 
 int nn_graph(ce_nn_engine *e, int32_t k, const float *actions, int64_t stride,
              const ce_multi_outputs *out, hipGraphExec_t *exec) {
-    if (!e) return fail(CE_EINVAL, "null engine");
-    if (!e->was_reset) return fail(CE_ESTATE, "step_many() before the first reset()");
-    if (k <= 0 || !actions || stride < 0) return fail(CE_EINVAL, "bad arguments");
-    if (out && !complete(out)) return fail(CE_EINVAL, "device outputs must all be set");
-    const ce_multi_outputs o = out ? *out : region(e, e->d_out);
+    int rc = ce::many_args_ok(e, k, actions, stride, out);
+    if (rc != CE_OK) return rc;
+    const ce_multi_outputs o = out ? *out : e->host.region(e->host.d_out);
     // the captured launches bake in the ping-pong pointers of their parity
     const int p0 = e->parity;
-    const int rc = e->graphs.get(ce::graph_key(k, p0, actions, stride, e->stream, o), [&] {
-        for (int s = 0; s < k; ++s) launch_step(e, actions + s * stride, o, e->stream);
+    rc = e->host.graphs.get(ce::graph_key(k, p0, actions, stride, e->host.stream, o), [&] {
+        (void)ce::launch_steps<NnOps>(e, k, actions, stride, o, 0);
     }, exec);
     e->parity = p0;
     return rc;
@@ -456,7 +355,7 @@ int ce_nn_step_many(ce_nn_engine *e, int32_t k, const float *actions, int64_t st
     hipGraphExec_t exec;
     const int rc = nn_graph(e, k, actions, stride, out, &exec);
     if (rc != CE_OK) return rc;
-    CE_HIP(hipGraphLaunch(exec, e->stream));
+    CE_HIP(hipGraphLaunch(exec, e->host.stream));
     e->parity ^= (k & 1);
     return CE_OK;
 }
@@ -467,18 +366,14 @@ int ce_nn_step_many_prepare(ce_nn_engine *e, int32_t k, const float *actions, in
     return nn_graph(e, k, actions, stride, out, &exec);
 }
 
-int ce_nn_host_outputs(ce_nn_engine *e, ce_multi_outputs *view) {
-    if (!e || !view) return fail(CE_EINVAL, "null argument");
-    *view = region(e, e->h_out);
-    return CE_OK;
-}
+int ce_nn_host_outputs(ce_nn_engine *e, ce_multi_outputs *view) { return ce::host_outputs(e, view); }
 
 #ifdef CE_DIAG
 // Diagnostic builds only (not part of include/custom_envs_amd.h): the eval
 // kernels' phase stamps, [2 kernels][E][kNnStamps].
 int ce_nn_diag_stamps(ce_nn_engine *e, unsigned long long *out) {
     if (!e || !out) return fail(CE_EINVAL, "null argument");
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     CE_HIP(hipMemcpy(out, e->diag,
                      2 * sizeof(unsigned long long) * e->cfg.num_envs * ce::kNnStamps,
                      hipMemcpyDeviceToHost));
@@ -490,7 +385,7 @@ int ce_nn_get_state(ce_nn_engine *e, float *theta, float *gprev, int32_t *step, 
                     int32_t *order) {
     if (!e) return fail(CE_EINVAL, "null engine");
     const size_t E = e->cfg.num_envs, P = e->P, Ps = e->Ps, N = e->cfg.n_rows;
-    CE_HIP(hipStreamSynchronize(e->stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     if (theta)
         CE_HIP(hipMemcpy2D(theta, P * sizeof(float), e->theta_buf[e->parity], Ps * sizeof(float),
                            P * sizeof(float),

@@ -354,27 +354,13 @@ class OptimizeEngine:
         Returns (fields, record_bytes): fields maps each output name to a
         (k, E, ...) view of the buffer."""
         import torch
-        dev = torch_device or torch.device('cuda', self.device)
-        offs, off = {}, 0
-        spec = self.output_fields()
-        for name, dtype, rows, tail in spec:
-            n = self.num_envs * rows * int(np.prod(tail, dtype=np.int64)) * \
-                torch.empty((), dtype=dtype).element_size()
-            offs[name] = off
-            off += -(-n // 256) * 256
-        rec = off
-        buf = torch.zeros(int(k) * rec, dtype=torch.uint8, device=dev)
-        fields = {}
-        for name, dtype, rows, tail in spec:
-            size = torch.empty((), dtype=dtype).element_size()
-            inner = (self.num_envs * rows,) + tuple(tail)
-            strides = [1] * len(inner)
-            for i in range(len(inner) - 2, -1, -1):
-                strides[i] = strides[i + 1] * inner[i + 1]
-            fields[name] = buf.view(dtype).as_strided((int(k),) + inner, (rec // size,) + tuple(strides),
-                                                      offs[name] // size)
+        from custom_envs_amd.distributed import PackedLayout
+        lay = PackedLayout(self.output_fields(), self.num_envs)
+        buf = torch.zeros(int(k) * lay.nbytes, dtype=torch.uint8,
+                          device=torch_device or torch.device('cuda', self.device))
+        fields = lay.chunk_views(buf, self.num_envs, int(k))
         fields['_buffer'] = buf
-        return fields, rec
+        return fields, lay.nbytes
 
     def rollout_device(self, k, actions, fields, record_bytes, per_step_actions=True):
         """k stream-ordered steps keeping every step's outputs: step t reads

@@ -82,7 +82,7 @@ class MultiOptEngine:
 
     # ------------------------------------------------- K steps in one launch
     def set_persistent(self, on=True):
-        """K-step calls as ONE launch of multi_persist_kernel (max_history 5)
+        """K-step calls as ONE launch of multi_persist5_kernel (max_history 5)
         or one launch per step (on=False, the A/B form)."""
         self._call('set_persistent', 1 if on else 0)
         self.many_kernel = self._lib.ce_multi_step_many_kernel(self._h).decode()

@@ -318,7 +318,7 @@ int ce_multi_step_many_prepare(ce_multi_engine *eng, int32_t k, const float *act
                                int64_t action_step_stride, const ce_multi_outputs *out);
 /* As ce_step_many_strided: step t writes every output advanced by
  * t * out_step_bytes.  With max_history == 5 (the reference default,
- * multioptlrs.py:39) the K steps are ONE launch of multi_persist_kernel (the
+ * multioptlrs.py:39) the K steps are ONE launch of multi_persist5_kernel (the
  * state in registers across them); otherwise K step launches. */
 int ce_multi_step_many_strided(ce_multi_engine *eng, int32_t k, const float *actions,
                                int64_t action_step_stride, const ce_multi_outputs *out,

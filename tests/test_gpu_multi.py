@@ -395,7 +395,7 @@ def _multi_rollout(eng, acts, chunks):
     ({'ndims': 16, 'initial_points': [(-1.0) ** i * (0.3 + 0.05 * i) for i in range(16)]}, 20, 8, 21, [7, 3, 11]),
 ])
 def test_persistent_multi_bit_equal_to_step_launches(problem, E, MB, T, chunks):
-    """multi_persist_kernel (K steps per launch, the state in registers) gives
+    """multi_persist5_kernel (K steps per launch, the state in registers) gives
     the one-step kernel's bits for every output of every step and the final
     theta / step: early stops (loss > 1e4), max_batches ends, a partial last
     wave, and agent groups with idle lanes (P = 6 in groups of 8)."""
@@ -566,3 +566,63 @@ def test_multi_rollout_argument_checks():
         assert fields['episode_len'][:, 0].cpu().tolist() == [1, 2, 3, 4]
     finally:
         eng.close()
+
+
+@pytest.mark.parametrize('H,persist_off', [(3, False), (5, True)])
+def test_step_many_graph_bit_equal_to_step_launches(H, persist_off):
+    """ce_multi_step_many as a cached graph of K captured launches -- the only
+    K-step form with max_history != 5 (the any-H kernel), and the form behind
+    set_persistent(False) at max_history 5 -- and the per-step strided form
+    at the same history give the bits of K step_device launches: 17 envs (a
+    full 16-env wave and a one-env partial one), K = 3, an episode end inside
+    (max_batches 2)."""
+    import torch
+    from custom_envs_amd.multi_engine import MultiOptEngine
+    E, K, MB = 17, 3, 2
+    acts = torch.from_numpy(np.random.RandomState(H).uniform(1.0, 2.6, (K, E * 4)).astype(np.float32)).cuda()
+    torch.cuda.synchronize()              # the engines run on their own streams
+
+    def engine():
+        eng = MultiOptEngine(E, 'func4', max_batches=MB, max_history=H)
+        if persist_off:
+            eng.set_persistent(False)
+        assert not eng.persistent
+        assert eng.many_kernel == 'multi_step_kernel<4,%d>' % (5 if H == 5 else 0)
+        return eng
+
+    ref, steps = engine(), []
+    out = ref.alloc_device_outputs()
+    ref.reset_device(out)
+    for t in range(K):
+        ref.step_device(acts[t], out)
+        ref.wait()
+        steps.append({n: v.cpu().numpy() for n, v in out.items()})
+    ref_state = ref.get_state()
+    ref.close()
+    assert any(s['done'].any() for s in steps), 'no episode ended'
+
+    many = engine()
+    mout = many.alloc_device_outputs()
+    many.reset_device(mout)
+    many.prepare_many_device(K, acts, mout)
+    many.step_many_device(K, acts, mout)
+    many.wait()
+    for n, v in mout.items():
+        assert np.array_equal(v.cpu().numpy(), steps[-1][n], equal_nan=True), n
+    state = many.get_state()
+    many.close()
+    for n in ('theta', 'step'):
+        assert np.array_equal(state[n], ref_state[n]), n
+
+    roll = engine()
+    fields, rb = roll.alloc_rollout(K)
+    roll.reset_device(roll.alloc_device_outputs())
+    roll.rollout_device(K, acts, fields, rb)
+    roll.wait()
+    for t in range(K):
+        for n in steps[t]:
+            assert np.array_equal(fields[n][t].cpu().numpy(), steps[t][n], equal_nan=True), (t, n)
+    state = roll.get_state()
+    roll.close()
+    for n in ('theta', 'step'):
+        assert np.array_equal(state[n], ref_state[n]), n

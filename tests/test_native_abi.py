@@ -81,6 +81,51 @@ def test_bad_arguments_are_reported():
     assert b'ABI' in lib.ce_last_error()
 
 
+# Every entry point of the three engines whose first argument is the handle.
+_HANDLE_TAKING = sorted(
+    name for name in _native.EXPORTS
+    if (name.startswith(('ce_multi_', 'ce_nn_')) and not name.endswith(('_create', '_seed_draws')))
+    or name in ('ce_destroy', 'ce_set_stream', 'ce_set_compact_outputs', 'ce_num_envs',
+                'ce_obs_dim', 'ce_act_dim', 'ce_seed', 'ce_reset', 'ce_step', 'ce_step_async',
+                'ce_wait', 'ce_step_many', 'ce_step_many_prepare', 'ce_step_many_strided',
+                'ce_set_persistent', 'ce_step_many_kernel', 'ce_host_outputs', 'ce_step_kernel',
+                'ce_get_state', 'ce_set_state', 'ce_rollout_policy'))
+
+
+@pytest.mark.parametrize('name', _HANDLE_TAKING)
+def test_null_handle_is_einval(name):
+    """A NULL engine handle, every other argument valid: CE_EINVAL with
+    ce_last_error set, before anything is dereferenced.  The kernel-name
+    getters return "", destroy is a no-op, and the three size getters return
+    a plain CE_EINVAL."""
+    lib = _native.load()
+    fn = getattr(lib, name)
+    assert fn.argtypes[0] is ctypes.c_void_p
+    buf = np.zeros(64, np.float64)
+    keep, args = [], [None]
+    for t in fn.argtypes[1:]:
+        if t is ctypes.c_void_p:
+            args.append(buf.ctypes.data)
+        elif hasattr(t, 'contents'):                    # POINTER(struct): a zeroed struct
+            keep.append(t._type_())
+            args.append(ctypes.byref(keep[-1]))
+        else:
+            args.append(1)
+    assert lib.ce_seed_draws(0, 0, 2, 4, None, None) == _native.CE_EINVAL
+    marker = lib.ce_last_error()
+    rc = fn(*args)
+    if name.endswith('_destroy'):
+        assert rc is None
+    elif name.endswith('_kernel'):
+        assert rc == b''
+    elif name in ('ce_num_envs', 'ce_obs_dim', 'ce_act_dim'):
+        assert rc == _native.CE_EINVAL
+    else:
+        assert rc == _native.CE_EINVAL
+        msg = lib.ce_last_error()
+        assert msg != marker and b'null' in msg, msg
+
+
 def test_unsupported_shape_is_loud():
     """Beyond the f64 MFMA kernel's F <= 64, K <= 16 (any other shape runs)."""
     lib = _native.load()
