@@ -45,6 +45,8 @@ EXPORTS = (
     'ce_nn_step_many', 'ce_nn_step_many_prepare', 'ce_nn_host_outputs', 'ce_nn_get_state',
     'ce_policy_n_params', 'ce_policy_create', 'ce_policy_destroy', 'ce_policy_set_params',
     'ce_policy_set_bounds', 'ce_policy_forward', 'ce_rollout_policy', 'ce_multi_rollout_policy',
+    'ce_ppo2_create', 'ce_ppo2_destroy', 'ce_ppo2_set_params', 'ce_ppo2_get_params',
+    'ce_ppo2_gae', 'ce_ppo2_grad', 'ce_ppo2_step',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -103,6 +105,13 @@ class CePolicyOutputs(ctypes.Structure):
                 ('neglogp', ctypes.c_void_p), ('value', ctypes.c_void_p)]
 
 
+class CePpo2Config(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_float) for name in (
+        'gamma', 'lam', 'cliprange', 'cliprange_vf', 'ent_coef', 'vf_coef', 'max_grad_norm',
+        'lr', 'beta1', 'beta2', 'eps')] + [('normalize_adv', ctypes.c_int32),
+                                            ('grid_limit', ctypes.c_int32)]
+
+
 class CeState(ctypes.Structure):
     _fields_ = [('weights', ctypes.c_void_p), ('grad_hist', ctypes.c_void_p),
                 ('loss_hist', ctypes.c_void_p), ('step', ctypes.c_void_p),
@@ -114,6 +123,7 @@ _lib = None
 
 def _declare(lib):
     vp, i32, u32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64
+    f32 = ctypes.c_float
     sig = {
         'ce_abi_version': ([], ctypes.c_int),
         'ce_last_error': ([], ctypes.c_char_p),
@@ -183,6 +193,13 @@ def _declare(lib):
                                ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
         'ce_multi_rollout_policy': ([vp, vp, i32, vp, vp, i64, ctypes.POINTER(CeMultiOutputs), i64,
                                      ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
+        'ce_ppo2_create': ([vp, ctypes.POINTER(CePpo2Config), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_ppo2_destroy': ([vp], None),
+        'ce_ppo2_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_ppo2_get_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_ppo2_gae': ([vp, i32, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp], ctypes.c_int),
+        'ce_ppo2_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp], ctypes.c_int),
+        'ce_ppo2_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

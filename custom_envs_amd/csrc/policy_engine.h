@@ -26,6 +26,26 @@ int policy_rollout_args_ok(const char *who, const ce_policy *p, int engine_obs_d
                            int64_t out_step_bytes, const ce_policy_outputs *pout,
                            int64_t pout_step_bytes);
 
+// What the PPO2 learner (ppo2_engine.hip, ppo2_kernels.h) needs of a policy,
+// as plain data: its shape, the offsets of its padded parameter image (every
+// W zero-padded to [in_pad][out_pad], policy_engine.hip: plan), the segments
+// that map the flat parameter vector into the image, and the image itself.
+constexpr int kPlanLayers = 4;                  // hidden layers + the head
+constexpr int kPlanSegs = 4 * kPlanLayers + 1;  // (W, b) per layer per network + logstd
+struct PolicyPlan {
+    int D, A, n_hidden;
+    int in_pad[kPlanLayers], out_pad[2][kPlanLayers];
+    int off_w[2][kPlanLayers], off_b[2][kPlanLayers], off_logstd;
+    int n_segs;                                 // logstd is the last segment
+    int seg_dst[kPlanSegs], seg_src[kPlanSegs], seg_cols[kPlanSegs], seg_cols_pad[kPlanSegs];
+    int n_params, img_floats, device;
+    float *img;
+};
+PolicyPlan policy_plan(const ce_policy *p);
+
+// Enqueue the repack of the device vector `flat` [n_params] into the image.
+void policy_repack(const ce_policy *p, const float *flat, hipStream_t stream);
+
 // the policy outputs of step t of a rollout
 ce_policy_outputs policy_advance(const ce_policy_outputs &o, int64_t bytes);
 

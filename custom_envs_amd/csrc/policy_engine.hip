@@ -132,6 +132,41 @@ void policy_dims(const ce_policy *p, int *obs_dim, int *act_dim) {
     *act_dim = p->cfg.act_dim;
 }
 
+PolicyPlan policy_plan(const ce_policy *p) {
+    static_assert(kPlanLayers == kPolLayers && kPlanSegs == kPolSegs, "plan sizes");
+    const PolicyArgs &a = p->args;
+    PolicyPlan q{};
+    q.D = a.D;
+    q.A = a.A;
+    q.n_hidden = a.n_hidden;
+    for (int l = 0; l < kPolLayers; ++l) {
+        q.in_pad[l] = a.in_pad[l];
+        for (int net = 0; net < 2; ++net) {
+            q.out_pad[net][l] = a.out_pad[net][l];
+            q.off_w[net][l] = a.off_w[net][l];
+            q.off_b[net][l] = a.off_b[net][l];
+        }
+    }
+    q.off_logstd = a.off_logstd;
+    q.n_segs = p->pack.n;
+    for (int s = 0; s < p->pack.n; ++s) {
+        q.seg_dst[s] = p->pack.dst[s];
+        q.seg_src[s] = p->pack.src[s];
+        q.seg_cols[s] = p->pack.cols[s];
+        q.seg_cols_pad[s] = p->pack.cols_pad[s];
+    }
+    q.n_params = p->n_params;
+    q.img_floats = p->img_floats;
+    q.device = p->cfg.device;
+    q.img = p->img;
+    return q;
+}
+
+void policy_repack(const ce_policy *p, const float *flat, hipStream_t stream) {
+    hipLaunchKernelGGL(policy_pack_kernel, dim3(p->pack.n), dim3(256), 0, stream, p->pack, flat,
+                       p->img);
+}
+
 void policy_launch(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
                    const ce_policy_outputs &out, hipStream_t stream) {
     PolicyArgs a = p->args;

@@ -466,6 +466,69 @@ int ce_multi_rollout_policy(ce_multi_engine *eng, const ce_policy *p, int32_t k,
                             const ce_multi_outputs *out, int64_t out_step_bytes,
                             const ce_policy_outputs *pout, int64_t pout_step_bytes);
 
+/* ------------------------------------------------------------------------
+ * The PPO2 learner on the device (stable-baselines 2.x PPO2 over the policy
+ * above; custom_envs_amd/ppo2.py states the semantics in NumPy): GAE, the
+ * loss gradient, a global-norm clip, TF-style Adam and the repack of the
+ * policy's image (ppo2_kernels.h).  The learner owns the master flat
+ * parameters, Adam's m and v, the step count and the partial slab on the
+ * policy's device.  ce_ppo2_gae / _grad / _step are stream-ordered on the
+ * caller's stream and never synchronise; results are bit-identical run after
+ * run for the same inputs and grid_limit (no floating-point atomics).
+ * Every argument check precedes the first HIP call, and the checks of the
+ * plain arguments precede the check of the handle.
+ */
+typedef struct ce_ppo2 ce_ppo2;
+
+typedef struct ce_ppo2_config {
+    float gamma;           /* in [0, 1]                                      */
+    float lam;             /* in [0, 1]                                      */
+    float cliprange;       /* > 0                                            */
+    float cliprange_vf;    /* value clip range; negative: no value clipping  */
+    float ent_coef;
+    float vf_coef;
+    float max_grad_norm;   /* global-norm clip; <= 0: none                   */
+    float lr;              /* > 0                                            */
+    float beta1;           /* in [0, 1)                                      */
+    float beta2;           /* in [0, 1)                                      */
+    float eps;             /* > 0                                            */
+    int32_t normalize_adv; /* normalise advantages over the rows of a call   */
+    int32_t grid_limit;    /* workgroups per network; 0: one per CU          */
+} ce_ppo2_config;
+
+/* The policy must outlive the learner.  The master parameters start as zeros. */
+int ce_ppo2_create(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out);
+void ce_ppo2_destroy(ce_ppo2 *l);
+/* The master parameters (n = ce_policy_n_params; host pointer: synchronises;
+ * CE_PTR_DEVICE: stream-ordered).  Both also write through to the policy's
+ * image.  Adam's moments and the step count are kept. */
+int ce_ppo2_set_params(ce_ppo2 *l, const float *flat, int64_t n, uint32_t flags,
+                       void *hip_stream);
+int ce_ppo2_get_params(ce_ppo2 *l, float *flat, int64_t n, uint32_t flags, void *hip_stream);
+/* adv, ret [k][rows] contiguous float32 from rewards (float32), dones (uint8)
+ * and values (float32) read in place in rollout records: record t of each at
+ * base + t * stride bytes (reward / value strides multiples of 4), last_values
+ * [rows].  Device pointers. */
+int ce_ppo2_gae(const ce_ppo2 *l, int32_t k, int64_t rows, const float *rewards,
+                int64_t reward_stride_bytes, const uint8_t *dones, int64_t done_stride_bytes,
+                const float *values, int64_t value_stride_bytes, const float *last_values,
+                float *adv, float *ret, void *hip_stream);
+/* The loss gradient of n rows: rows idx[0..n) (int32, clamped to [0, m)) of
+ * the m-row arrays obs [m][D], actions [m][A], advantages, returns,
+ * old_neglogp, old_values [m], or rows 0..n-1 when idx is NULL (n <= m).
+ * cliprange < 0: the learner's.  Writes grad [n_params] and stats [8]: loss,
+ * pg_loss, vf_loss, entropy, approxkl, clipfrac, |grad|^2, 0.  No update. */
+int ce_ppo2_grad(ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
+                 const float *actions, const float *advantages, const float *returns,
+                 const float *old_neglogp, const float *old_values, float cliprange,
+                 float *grad, float *stats, void *hip_stream);
+/* ce_ppo2_grad, then the clip, Adam and the policy image's repack, one call.
+ * lr < 0 / cliprange < 0: the learner's. */
+int ce_ppo2_step(ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
+                 const float *actions, const float *advantages, const float *returns,
+                 const float *old_neglogp, const float *old_values, float lr, float cliprange,
+                 float *stats, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,319 @@
+"""The PPO2 learner on the device (ce_ppo2_*, csrc/ppo2_kernels.h) against the
+NumPy statements of custom_envs_amd/ppo2.py in float64.
+
+1. GAE parity on true strided rollout records (K = 10, episodes of 4 steps,
+   R = 1, 3, 65 envs of the two-class shape and the 8 agent rows of func4):
+   1e-5 norm-relative against ``gae_numpy`` in float64, and bit-equal to
+   ``gae_numpy`` in float32 (the kernel keeps its multiplies and adds unfused
+   and in the statement's order).
+2. Gradient parity, every case of ppo2_cases: each parameter block within
+   1e-5 of ``loss_grad_numpy`` in float64 (max|d| / max|ref over the whole
+   gradient|), each statistic within 1e-5 relative, clipfrac exact.
+3. ``idx``: a shuffled subset of a larger batch equals the contiguous call on
+   the gathered copy; a permutation of all rows differs by summation order.
+4. Determinism: the same call twice, bit-identical.
+5. Grid independence: grid_limit 1, 2, 0 agree to the bound.
+6. Three ``step`` calls against ``loss_grad_numpy`` + ``adam_step_numpy`` in
+   float64, the norm clip biting and idle; the policy image follows.
+7. collect -> gae -> update -> collect, and its bit-identical replay.
+"""
+import numpy as np
+import pytest
+
+import policy_cases as pc
+import ppo2_cases as cases
+from custom_envs_amd.policy import MlpPolicy, forward_numpy
+from custom_envs_amd.ppo2 import (STAT_NAMES, PPO2Learner, adam_step_numpy, gae_numpy,
+                                  loss_grad_numpy)
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 1e-5
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _need_gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a ROCm device')
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _dev(inputs, names=cases.BATCH_FIELDS):
+    import torch
+    return {n: torch.from_numpy(np.ascontiguousarray(inputs[n])).cuda() for n in names}
+
+
+def _learner(case, grid_limit=None, **over):
+    inputs = cases.draw_case(case)
+    _, D, hidden, A, limit = case
+    policy = MlpPolicy(D, A, hidden)
+    hyper = dict(cliprange=cases.HP.cliprange, cliprange_vf=cases.HP.cliprange_vf,
+                 ent_coef=cases.HP.ent_coef, vf_coef=cases.HP.vf_coef,
+                 normalize_adv=cases.HP.normalize_adv,
+                 grid_limit=limit if grid_limit is None else grid_limit)
+    hyper.update(over)
+    learner = PPO2Learner(policy, **hyper)
+    learner.set_params(inputs['params'])
+    return learner, inputs
+
+
+_REF = {}
+
+
+def _reference(case):
+    """(stats, grad) of the float64 statement, computed once per case."""
+    if case not in _REF:
+        inputs = cases.draw_case(case)
+        _REF[case] = loss_grad_numpy(inputs['params'], *[inputs[n] for n in cases.BATCH_FIELDS],
+                                     hp=cases.HP, hidden=inputs['hidden'])
+    return _REF[case]
+
+
+def _check(case, grad, stats, ref, what):
+    ref_stats, ref_grad = ref
+    errs = cases.block_errs(case, grad, ref_grad)
+    got = stats.stats()
+    # relative; a statistic that is exactly zero (pg_loss of a single
+    # normalised row) must come out exactly zero
+    serr = {n: abs(got[n] - float(ref_stats[n])) / abs(float(ref_stats[n]))
+            if float(ref_stats[n]) != 0.0 else abs(got[n])
+            for n in STAT_NAMES if n != 'clipfrac'}
+    print(what, case, 'worst block %.3g' % max(errs.values()), errs, serr)
+    for name, err in errs.items():
+        assert err <= BOUND, (what, name, err)
+    for name, err in serr.items():
+        assert err <= BOUND, (what, name, err)
+    assert got['clipfrac'] == float(np.float32(ref_stats['clipfrac'])), what
+    ref_norm = float(np.sqrt(np.sum(np.asarray(ref_grad) ** 2)))
+    assert abs(got['grad_norm'] - ref_norm) <= BOUND * ref_norm, what
+
+
+# ------------------------------------------------------------------ 1. GAE
+def _rollout(name, num_envs, stream_handle):
+    """A K-step closed-loop rollout of `num_envs` envs of a policy_cases
+    shape on the given stream: (engine, policy, env fields, policy fields,
+    last_values, rows)."""
+    import torch
+    kind, kw = pc.ROLLOUT_SHAPES[name]
+    rows, D, A = pc.rollout_dims(name)
+    if kind == 'optimize':
+        from custom_envs_amd.engine import OptimizeEngine
+        features, targets = pc.rollout_dataset(name)
+        eng = OptimizeEngine(features, targets, num_envs=num_envs, batch_size=kw['batch_size'],
+                             max_steps=4)
+        eng.seed([21 + i for i in range(num_envs)])
+        rows = num_envs
+    else:
+        from custom_envs_amd.multi_engine import MultiOptEngine
+        eng = MultiOptEngine(num_envs, kw['problem'], max_batches=4, max_history=5)
+        rows = num_envs * (rows // kw['num_envs'])
+    eng.set_stream(stream_handle)
+    params, _ = pc.rollout_policy_inputs(name)
+    policy = MlpPolicy(D, A, pc.ROLLOUT_HIDDEN)
+    policy.set_params(params)
+    noise = np.random.RandomState(11).normal(0, 1, (pc.ROLLOUT_K, rows, A)).astype(np.float32)
+    first = eng.alloc_device_outputs()
+    eng.reset_device(first)
+    fields, rec, pfields, prec = eng.alloc_policy_rollout(pc.ROLLOUT_K, policy)
+    eng.rollout_policy(pc.ROLLOUT_K, policy, first['obs'], torch.from_numpy(noise).cuda(),
+                       fields, rec, pfields, prec)
+    last = policy.forward_device(fields['obs'][pc.ROLLOUT_K - 1])
+    return eng, policy, fields, pfields, last['value'], rows
+
+
+@pytest.mark.parametrize('name, num_envs', [('lr_two_class_f64', 1), ('lr_two_class_f64', 3),
+                                            ('lr_two_class_f64', 65), ('multi_func4', 2)])
+def test_gae_parity_on_rollout_records(name, num_envs):
+    import torch
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):       # the engine's launches and the learner's share it
+        eng, policy, fields, pfields, last_values, rows = _rollout(name, num_envs,
+                                                                   stream.cuda_stream)
+        learner = PPO2Learner(policy, gamma=0.99, lam=0.95)
+        rewards, dones, values = fields['reward'], fields['done'], pfields['value']
+        assert tuple(rewards.shape) == (pc.ROLLOUT_K, rows)
+        assert rewards.stride(0) > rows and values.stride(0) > rows      # strided records
+        adv, ret = learner.gae(rewards=rewards, values=values, dones=dones, last_values=last_values)
+        stream.synchronize()
+    r, v, d, lv = _np(rewards), _np(values), _np(dones), _np(last_values)
+    assert d.sum() == 2 * rows                      # two episode ends inside K
+    ref_adv, ref_ret = gae_numpy(r, v, d, lv, 0.99, 0.95)
+    for got, ref in ((_np(adv), ref_adv), (_np(ret), ref_ret)):
+        err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
+        print('gae', name, rows, err)
+        assert err <= BOUND
+    a32, r32 = gae_numpy(r, v, d, lv, 0.99, 0.95, dtype=np.float32)
+    assert np.array_equal(_np(adv), a32) and np.array_equal(_np(ret), r32)
+    learner.close()
+    policy.close()
+    eng.close()
+
+
+# ---------------------------------------------------------- 2. gradient parity
+@pytest.mark.parametrize('case', cases.CASES, ids=cases.CASE_IDS)
+def test_gradient_parity(case):
+    import torch
+    learner, inputs = _learner(case)
+    grad, stats = learner.grad(_dev(inputs))
+    torch.cuda.synchronize()
+    _check(case, _np(grad), stats, _reference(case), 'gradient parity')
+    # the statement in float32 on the same inputs, for scale
+    _, g32 = loss_grad_numpy(inputs['params'], *[inputs[n] for n in cases.BATCH_FIELDS],
+                             hp=cases.HP, hidden=inputs['hidden'], dtype=np.float32)
+    print('float32 statement', case, max(cases.block_errs(case, g32, _reference(case)[1]).values()))
+    learner.close()
+    learner.policy.close()
+
+
+def test_gradient_parity_without_value_clip_and_normalisation():
+    import torch
+    case = cases.CASES[2]
+    learner, inputs = _learner(case, cliprange_vf=-1.0, normalize_adv=False)
+    grad, stats = learner.grad(_dev(inputs))
+    torch.cuda.synchronize()
+    ref = loss_grad_numpy(inputs['params'], *[inputs[n] for n in cases.BATCH_FIELDS],
+                          hp=cases.HP._replace(cliprange_vf=-1.0, normalize_adv=False),
+                          hidden=inputs['hidden'])
+    _check(case, _np(grad), stats, ref, 'no value clip')
+    learner.close()
+    learner.policy.close()
+
+
+# ------------------------------------------------------------------- 3. idx
+def test_idx_gathers_rows():
+    import torch
+    case = cases.CASES[3]                        # 130 rows as the [K R] batch
+    learner, inputs = _learner(case)
+    batch = _dev(inputs)
+    rs = np.random.RandomState(7)
+    sub = rs.permutation(case[0])[:70].astype(np.int32)
+    gathered = {n: inputs[n][sub] for n in cases.BATCH_FIELDS}
+    ref = loss_grad_numpy(inputs['params'], *[gathered[n] for n in cases.BATCH_FIELDS],
+                          hp=cases.HP, hidden=inputs['hidden'])
+    g_idx, s_idx = learner.grad(batch, torch.from_numpy(sub).cuda())
+    g_copy, s_copy = learner.grad(_dev(gathered))
+    torch.cuda.synchronize()
+    _check(case, _np(g_idx), s_idx, ref, 'idx subset')
+    _check(case, _np(g_copy), s_copy, ref, 'gathered copy')
+    assert np.array_equal(_np(g_idx), _np(g_copy))       # the same rows in the same order
+    assert np.array_equal(_np(s_idx.tensor), _np(s_copy.tensor))
+    # every row, permuted: the summation order alone differs
+    perm = rs.permutation(case[0]).astype(np.int32)
+    g_perm, s_perm = learner.grad(batch, torch.from_numpy(perm).cuda())
+    torch.cuda.synchronize()
+    _check(case, _np(g_perm), s_perm, _reference(case), 'idx permutation')
+    learner.close()
+    learner.policy.close()
+
+
+# ---------------------------------------------------------- 4. determinism
+@pytest.mark.parametrize('case', [cases.CASES[2], cases.CASES[4]], ids=[cases.CASE_IDS[2], cases.CASE_IDS[4]])
+def test_same_call_twice_is_bit_identical(case):
+    import torch
+    learner, inputs = _learner(case)
+    batch = _dev(inputs)
+    g1, s1 = learner.grad(batch)
+    g2, s2 = learner.grad(batch)
+    torch.cuda.synchronize()
+    assert np.array_equal(_np(g1), _np(g2))
+    assert np.array_equal(_np(s1.tensor), _np(s2.tensor))
+    learner.close()
+    learner.policy.close()
+
+
+# ------------------------------------------------------ 5. grid independence
+@pytest.mark.parametrize('case', [cases.CASES[2], cases.CASES[4]], ids=[cases.CASE_IDS[2], cases.CASE_IDS[4]])
+def test_grid_limits_agree(case):
+    import torch
+    grads = {}
+    for limit in (1, 2, 0):
+        learner, inputs = _learner(case, grid_limit=limit)
+        grad, stats = learner.grad(_dev(inputs))
+        torch.cuda.synchronize()
+        grads[limit] = _np(grad)
+        _check(case, grads[limit], stats, _reference(case), 'grid_limit %d' % limit)
+        learner.close()
+        learner.policy.close()
+    for limit in (2, 0):
+        errs = cases.block_errs(case, grads[limit], grads[1].astype(np.float64))
+        assert max(errs.values()) <= BOUND, (limit, errs)
+
+
+# ------------------------------------------------------------------ 6. step
+@pytest.mark.parametrize('case, max_grad_norm, bites', [(cases.CASES[2], 0.05, True),
+                                                        (cases.CASES[3], 100.0, False)],
+                         ids=['clip_bites', 'clip_idle'])
+def test_three_steps_follow_the_statement(case, max_grad_norm, bites):
+    import torch
+    lr = 1e-2
+    learner, inputs = _learner(case, max_grad_norm=max_grad_norm, lr=lr)
+    batch = _dev(inputs)
+    args = [inputs[n] for n in cases.BATCH_FIELDS]
+    p = inputs['params'].astype(np.float64)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    for t in (1, 2, 3):
+        ref_stats, g = loss_grad_numpy(p, *args, hp=cases.HP, hidden=inputs['hidden'])
+        assert (np.sqrt(np.sum(g * g)) > max_grad_norm) == bites
+        p, m, v = adam_step_numpy(p, g, m, v, t, lr, max_grad_norm)
+        stats = learner.step(batch)
+        got = learner.get_params()
+        err = np.linalg.norm(got - p) / np.linalg.norm(p)
+        print('step', t, case, err, stats.stats()['loss'], float(ref_stats['loss']))
+        assert err <= BOUND, (t, err)
+        assert abs(stats.stats()['loss'] - float(ref_stats['loss'])) <= BOUND * abs(float(ref_stats['loss']))
+    assert np.linalg.norm(p - inputs['params']) > 100 * BOUND * np.linalg.norm(p)    # it moved
+    # the policy's image was repacked: its forward is the statement's at p
+    out = learner.policy.forward_device(batch['obs'])
+    torch.cuda.synchronize()
+    ref = forward_numpy(inputs['obs'], None, p, inputs['hidden'])
+    assert pc.rel_err(_np(out['action']), ref['mean']) <= BOUND
+    assert pc.rel_err(_np(out['value']), ref['value']) <= BOUND
+    learner.close()
+    learner.policy.close()
+
+
+# ----------------------------------------------------------- 7. closed loop
+def _closed_loop():
+    import torch
+    from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
+    name, E, K = 'lr_two_class_f64', 3, 10
+    features, targets = pc.rollout_dataset(name)
+    rows, D, A = pc.rollout_dims(name)
+    params, _ = pc.rollout_policy_inputs(name)
+    policy = MlpPolicy(D, A, pc.ROLLOUT_HIDDEN)
+    policy.set_params(params)
+    learner = PPO2Learner(policy, lr=1e-2)
+    noise = torch.from_numpy(np.random.RandomState(13).normal(0, 1, (2, K, rows, A))
+                             .astype(np.float32)).cuda()
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(5)
+    env = GPUVecEnv(E, data_set=(features, targets), max_steps=4, seed=[21, 22, 23])
+    env.reset()
+    first = env.collect(policy, K, noise[0])
+    adv, ret = learner.gae(first)
+    stats = learner.update(first, noptepochs=2, nminibatches=2, generator=gen)
+    second = env.collect(policy, K, noise[1])
+    torch.cuda.synchronize()
+    out = {'adv': _np(adv), 'ret': _np(ret), 'values0': _np(first['values']),
+           'values1': _np(second['values']), 'rewards1': _np(second['rewards']),
+           'params': learner.get_params(), 'stats': np.stack([_np(s.tensor) for s in stats])}
+    env.close()
+    learner.close()
+    policy.close()
+    return out
+
+
+def test_collect_gae_update_collect():
+    a = _closed_loop()
+    assert a['stats'].shape == (4, 8) and np.isfinite(a['stats']).all()
+    assert np.isfinite(a['values1']).all() and np.isfinite(a['params']).all()
+    assert not np.array_equal(a['values0'], a['values1'])
+    # the first value of the second rollout comes from the updated network
+    assert np.max(np.abs(a['values1'][0] - a['values0'][-1])) > 0
+    b = _closed_loop()
+    for key in a:
+        assert np.array_equal(a[key], b[key]), key
