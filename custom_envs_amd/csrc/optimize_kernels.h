@@ -561,6 +561,35 @@ __device__ __forceinline__ double log_pos(double q) {
 }
 __device__ __forceinline__ float log_pos(float q) { return __logf(q); }
 
+// log(x) for a positive normal x through the exp table the two-class kernels
+// already hold (CE_LR_TLOG): x = 2^ex m, m in [1/2, 1).  v_log_f32 is a
+// base-2 log, so j = rint(-2047 log2f(m)) in [0, 2047] (the 1.5 2^23 shifter
+// leaves the integer in the low mantissa bits: no conversion, and the mask
+// keeps any input inside the table) is within 1.5 table steps of
+// -2048 log2(m).  T[j] = 2^(j/2048) as it stands is the reduction factor:
+// z = m T[j] - 1 (one exact-product fma), |z| <= 1.5 ln2/2048 = 5.1e-4
+// (2.5 steps, 8.5e-4 < 2^-10, with j one off either way), log1p(z) by its
+// degree-4 Taylor polynomial (z^5/5 < 9e-17), and
+// log x = (2048 ex - j) ln2/2048 + log1p(z) with exp_neg_tab's split
+// constants (n kH is exact: kLn2Hi ends in 32 zero bits, |n| < 2^22).  The
+// scale 2047 rather than 2048 is what needs no special case: m = 1/2 lands
+// on the table's last entry, not one past it.  20 instructions with a
+// dependent depth of 13 against log_pos's 55 in one chain; within 1.5 ulp
+// for |log x| >= 0.5 and 1.3e-16 absolute below (tests/test_log_table.py).
+__device__ __forceinline__ double log_pos_tab(double x, const double *tab) {
+    constexpr double kH = kLn2Hi / kLrExpTab, kL = kLn2Lo / kLrExpTab;
+    const int ex = __builtin_amdgcn_frexp_exp(x);
+    const double m = __builtin_amdgcn_frexp_mant(x);
+    const float lf = __builtin_amdgcn_logf(static_cast<float>(m));      // log2(m) in [-1, 0]
+    const float sh = fmaf(lf, -static_cast<float>(kLrExpTab - 1), 0x1.8p23f);
+    const int j = __float_as_int(sh) & (kLrExpTab - 1);
+    const double z = fma(m, tab[j], -1.0);
+    const double q = fma(fma(z, -0.25, 1.0 / 3.0), z, -0.5);
+    const double lp = fma(z * z, q, z);
+    const double n = static_cast<double>((ex << kLrExpBits) - j);
+    return fma(n, kH, fma(n, kL, lp));
+}
+
 // Two-class rows are stored pre-multiplied by s_y = +1 (y = 0) or -1 (y = 1)
 // (engine.hip builds the image), so one dot product gives u = s_y z with
 // z = x.(w0 - w1) the logit margin of class 0.  Negating an FMA chain's

@@ -92,6 +92,20 @@ typedef double lr_d4 __attribute__((ext_vector_type(4)));
 #ifndef CE_LR_TGLOBAL
 #define CE_LR_TGLOBAL 1
 #endif
+//  CE_LR_TLOG     the loss logarithm through the same table (log_pos_tab, 20
+//                 instructions, dependent depth 13) instead of log_pos's
+//                 float32 guess refined by a degree-10 exponential (55
+//                 instructions in one chain ahead of the step's barrier)
+#ifndef CE_LR_TLOG
+#define CE_LR_TLOG 1
+#endif
+//  CE_LR_RCPB     one v_rcp_f64 for the four softmax values of a tile in a
+//                 lane (lr_post4) where the |u| bound allows the product of
+//                 four denominators; v_rcp_f64 issues at 16.8 cycles against
+//                 5.3 for a multiply (profiles/archive/r01_f64_costs.jsonl)
+#ifndef CE_LR_RCPB
+#define CE_LR_RCPB 1
+#endif
 
 constexpr int kLrEnvs = 16;                    // envs per workgroup (MFMA N)
 
@@ -224,6 +238,114 @@ __device__ __forceinline__ unsigned lr_miss(double u, bool valid) {
     return valid ? hi >> 31 : 1u;
 }
 __device__ __forceinline__ int lr_hit(double u) { return __double_as_longlong(u) >= 0 ? 1 : 0; }
+
+// The loss logarithm of the two-class kernels: through the exp table they
+// hold (CE_LR_TLOG), or log_pos
+__device__ __forceinline__ double lr_log(double x, const double *tab) {
+#if CE_LR_TLOG && CE_LR_TEXP
+    return log_pos_tab(x, tab);
+#else
+    (void)tab;
+    return log_pos(x);
+#endif
+}
+
+// The row loop has three bodies, chosen per step from the lane's partial ub
+// of the |u| bound sum_f max_r |x_rf| |w'_f0 - w'_f1| (features 4k + h of
+// env c: four partials make the sum).  Every wave of a workgroup forms the
+// same partials, so the choice is uniform over the workgroup.
+//   batched  every partial below 40: |u| < 160, so 1 + e^-u < 2^231 and the
+//            product of a tile's four denominators in a lane stays below
+//            2^924 with a normal reciprocal (lr_post4, CE_LR_RCPB)
+//   free     below 162.5: |u| < 650, no u can leave the exp's [-700, 750]
+//            argument range, no clamp (CE_LR_NOCLAMP)
+//   clamped  anything else, NaN and infinite weights included
+constexpr int kLrBatched = 0, kLrFree = 1, kLrClamped = 2;
+template <int T>
+using LrTier = std::integral_constant<int, T>;
+__device__ __forceinline__ int lr_tier(double ub) {
+#if CE_LR_NOCLAMP
+#if CE_LR_RCPB
+    if (__all(ub < 40.0)) return kLrBatched;
+#endif
+    return __all(ub < 162.5) ? kLrFree : kLrClamped;
+#else
+    (void)ub;
+    return kLrClamped;
+#endif
+}
+template <typename Rows>
+__device__ __forceinline__ void lr_run_tier(int tier, Rows &&rows) {
+    if (tier == kLrBatched) rows(LrTier<kLrBatched>{});
+    else if (tier == kLrFree) rows(LrTier<kLrFree>{});
+    else rows(LrTier<kLrClamped>{});
+}
+
+// Per (row, env) after the exp, from t = e^-u and p_y = inv = 1/(1 + t): the
+// gradient weight q = t p_y, the loss factor p_y + 1e-16 into the running
+// product, min |u| (the tie flag) and the argmax miss.  A padding row
+// (valid == false) leaves every statistic alone.
+__device__ __forceinline__ void lr_post_tail(double uq, double t, double inv, bool valid, double &qo,
+                                             double &prod, double &umin, unsigned &miss) {
+    qo = valid ? t * inv : 0.0;
+    prod *= valid ? inv + 1e-16 : 1.0;
+    // min(umin, |u|) as one v_min_f64 with the abs modifier (fmin of an MFMA
+    // result gets a canonicalising v_max_f64 first)
+    {
+        const double au = valid ? uq : 1.0;
+        asm("v_min_f64 %0, %1, |%2|" : "=v"(umin) : "v"(umin), "v"(au));
+    }
+    miss += lr_miss(uq, valid);
+}
+// one value: its own reciprocal (the free and the clamped body)
+__device__ __forceinline__ void lr_post(double uq, double t, bool valid, double &qo, double &prod,
+                                        double &umin, unsigned &miss) {
+#if CE_LR_RCP1
+    const double inv = rcp_newton1(1.0 + t);
+#else
+    const double inv = rcp_unit(1.0 + t);
+#endif
+    lr_post_tail(uq, t, inv, valid, qo, prod, umin, miss);
+}
+// the four values of one tile in a lane (the forward's four C registers),
+// one reciprocal between them (the batched body): with d_i = 1 + t_i and
+// p = (d0 d1)(d2 d3), 1/d0 = ((1/p) d2 d3) d1 and so on.  Each value carries
+// four more roundings than its own reciprocal would (d0 d1, p, times d2 d3,
+// times d1), each up to one ulp of the result, on top of the Newton step's
+// e^2 (32 ulp at a 2^-24 seed): with rcp_newton1(p) the worst is 34.9 ulp
+// against rcp_newton1's own 32.5 (tests/test_log_table.py, the seed modelled
+// at its measured bound).  So the seed r0 gets the third-order correction
+// 1 + s, s = e + e^2, e = 1 - p r0 (what two Newton steps give: 3.4 ulp),
+// and it is applied to r0 d2 d3 and r0 d0 d1, which are formed beside e and
+// s: the chain from v_rcp_f64 to a value is four operations, as with one
+// Newton step (two Newton steps on r0 itself, six, measured 1 % slower).
+// One v_rcp_f64, four FMAs and nine multiplies for four reciprocals and
+// eight FMAs.  CE_LR_RCPB_NEWTON=1 is the plain rcp_newton1(p) form for the
+// A/B.  Padding rows enter the product with their finite d (u = 0, d = 2).
+// All three two-class kernels batch the same four values, so they stay
+// bit-identical.
+#ifndef CE_LR_RCPB_NEWTON
+#define CE_LR_RCPB_NEWTON 2
+#endif
+__device__ __forceinline__ void lr_post4(const lr_d4 &u, const double (&t)[4], const bool (&valid)[4],
+                                         double (&qo)[4], double &prod, double &umin, unsigned &miss) {
+    const double d0 = 1.0 + t[0], d1 = 1.0 + t[1], d2 = 1.0 + t[2], d3 = 1.0 + t[3];
+    const double ab = d0 * d1, cd = d2 * d3;
+    const double p = ab * cd;
+#if CE_LR_RCPB_NEWTON == 1
+    const double r = rcp_newton1(p);
+    const double rab = r * cd, rcd = r * ab;
+#else
+    const double r0 = __builtin_amdgcn_rcp(p);
+    const double e = fma(-p, r0, 1.0);
+    const double s = fma(e, e, e);
+    const double rab0 = r0 * cd, rcd0 = r0 * ab;
+    const double rab = fma(rab0, s, rab0), rcd = fma(rcd0, s, rcd0);
+#endif
+    const double inv[4] = {rab * d1, rab * d0, rcd * d3, rcd * d2};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lr_post_tail(u[i], t[i], inv[i], valid[i], qo[i], prod, umin, miss);
+}
 
 // sum of an int over lanes l, l^16, l^32, l^48 (permlane swaps)
 __device__ __forceinline__ int fold_env_lanes(int v) {
@@ -395,18 +517,16 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     }
 #if CE_LR_NOCLAMP
     // |u| <= sum_f |x_f| |w'_f0 - w'_f1| <= sum_f max_r |x_rf| |wd_f| (the
-    // rounding of u and of this sum is ~1e-15 relative): below 650, no u can
-    // leave the exp's [-700, 750] argument range, so the row loop runs
-    // without the clamp.  Every wave forms the same wd, so the choice is
-    // uniform over the workgroup.
+    // rounding of u and of this sum is ~1e-15 relative): the lane's partial
+    // covers features 4k + h of env c, and four partials below a quarter of
+    // a bound keep |u| below it (sufficient, no cross-lane fold).  lr_tier
+    // picks the row body.
     double ub = 0.0;
 #pragma unroll
     for (int k = 0; k < NKF; ++k) ub = fma(fabs(wd[k]), xm[k], ub);
-    // the lane's partial covers features 4k + h of env c: four partials
-    // below 162.5 bound the sum below 650 (sufficient, no cross-lane fold)
-    const bool bounded = __all(ub < 162.5);
+    const int tier = lr_tier(ub);
 #else
-    const bool bounded = false;
+    const int tier = kLrClamped;
 #endif
     const int cur = step_prev + 1;
     // the epilogue's divisors are known now: their reciprocals leave the
@@ -462,35 +582,30 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     // cover it, and the 128-register budget has no room for 4)
     constexpr int QC = W >= 16 ? 2 : 4;
     // per (row, env) after the exp: p_y, q, the loss factor, min |u|, hit
-    auto post = [&](double uq, double t, int y, double &qo) {
-#if CE_LR_RCP1
-        const double inv = rcp_newton1(1.0 + t);        // p_y
-#else
-        const double inv = rcp_unit(1.0 + t);           // p_y
-#endif
-        const bool valid = !PAD || y >= 0;
-        qo = valid ? t * inv : 0.0;
-        prod *= valid ? inv + 1e-16 : 1.0;
-        // min(umin, |u|) as one v_min_f64 with the abs modifier (fmin of an
-        // MFMA result gets a canonicalising v_max_f64 first)
-        {
-            const double au = valid ? uq : 1.0;
-            asm("v_min_f64 %0, %1, |%2|" : "=v"(umin) : "v"(umin), "v"(au));
-        }
-        miss += lr_miss(uq, valid);
-    };
-    auto softmax = [&](auto clamp_c, const lr_d4 &u, const int (&ys)[4], double (&qv)[4]) {
+    // (lr_post; the batched body takes the tile's four values together)
+    const double *tab = TLDS ? tab_s : tab_g;
+    auto softmax = [&](auto tier_c, const lr_d4 &u, const int (&ys)[4], double (&qv)[4]) {
+        constexpr int TIER = decltype(tier_c)::value;
+        [[maybe_unused]] double t4[4];
 #pragma unroll
         for (int q0 = 0; q0 < 4; q0 += QC) {
             double tx[QC];
 #pragma unroll
             for (int i = 0; i < QC; ++i) {
-                if constexpr (decltype(clamp_c)::value) tx[i] = clamp_u(u[q0 + i]);
+                if constexpr (TIER == kLrClamped) tx[i] = clamp_u(u[q0 + i]);
                 else tx[i] = u[q0 + i];
             }
-            lr_exp_neg<QC>(tx, TLDS ? tab_s : tab_g);   // t = e^-u
+            lr_exp_neg<QC>(tx, tab);                    // t = e^-u
 #pragma unroll
-            for (int i = 0; i < QC; ++i) post(u[q0 + i], tx[i], ys[q0 + i], qv[q0 + i]);
+            for (int i = 0; i < QC; ++i) {
+                if constexpr (TIER == kLrBatched) t4[q0 + i] = tx[i];
+                else lr_post(u[q0 + i], tx[i], !PAD || ys[q0 + i] >= 0, qv[q0 + i], prod, umin, miss);
+            }
+        }
+        if constexpr (TIER == kLrBatched) {
+            const bool valid[4] = {!PAD || ys[0] >= 0, !PAD || ys[1] >= 0, !PAD || ys[2] >= 0,
+                                   !PAD || ys[3] >= 0};
+            lr_post4(u, t4, valid, qv, prod, umin, miss);
         }
     };
     auto forward = [&](const double (&xv)[NKF]) {
@@ -531,12 +646,12 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     const int t_first = wave;
 #endif
     const int none[4] = {0, 0, 0, 0};
-    auto row_loop = [&](auto clamp_c) {
+    auto row_loop = [&](auto tier_c) {
     for (int t = t_first; t < ntiles; t += NT * kLrWaves) {
         since += NT;
         rows_seen += 4 * NT;
         if (since > 4) {                                // 16 factors in (1e-16, 1]: fold
-            nlog -= log_pos(prod);
+            nlog -= lr_log(prod, tab);
             prod = 1.0;
             since = NT;
         }
@@ -564,13 +679,12 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             double qv[4];
-            softmax(clamp_c, u[i], PAD ? ys[i] : none, qv);
+            softmax(tier_c, u[i], PAD ? ys[i] : none, qv);
             gradient(i, qv);
         }
     }
     };
-    if (bounded) row_loop(std::false_type{});
-    else row_loop(std::true_type{});
+    lr_run_tier(tier, row_loop);
     // a tie (p0 == p1) is np.argmax's class 0: hit iff y == 0.  Only a wave
     // that saw |u| < 2^-52 re-walks its tiles with the exact test e^-|u| == 1
     // (practically never).
@@ -613,7 +727,7 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     }
     // partials of this wave: s (features h + 4r of env c); -log of the
     // cross-entropy factors and the hits summed over the env's 4 lane groups
-    double lsum = nlog - log_pos(prod);
+    double lsum = nlog - lr_log(prod, tab);
     lsum = fold_pair<16>(lsum, lsum);
     lsum = fold_pair<32>(lsum, lsum);
     const double hsum = static_cast<double>(fold_env_lanes(hits));

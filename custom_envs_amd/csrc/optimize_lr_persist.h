@@ -260,41 +260,26 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
             for (int k = 0; k < NKF; ++k) an[k] = *reinterpret_cast<const float2 *>(actn + ioff[k]);
         }
 #if CE_LR_NOCLAMP
-        // |u| <= sum_f max_r |x_rf| |wd_f| < 650: no exp argument can leave
-        // [-700, 750], the row work runs without the clamp (uniform choice)
+        // the lane's partial of |u| <= sum_f max_r |x_rf| |wd_f| picks this
+        // step's row body (lr_tier: batched reciprocals, clamp-free, clamped)
         double ub = 0.0;
 #pragma unroll
         for (int k = 0; k < NKF; ++k) ub = fma(fabs(wd[k]), xm[k], ub);
-        // the lane's partial covers features 4k + h of env c: four partials
-        // below 162.5 bound the sum below 650 (sufficient, no cross-lane fold)
-        const bool bounded = __all(ub < 162.5);
+        const int tier = lr_tier(ub);
 #else
-        const bool bounded = false;
+        const int tier = kLrClamped;
 #endif
         // ---- the row work: per group of NG tiles every forward chain, then
         // per tile the signed two-class softmax and its 4 gradient MFMAs
         lr_d4 sacc = {0.0, 0.0, 0.0, 0.0};                 // one gradient chain, tile order
         double prod = 1.0, nlog = 0.0, umin = 1.0;
         unsigned miss = 0;
-        auto post = [&](double uq, double tq, bool valid, double &qo) {
-#if CE_LR_RCP1
-            const double inv = rcp_newton1(1.0 + tq);       // p_y
-#else
-            const double inv = rcp_unit(1.0 + tq);
-#endif
-            qo = valid ? tq * inv : 0.0;
-            prod *= valid ? inv + 1e-16 : 1.0;
-            {
-                const double au = valid ? uq : 1.0;
-                asm("v_min_f64 %0, %1, |%2|" : "=v"(umin) : "v"(umin), "v"(au));
-            }
-            miss += lr_miss(uq, valid);
-        };
-        auto rows = [&](auto clamp_c) {
+        auto rows = [&](auto tier_c) {
+            constexpr int TIER = decltype(tier_c)::value;
 #pragma unroll
             for (int g0 = 0; g0 < TPW; g0 += NG) {
                 if (g0 > 0) {                               // 16 factors in (1e-16, 1]: fold
-                    nlog -= log_pos(prod);
+                    nlog -= lr_log(prod, tab_s);
                     prod = 1.0;
                 }
                 lr_d4 u[NG];
@@ -303,20 +288,21 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
 #pragma unroll
                 for (int i = 0; i < NG; ++i) {
                     double qv[4];
+                    static_assert(QC == 4, "the tile's four values go through the exp together");
+                    double tx[QC];
+                    bool valid[QC];
 #pragma unroll
-                    for (int q0 = 0; q0 < 4; q0 += QC) {
-                        double tx[QC];
+                    for (int j = 0; j < QC; ++j) {
+                        if constexpr (TIER == kLrClamped) tx[j] = clamp_u(u[i][j]);
+                        else tx[j] = u[i][j];
+                        valid[j] = !PAD || ((vmask >> (4 * (g0 + i) + j)) & 1u);
+                    }
+                    lr_exp_neg<QC>(tx, tab_s);                      // t = e^-u
+                    if constexpr (TIER == kLrBatched) {
+                        lr_post4(u[i], tx, valid, qv, prod, umin, miss);
+                    } else {
 #pragma unroll
-                        for (int j = 0; j < QC; ++j) {
-                            if constexpr (decltype(clamp_c)::value) tx[j] = clamp_u(u[i][q0 + j]);
-                            else tx[j] = u[i][q0 + j];
-                        }
-                        lr_exp_neg<QC>(tx, tab_s);                  // t = e^-u
-#pragma unroll
-                        for (int j = 0; j < QC; ++j) {
-                            const bool valid = !PAD || ((vmask >> (4 * (g0 + i) + q0 + j)) & 1u);
-                            post(u[i][q0 + j], tx[j], valid, qv[q0 + j]);
-                        }
+                        for (int j = 0; j < QC; ++j) lr_post(u[i][j], tx[j], valid[j], qv[j], prod, umin, miss);
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
@@ -324,8 +310,7 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
                 }
             }
         };
-        if (bounded) rows(std::false_type{});
-        else rows(std::true_type{});
+        lr_run_tier(tier, rows);
         // a tie (p0 == p1, |u| < 2^-52) is np.argmax's class 0: hit iff y == 0;
         // only a wave that saw one re-walks its tiles exactly (practically never)
         int hits = 4 * TPW - static_cast<int>(miss);
@@ -350,7 +335,7 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
         }
         // this wave's partials: s (features h + 4r of env c); -log of the
         // cross-entropy factors and the hits over the env's 4 lane groups
-        double lsum = nlog - log_pos(prod);
+        double lsum = nlog - lr_log(prod, tab_s);
         lsum = fold_pair<16>(lsum, lsum);
         lsum = fold_pair<32>(lsum, lsum);
         const double hsum = static_cast<double>(fold_env_lanes(hits));
@@ -527,7 +512,11 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
     if (wave < W) {
         // ======================= row waves =======================
 #if CE_LP_ROW_PRIO > 0
-        __builtin_amdgcn_s_setprio(CE_LP_ROW_PRIO);      // experiment: row waves win arbitration
+        // the row waves win every issue arbitration against the epilogue
+        // wave of their SIMD (the step's critical path is theirs): priority
+        // 3, the shipped default, measured 2.048-2.050 against 2.056-2.065 us
+        // per step without it
+        __builtin_amdgcn_s_setprio(CE_LP_ROW_PRIO);
 #endif
         const int e = e0 + c;
         const bool env_ok = e < E;
@@ -631,11 +620,9 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             double ub = 0.0;
 #pragma unroll
             for (int k = 0; k < NKF; ++k) ub = fma(fabs(wd[k]), xm[k], ub);
-            // the lane's partial covers features 4k + h of env c: four partials
-            // below 162.5 bound the sum below 650 (sufficient, no cross-lane fold)
-            const bool bounded = __all(ub < 162.5);
+            const int tier = lr_tier(ub);                   // this step's row body
 #else
-            const bool bounded = false;
+            const int tier = kLrClamped;
 #endif
             lr_d4 sacc = {0.0, 0.0, 0.0, 0.0};             // one gradient chain, tile order
             double gacc[NKF];                               // G4: one chain per feature group
@@ -643,25 +630,12 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             for (int g = 0; g < NKF; ++g) gacc[g] = 0.0;
             double prod = 1.0, nlog = 0.0, umin = 1.0;
             unsigned miss = 0;
-            auto post = [&](double uq, double tq, bool valid, double &qo) {
-#if CE_LR_RCP1
-                const double inv = rcp_newton1(1.0 + tq);
-#else
-                const double inv = rcp_unit(1.0 + tq);
-#endif
-                qo = valid ? tq * inv : 0.0;
-                prod *= valid ? inv + 1e-16 : 1.0;
-                {
-                    const double au = valid ? uq : 1.0;
-                    asm("v_min_f64 %0, %1, |%2|" : "=v"(umin) : "v"(umin), "v"(au));
-                }
-                miss += lr_miss(uq, valid);
-            };
-            auto rows = [&](auto clamp_c) {
+            auto rows = [&](auto tier_c) {
+                constexpr int TIER = decltype(tier_c)::value;
 #pragma unroll
                 for (int g0 = 0; g0 < TPW; g0 += NG) {
                     if (g0 > 0) {
-                        nlog -= log_pos(prod);
+                        nlog -= lr_log(prod, tab_s);
                         prod = 1.0;
                     }
                     lr_d4 u[NG];
@@ -685,20 +659,22 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                             for (int q = 0; q < 4; ++q) gv[q] = xgs[wave][g0 + i][q][lane];
                         }
                         double qv[4];
+                        static_assert(QC == 4, "the tile's four values go through the exp together");
+                        double tx[QC];
+                        bool valid[QC];
 #pragma unroll
-                        for (int q0 = 0; q0 < 4; q0 += QC) {
-                            double tx[QC];
+                        for (int j = 0; j < QC; ++j) {
+                            if constexpr (TIER == kLrClamped) tx[j] = clamp_u(u[i][j]);
+                            else tx[j] = u[i][j];
+                            valid[j] = !PAD || ((vmask >> (4 * (g0 + i) + j)) & 1u);
+                        }
+                        lr_exp_neg<QC>(tx, tab_s);
+                        if constexpr (TIER == kLrBatched) {
+                            lr_post4(u[i], tx, valid, qv, prod, umin, miss);
+                        } else {
 #pragma unroll
-                            for (int j = 0; j < QC; ++j) {
-                                if constexpr (decltype(clamp_c)::value) tx[j] = clamp_u(u[i][q0 + j]);
-                                else tx[j] = u[i][q0 + j];
-                            }
-                            lr_exp_neg<QC>(tx, tab_s);
-#pragma unroll
-                            for (int j = 0; j < QC; ++j) {
-                                const bool valid = !PAD || ((vmask >> (4 * (g0 + i) + q0 + j)) & 1u);
-                                post(u[i][q0 + j], tx[j], valid, qv[q0 + j]);
-                            }
+                            for (int j = 0; j < QC; ++j)
+                                lr_post(u[i][j], tx[j], valid[j], qv[j], prod, umin, miss);
                         }
                         if constexpr (G4) {
                             // S[4g + m][4b + n] += X~[4q + k][4g + m] q[4q + k][4b + n]:
@@ -716,8 +692,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                     }
                 }
             };
-            if (bounded) rows(std::false_type{});
-            else rows(std::true_type{});
+            lr_run_tier(tier, rows);
             int hits = 4 * TPW - static_cast<int>(miss);
             if (__any(umin < 0x1p-52)) {
 #pragma unroll
@@ -738,7 +713,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                         if (yv[q] >= 0 && tx[q] == 1.0) hits += (yv[q] == 0 ? 1 : 0) - lr_hit(uu[q]);
                 }
             }
-            double lsum = nlog - log_pos(prod);
+            double lsum = nlog - lr_log(prod, tab_s);
             lsum = fold_pair<16>(lsum, lsum);
             lsum = fold_pair<32>(lsum, lsum);
             const double hsum = static_cast<double>(fold_env_lanes(hits));

@@ -6,10 +6,12 @@ Compiles csrc/optimize_lr_persist.hip to assembly (the product flags of
 custom_envs_amd/build.py), cuts out the benchmark instance
 (optimize_lr_persist_ws_kernel<3,4,false>), finds the row waves' and the
 epilogue waves' step loops (the two loops that hold an s_barrier), and counts
-per step, by issue class: f64 MFMA, f64 VALU, 32-bit VALU, LDS, VMEM, SALU,
-s_waitcnt and s_nop.  The row loop has two bodies behind the clamp-free test
-(CE_LR_NOCLAMP); the bounded body is the one that runs on the benchmark data
-and is counted (the clamped body and the tie re-walk are listed apart).
+per step, by issue class: f64 MFMA, f64 VALU, 32-bit VALU, transcendental
+VALU (v_rcp_*, v_log_*, ...: priced apart), LDS, VMEM, SALU, s_waitcnt and
+s_nop.  The row loop has three bodies behind the |u| bound's tiers (lr_tier:
+batched reciprocals, clamp-free, clamped); the one that runs on the
+benchmark data (the fewest reciprocals, then the fewest f64 VALU) is counted
+with the blocks around the bodies, and priced beside round 6's counts.
 
 The per-class costs ("Issue budget") turn the counts into
 time: they are measured, not assumed (profiles/r06_mfma_overlap.jsonl and
@@ -60,9 +62,34 @@ def classify(op):
         return 'nop'
     if op.startswith('s_'):
         return 'salu'
+    if op.startswith(TRANS):
+        return 'trans'
     if op.startswith('v_'):
         return 'valu64' if 'f64' in op else 'valu32'
     return 'other'
+
+
+# Transcendental VALU operations: quarter-rate or slower, counted apart from
+# the ordinary f64 / 32-bit classes.  v_rcp_f64 measured 16.76 cycles per
+# instruction with one wave per SIMD (profiles/archive/r01_f64_costs.jsonl).
+TRANS = ('v_rcp_', 'v_rsq_', 'v_sqrt_', 'v_log_', 'v_exp_', 'v_sin_', 'v_cos_')
+
+# ns per instruction ("Issue budget"): the 16x16x4 f64 MFMA
+# 27.6, the 4x4x4 one 0.26 of it, f64 VALU 2.35, 32-bit VALU 2.0,
+# transcendental 16.8 cycles at 2.16 GHz
+COST_NS = {'mfma16': 27.6, 'mfma4': 27.6 * 0.26, 'valu64': 2.35, 'valu32': 2.0, 'trans': 16.8 / 2.16}
+# round 6's tree (CE_LR_TLOG=0, CE_LR_RCPB=0) by the same classes: its 325
+# f64 VALU held 16 v_rcp_f64, its 138 32-bit VALU one v_log_f32
+ROUND6 = {'mfma16': 12, 'mfma4': 48, 'valu64': 309, 'valu32': 137, 'trans': 17}
+
+
+def budget(counts, ops):
+    """The counted classes priced: (class -> count, class -> us, total us)."""
+    n4 = sum(n for op, n in ops.items() if op.startswith('v_mfma_f64_4x4x4'))
+    n = {'mfma16': counts.get('mfma', 0) - n4, 'mfma4': n4, 'valu64': counts.get('valu64', 0),
+         'valu32': counts.get('valu32', 0), 'trans': counts.get('trans', 0)}
+    us = {k: n[k] * COST_NS[k] * 1e-3 for k in n}
+    return n, us, sum(us.values())
 
 
 def count(body, a, b):
@@ -126,8 +153,10 @@ def main():
             blocks.append(cur)
         info = [(blk, count(body, blk[0], blk[1] + 1)[0]) for blk in blocks]
         mf = [(blk, c) for blk, c in info if c.get('mfma', 0) >= 20]
-        # the bounded body: the heavy block with fewer f64 VALU (no clamp)
-        mf.sort(key=lambda x: x[1].get('valu64', 0))
+        # the body that runs on the benchmark data: the heavy block with the
+        # fewest reciprocals (batched, CE_LR_RCPB), then the fewest f64 VALU
+        # (no clamp)
+        mf.sort(key=lambda x: (x[1].get('trans', 0), x[1].get('valu64', 0)))
         if mf:
             bounded = mf[0]
             # the hot path: the blocks ahead of the first row body and the
@@ -140,9 +169,14 @@ def main():
                 rest.update(c)
             total = collections.Counter(bounded[1])
             total.update(rest)
+            hot_ops = collections.Counter()
+            for blk, c in [bounded] + info[:first] + info[last + 1:]:
+                hot_ops.update(count(body, blk[0], blk[1] + 1)[1])
             row['bounded_body'] = bounded[1]
             row['outside_bodies'] = dict(rest)
             row['per_step_bounded'] = dict(total)
+            n, us, tot = budget(total, hot_ops)
+            row['budget'] = {'counts': n, 'us': us, 'total_us': tot}
     txt = json.dumps(res, indent=1)
     if args.json:
         with open(args.json, 'w') as fh:
@@ -152,6 +186,14 @@ def main():
         if 'bounded_body' in lp:
             print('   bounded row body:', lp['bounded_body'])
             print('   around it       :', lp['outside_bodies'])
+        if 'budget' in lp:
+            keys = ('mfma16', 'mfma4', 'valu64', 'valu32', 'trans')
+            r6 = {k: ROUND6[k] * COST_NS[k] * 1e-3 for k in keys}
+            print('   budget, us      : ' + ' '.join('%8s' % k for k in keys) + '    total')
+            for name, n, us in (('round 6', ROUND6, r6), ('this tree', lp['budget']['counts'], lp['budget']['us'])):
+                print('   %-10s count: ' % name + ' '.join('%8d' % n[k] for k in keys))
+                print('   %-10s    us: ' % name + ' '.join('%8.3f' % us[k] for k in keys)
+                      + ' %8.3f' % sum(us[k] for k in keys))
     return 0
 
 
