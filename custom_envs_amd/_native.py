@@ -47,6 +47,8 @@ EXPORTS = (
     'ce_policy_set_bounds', 'ce_policy_forward', 'ce_rollout_policy', 'ce_multi_rollout_policy',
     'ce_ppo2_create', 'ce_ppo2_destroy', 'ce_ppo2_set_params', 'ce_ppo2_get_params',
     'ce_ppo2_gae', 'ce_ppo2_grad', 'ce_ppo2_step',
+    'ce_a2c_create', 'ce_a2c_destroy', 'ce_a2c_set_params', 'ce_a2c_get_params',
+    'ce_a2c_returns', 'ce_a2c_grad', 'ce_a2c_step', 'ce_a2c_update',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -110,6 +112,12 @@ class CePpo2Config(ctypes.Structure):
         'gamma', 'lam', 'cliprange', 'cliprange_vf', 'ent_coef', 'vf_coef', 'max_grad_norm',
         'lr', 'beta1', 'beta2', 'eps')] + [('normalize_adv', ctypes.c_int32),
                                             ('grid_limit', ctypes.c_int32)]
+
+
+class CeA2cConfig(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_float) for name in (
+        'gamma', 'ent_coef', 'vf_coef', 'max_grad_norm', 'lr', 'alpha', 'eps', 'momentum')] + [
+            ('grid_limit', ctypes.c_int32)]
 
 
 class CeState(ctypes.Structure):
@@ -200,6 +208,15 @@ def _declare(lib):
         'ce_ppo2_gae': ([vp, i32, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp], ctypes.c_int),
         'ce_ppo2_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp], ctypes.c_int),
         'ce_ppo2_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp], ctypes.c_int),
+        'ce_a2c_create': ([vp, ctypes.POINTER(CeA2cConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_a2c_destroy': ([vp], None),
+        'ce_a2c_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_a2c_get_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_a2c_returns': ([vp, i32, i64, vp, i64, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_a2c_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_a2c_step': ([vp, i64, i64, vp, vp, vp, vp, vp, f32, vp, vp], ctypes.c_int),
+        'ce_a2c_update': ([vp, i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, vp, vp],
+                          ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

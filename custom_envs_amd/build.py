@@ -31,7 +31,8 @@ def _hipcc():
 def sources():
     return [os.path.join(CSRC, f) for f in ('engine.hip', 'optimize_mfma.hip', 'optimize_lr_persist.hip',
                                             'multi_engine.hip', 'multinn_engine.hip', 'net_engine.hip',
-                                            'policy_engine.hip', 'ppo2_engine.hip', 'seeding.cpp')]
+                                            'policy_engine.hip', 'ppo2_engine.hip', 'a2c_engine.hip',
+                                            'seeding.cpp')]
 
 
 def headers():

@@ -30,6 +30,14 @@ struct ce_ppo2 {
     double *stat_slab = nullptr, *sq = nullptr;
 };
 
+namespace ce {
+
+void ppo2_launch_reduce(const Ppo2ReduceArgs &q, hipStream_t stream) {
+    hipLaunchKernelGGL(ppo2_reduce_kernel, dim3((q.p.n_params + 255) / 256), dim3(256), 0, stream, q);
+}
+
+}  // namespace ce
+
 namespace {
 
 using ce::fail;
@@ -119,7 +127,7 @@ void enqueue_grad(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, co
     q.slab = l->slab;
     q.grad = grad;
     q.sq = l->sq;
-    hipLaunchKernelGGL(ce::ppo2_reduce_kernel, dim3(l->n_sq), dim3(256), 0, stream, q);
+    ce::ppo2_launch_reduce(q, stream);
     ce::Ppo2FinishArgs f{};
     f.n = g.n;
     f.grid = g.grid;
