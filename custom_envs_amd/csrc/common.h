@@ -38,12 +38,14 @@ inline void note_stale(int code, const char *text, const char *where) {
 
 }  // namespace ce
 
-#define CE_CLEAR_STALE_ERROR()                                              \
+// `where`: the entry point's name (a shared body passes its caller's)
+#define CE_CLEAR_STALE_ERROR_AT(where)                                      \
     do {                                                                    \
         const hipError_t stale_ = hipGetLastError();                        \
         if (stale_ != hipSuccess)                                           \
-            ce::note_stale(static_cast<int>(stale_), hipGetErrorString(stale_), __func__); \
+            ce::note_stale(static_cast<int>(stale_), hipGetErrorString(stale_), where); \
     } while (0)
+#define CE_CLEAR_STALE_ERROR() CE_CLEAR_STALE_ERROR_AT(__func__)
 
 #define CE_HIP(call)                                                              \
     do {                                                                          \
@@ -51,6 +53,16 @@ inline void note_stale(int code, const char *text, const char *where) {
         if (err_ != hipSuccess)                                                   \
             return ce::fail(CE_EHIP, std::string(#call " failed: ") +             \
                                          hipGetErrorString(err_));                \
+    } while (0)
+
+// In a create function: a failed HIP call tears the half-built object down
+// through the caller's `bail(code)` and returns CE_EHIP.
+#define CE_TRY(call)                                                           \
+    do {                                                                       \
+        hipError_t err_ = (call);                                              \
+        if (err_ != hipSuccess)                                                \
+            return bail(ce::fail(CE_EHIP, std::string(#call " failed: ") +     \
+                                              hipGetErrorString(err_)));       \
     } while (0)
 
 namespace ce {

@@ -28,16 +28,6 @@
 #include "common.h"
 #include "policy_engine.h"
 
-// In a create function: a failed HIP call tears the half-built engine down
-// through the caller's `bail(code)` and returns CE_EHIP.
-#define CE_TRY(call)                                                           \
-    do {                                                                       \
-        hipError_t err_ = (call);                                              \
-        if (err_ != hipSuccess)                                                \
-            return bail(ce::fail(CE_EHIP, std::string(#call " failed: ") +     \
-                                              hipGetErrorString(err_)));       \
-    } while (0)
-
 namespace ce {
 
 // The members of an output struct in region order: each(f) calls

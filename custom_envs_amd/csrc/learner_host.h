@@ -1,0 +1,227 @@
+// The host shell the two learners share (ppo2_engine.hip, a2c_engine.hip):
+// what every learner holds besides its optimiser state (ce::LearnerCore), its
+// construction and teardown, the parameter entry points, the argument checks
+// that do not depend on the loss, and the launches around the gradient kernel.
+//
+// A learner keeps its config check, its per-tensor null checks, the launch of
+// its own gradient kernel (its loss head's arguments) and its optimiser:
+//   struct ce_x { ce_x_config cfg; <optimiser state>; ce::LearnerCore core; };
+//   create    learner_core_create(l->core, policy, grid_limit, x_grad_kernel, bail),
+//             then its own buffers and one hipDeviceSynchronize
+//   destroy   its own buffers, then learner_core_destroy
+//   gradient  learner_fill_grad_args(g, core, ...), its own fields, the launch,
+//             then learner_enqueue_reduce_finish<x_finish_kernel>(...)
+// Dispatch is static (a kernel that differs is a template parameter); nothing
+// here allocates on a call path, and every argument check precedes the first
+// HIP call.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+
+#include "common.h"
+#include "policy_engine.h"
+#include "ppo_grad_tile.h"
+
+namespace ce {
+
+constexpr int64_t kLearnerMaxRows = int64_t(1) << 24;
+
+struct LearnerCore {
+    ce_policy *policy = nullptr;
+    PolicyPlan plan{};
+    int grid_max = 0;            // workgroups per network the slab holds
+    int n_sq = 0;                // blocks of ppo2_reduce_kernel
+    int w_floats = 0, act_floats = 0;
+    size_t lds_bytes = 0;        // of the gradient kernel for this policy's shape
+    float *params = nullptr;     // the master flat parameters
+    float *grad = nullptr, *slab = nullptr;
+    double *stat_slab = nullptr, *sq = nullptr;
+};
+
+// The plan and the gradient kernel's LDS sizes, the device, grid_max, the
+// kernel's dynamic-LDS attribute and the shared buffers, `params` zeroed.  A
+// failed HIP call goes through the caller's `bail(code)`, which destroys the
+// half-built learner.  The caller synchronises after its own initialisation.
+template <class Bail>
+int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
+                        const void *grad_kernel, Bail &&bail) {
+    c.policy = policy;
+    c.plan = policy_plan(policy);
+    const PolicyPlan &pa = c.plan;
+    int wmax = 0, kmax = 0;
+    for (int net = 0; net < 2; ++net)
+        for (int i = 0; i <= pa.n_hidden; ++i) {
+            wmax = std::max(wmax, pa.in_pad[i] * (pa.out_pad[net][i] + 1));
+            kmax = std::max(kmax, pa.in_pad[i]);
+        }
+    c.w_floats = (wmax + 3) / 4 * 4;
+    c.act_floats = kmax * kPpoLd;
+    c.lds_bytes = static_cast<size_t>(c.w_floats + (pa.n_hidden + 1) * c.act_floats +
+                                      kPpoMaxA * kPpoLd +
+                                      (kPpoRowStats + 2) * kPpoTile) * sizeof(float);
+    c.n_sq = (pa.n_params + 255) / 256;
+    CE_TRY(hipSetDevice(pa.device));
+    hipDeviceProp_t prop;
+    CE_TRY(hipGetDeviceProperties(&prop, pa.device));
+    c.grid_max = grid_limit > 0 ? grid_limit : std::max(1, prop.multiProcessorCount);
+    CE_TRY(hipFuncSetAttribute(grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(kPpoMaxLdsBytes)));   // the limits' need
+    const size_t np = static_cast<size_t>(pa.n_params) * sizeof(float);
+    CE_TRY(hipMalloc(&c.params, np));
+    CE_TRY(hipMalloc(&c.grad, np));
+    CE_TRY(hipMalloc(&c.slab, static_cast<size_t>(c.grid_max) * pa.img_floats * sizeof(float)));
+    CE_TRY(hipMalloc(&c.stat_slab, static_cast<size_t>(c.grid_max) * 2 * kPpoRowStats * sizeof(double)));
+    CE_TRY(hipMalloc(&c.sq, static_cast<size_t>(c.n_sq) * sizeof(double)));
+    CE_TRY(hipMemset(c.params, 0, np));
+    return CE_OK;
+}
+
+inline void learner_core_destroy(LearnerCore &c) {
+    for (void *q : {static_cast<void *>(c.params), static_cast<void *>(c.grad),
+                    static_cast<void *>(c.slab), static_cast<void *>(c.stat_slab),
+                    static_cast<void *>(c.sq)})
+        if (q) (void)hipFree(q);
+}
+
+// ---- the parameter entry points (`core` null: a null learner) ---------------
+
+inline int learner_params_ok(const char *who, const LearnerCore *core, const void *flat,
+                             int64_t n, const char *got) {
+    if (!flat) return fail(CE_EINVAL, std::string(who) + ": null parameter vector");
+    if (!core) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    if (n != core->plan.n_params)
+        return fail(CE_EINVAL, std::string(who) + got + std::to_string(n) +
+                                   " parameters, the policy has " + std::to_string(core->plan.n_params));
+    return CE_OK;
+}
+
+// `flat` into the master parameters and through to the policy's image.
+inline int learner_set_params(const char *who, LearnerCore *core, const float *flat, int64_t n,
+                              uint32_t flags, void *hip_stream) {
+    const int rc = learner_params_ok(who, core, flat, n, ": got ");
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    CE_HIP(hipMemcpyAsync(core->params, flat, n * sizeof(float),
+                          dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));   // `flat` may be pageable
+    policy_repack(core->policy, core->params, stream);
+    CE_HIP(hipGetLastError());
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));
+    return CE_OK;
+}
+
+inline int learner_get_params(const char *who, LearnerCore *core, float *flat, int64_t n,
+                              uint32_t flags, void *hip_stream) {
+    const int rc = learner_params_ok(who, core, flat, n, ": got room for ");
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    CE_HIP(hipMemcpyAsync(flat, core->params, n * sizeof(float),
+                          dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    policy_repack(core->policy, core->params, stream);
+    CE_HIP(hipGetLastError());
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));
+    return CE_OK;
+}
+
+// ---- argument checks --------------------------------------------------------
+
+// n rows gathered by idx (null: the first n) out of an m-row batch
+inline int learner_rows_ok(const char *who, int64_t n, int64_t m, const int32_t *idx) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (n < 1) return bad(": n must be at least 1, got " + std::to_string(n));
+    if (m < 1 || m > kLearnerMaxRows)
+        return bad(": m must be in [1, 2^24], got " + std::to_string(m));
+    if (n > kLearnerMaxRows) return bad(": n must be at most 2^24");
+    if (!idx && n > m) return bad(": n exceeds m and there is no idx to gather by");
+    return CE_OK;
+}
+
+// the record stride of a [k][rows] float view (`name`: "reward", "value")
+inline int learner_stride_ok(const char *who, const char *name, int64_t stride_bytes,
+                             int64_t rows) {
+    if (stride_bytes < rows * 4 || stride_bytes % 4 != 0)
+        return fail(CE_EINVAL, std::string(who) + ": " + name + "_stride_bytes must be a multiple "
+                                   "of 4 of at least rows * 4");
+    return CE_OK;
+}
+
+// k, rows and the reward / done records of a rollout (`cap_total`: k * rows
+// is bounded as a batch's rows are, for a gradient over all of them)
+inline int learner_records_ok(const char *who, int32_t k, int64_t rows, const float *rewards,
+                              int64_t reward_stride_bytes, const uint8_t *dones,
+                              int64_t done_stride_bytes, const float *last_values,
+                              bool cap_total) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (k < 1) return bad(": k must be at least 1, got " + std::to_string(k));
+    if (rows < 1 || rows > kLearnerMaxRows)
+        return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
+    if (cap_total && int64_t(k) * rows > kLearnerMaxRows)
+        return bad(": k * rows must be at most 2^24, got " + std::to_string(int64_t(k) * rows));
+    if (!rewards) return bad(": null rewards");
+    if (!dones) return bad(": null dones");
+    if (!last_values) return bad(": null last_values");
+    const int rc = learner_stride_ok(who, "reward", reward_stride_bytes, rows);
+    if (rc != CE_OK) return rc;
+    if (done_stride_bytes < rows) return bad(": done_stride_bytes must be at least rows");
+    if (reinterpret_cast<uintptr_t>(rewards) & 3) return bad(": rewards must be 4-byte aligned");
+    return CE_OK;
+}
+
+// ---- the launches around a gradient kernel ----------------------------------
+
+// The fields of a gradient kernel's arguments every learner sets alike
+// (Ppo2GradArgs names them); the loss head's own are the caller's.
+template <class Args>
+void learner_fill_grad_args(Args &g, const LearnerCore &c, float vf_coef, int64_t n, int64_t m,
+                            const int32_t *idx, const float *obs) {
+    g.p = c.plan;
+    g.n = static_cast<int>(n);
+    g.m = static_cast<int>(m);
+    g.tiles = static_cast<int>((n + kPpoTile - 1) / kPpoTile);
+    g.grid = std::min(g.tiles, c.grid_max);
+    g.img_floats = c.plan.img_floats;
+    g.w_floats = c.w_floats;
+    g.act_floats = c.act_floats;
+    g.vf_coef = vf_coef;
+    g.idx = idx;
+    g.obs = obs;
+    g.slab = c.slab;
+    g.stat_slab = c.stat_slab;
+}
+
+// [reduce, finish] after a gradient kernel of `grid` workgroups per network
+// over n rows: the slab into grad, the statistics and |grad|^2 into stats.
+template <void (*Finish)(Ppo2FinishArgs)>
+void learner_enqueue_reduce_finish(const LearnerCore &c, int n, int grid, float ent_coef,
+                                   float vf_coef, float *grad, float *stats,
+                                   hipStream_t stream) {
+    Ppo2ReduceArgs q{};
+    q.p = c.plan;
+    q.grid = grid;
+    q.ent_coef = ent_coef;
+    q.slab = c.slab;
+    q.grad = grad;
+    q.sq = c.sq;
+    ppo2_launch_reduce(q, stream);
+    Ppo2FinishArgs f{};
+    f.n = n;
+    f.grid = grid;
+    f.n_sq = c.n_sq;
+    f.A = c.plan.A;
+    f.off_logstd = c.plan.off_logstd;
+    f.ent_coef = ent_coef;
+    f.vf_coef = vf_coef;
+    f.img = c.plan.img;
+    f.stat_slab = c.stat_slab;
+    f.sq = c.sq;
+    f.stats = stats;
+    hipLaunchKernelGGL(Finish, dim3(1), dim3(256), 0, stream, f);
+}
+
+}  // namespace ce

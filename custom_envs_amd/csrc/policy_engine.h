@@ -26,8 +26,8 @@ int policy_rollout_args_ok(const char *who, const ce_policy *p, int engine_obs_d
                            int64_t out_step_bytes, const ce_policy_outputs *pout,
                            int64_t pout_step_bytes);
 
-// What the PPO2 learner (ppo2_engine.hip, ppo2_kernels.h) needs of a policy,
-// as plain data: its shape, the offsets of its padded parameter image (every
+// What the learners (learner_host.h and its two users, ppo_grad_tile.h) need
+// of a policy, as plain data: its shape, the offsets of its padded parameter image (every
 // W zero-padded to [in_pad][out_pad], policy_engine.hip: plan), the segments
 // that map the flat parameter vector into the image, and the image itself.
 constexpr int kPlanLayers = 4;                  // hidden layers + the head

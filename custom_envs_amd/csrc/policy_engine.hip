@@ -234,13 +234,6 @@ int ce_policy_create(const ce_policy_config *cfg, ce_policy **out) {
         ce_policy_destroy(p);
         return code;
     };
-#define CE_TRY(call)                                                           \
-    do {                                                                       \
-        hipError_t err_ = (call);                                              \
-        if (err_ != hipSuccess)                                                \
-            return bail(fail(CE_EHIP, std::string(#call " failed: ") +         \
-                                          hipGetErrorString(err_)));           \
-    } while (0)
     CE_TRY(hipSetDevice(cfg->device));
     CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -255,7 +248,6 @@ int ce_policy_create(const ce_policy_config *cfg, ce_policy **out) {
         init[p->args.off_high + c] = INFINITY;
     }
     CE_TRY(hipMemcpy(p->img, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
-#undef CE_TRY
     p->args.img = p->img;
     *out = p;
     return CE_OK;

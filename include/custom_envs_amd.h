@@ -470,7 +470,8 @@ int ce_multi_rollout_policy(ce_multi_engine *eng, const ce_policy *p, int32_t k,
  * The PPO2 learner on the device (stable-baselines 2.x PPO2 over the policy
  * above; custom_envs_amd/ppo2.py states the semantics in NumPy): GAE, the
  * loss gradient, a global-norm clip, TF-style Adam and the repack of the
- * policy's image (ppo2_kernels.h).  The learner owns the master flat
+ * policy's image (ppo2_kernels.h; the host side both learners share is
+ * csrc/learner_host.h).  The learner owns the master flat
  * parameters, Adam's m and v, the step count and the partial slab on the
  * policy's device.  ce_ppo2_gae / _grad / _step are stream-ordered on the
  * caller's stream and never synchronise; results are bit-identical run after
@@ -566,7 +567,8 @@ typedef struct ce_a2c_config {
 /* The policy must outlive the learner.  The master parameters start as zeros. */
 int ce_a2c_create(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out);
 void ce_a2c_destroy(ce_a2c *l);
-/* As ce_ppo2_set_params / _get_params; ms and mom are kept. */
+/* As ce_ppo2_set_params / _get_params (one body, csrc/learner_host.h); ms and
+ * mom are kept. */
 int ce_a2c_set_params(ce_a2c *l, const float *flat, int64_t n, uint32_t flags, void *hip_stream);
 int ce_a2c_get_params(ce_a2c *l, float *flat, int64_t n, uint32_t flags, void *hip_stream);
 /* ret [k][rows] contiguous float32 from rewards (float32) and dones (uint8)

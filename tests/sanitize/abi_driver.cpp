@@ -30,6 +30,155 @@ template <typename T> static void dump(const char *tag, const std::vector<T> &v)
     std::printf("\n");
 }
 
+// The argument checks of ce_ppo2_* and ce_a2c_* with a NULL handle: one defect
+// per call (the lists of tests/test_ppo2_host.py and tests/test_a2c_host.py),
+// each refused with a message that names it, and the all-valid call refused
+// for the handle alone, last.
+#define REFUSED(call, word)                                                   \
+    EXPECT((call) == CE_EINVAL && std::strstr(ce_last_error(), word) != nullptr)
+
+static void learner_checks() {
+    std::vector<float> buf(64, 0.0f);
+    float *a = buf.data();
+    const uint8_t *d = reinterpret_cast<const uint8_t *>(a);
+    const int32_t *ix = reinterpret_cast<const int32_t *>(a);
+    const float *odd = reinterpret_cast<const float *>(reinterpret_cast<const char *>(a) + 2);
+    const int64_t big = int64_t(1) << 24;
+
+    // ---- create / destroy / parameters
+    ce_ppo2_config pc{0.99f, 0.95f, 0.2f, 0.2f, 0.01f, 0.5f, 0.5f, 2.5e-4f, 0.9f, 0.999f, 1e-5f, 1, 0};
+    ce_ppo2 *pl = nullptr;
+    REFUSED(ce_ppo2_create(nullptr, &pc, &pl), "null policy");
+    REFUSED(ce_ppo2_create(nullptr, nullptr, &pl), "null config");
+    REFUSED(ce_ppo2_create(nullptr, &pc, nullptr), "null output");
+    ce_ppo2_config pbad = pc;
+    pbad.gamma = 1.5f;
+    REFUSED(ce_ppo2_create(nullptr, &pbad, &pl), "gamma");
+    pbad = pc;
+    pbad.beta1 = 1.0f;
+    REFUSED(ce_ppo2_create(nullptr, &pbad, &pl), "beta1");
+    pbad = pc;
+    pbad.grid_limit = -1;
+    REFUSED(ce_ppo2_create(nullptr, &pbad, &pl), "grid_limit");
+    EXPECT(pl == nullptr);
+    ce_ppo2_destroy(nullptr);
+    ce_a2c_config ac{0.99f, 0.01f, 0.25f, 0.5f, 7e-4f, 0.99f, 1e-5f, 0.0f, 0};
+    ce_a2c *al = nullptr;
+    REFUSED(ce_a2c_create(nullptr, &ac, &al), "null policy");
+    REFUSED(ce_a2c_create(nullptr, nullptr, &al), "null config");
+    REFUSED(ce_a2c_create(nullptr, &ac, nullptr), "null output");
+    ce_a2c_config abad = ac;
+    abad.alpha = 1.0f;
+    REFUSED(ce_a2c_create(nullptr, &abad, &al), "alpha");
+    abad = ac;
+    abad.momentum = -0.5f;
+    REFUSED(ce_a2c_create(nullptr, &abad, &al), "momentum");
+    EXPECT(al == nullptr);
+    ce_a2c_destroy(nullptr);
+    REFUSED(ce_ppo2_set_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_ppo2_set_params(nullptr, a, 8, 0, nullptr), "null learner");
+    REFUSED(ce_ppo2_get_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_ppo2_get_params(nullptr, a, 8, 0, nullptr), "null learner");
+    REFUSED(ce_a2c_set_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_a2c_set_params(nullptr, a, 8, 0, nullptr), "null learner");
+    REFUSED(ce_a2c_get_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_a2c_get_params(nullptr, a, 8, 0, nullptr), "null learner");
+
+    // ---- ce_ppo2_gae(l, k, rows, rewards, rs, dones, ds, values, vs, last, adv, ret, stream)
+    REFUSED(ce_ppo2_gae(nullptr, 0, 4, a, 16, d, 4, a, 16, a, a, a, nullptr), "k must");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 0, a, 16, d, 4, a, 16, a, a, a, nullptr), "rows must");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, nullptr, 16, d, 4, a, 16, a, a, a, nullptr), "null rewards");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, nullptr, 4, a, 16, a, a, a, nullptr), "null dones");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, nullptr, 16, a, a, a, nullptr), "null values");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, a, 16, nullptr, a, a, nullptr), "null last_values");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, a, 16, a, nullptr, a, nullptr), "null adv");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, a, 16, a, a, nullptr, nullptr), "null adv or ret");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 18, d, 4, a, 16, a, a, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 8, d, 4, a, 16, a, a, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, a, 17, a, a, a, nullptr), "value_stride_bytes");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 3, a, 16, a, a, a, nullptr), "done_stride_bytes");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, odd, 16, d, 4, a, 16, a, a, a, nullptr), "4-byte aligned");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, odd, 16, a, a, a, nullptr), "4-byte aligned");
+    REFUSED(ce_ppo2_gae(nullptr, 2, 4, a, 16, d, 4, a, 16, a, a, a, nullptr), "null learner");
+    // k * rows past 2^24 is A2C's bound only
+    REFUSED(ce_ppo2_gae(nullptr, 2, big, a, 4 * big, d, big, a, 4 * big, a, a, a, nullptr), "null learner");
+
+    // ---- ce_ppo2_grad / _step(l, n, m, idx, obs, actions, adv, ret, old_neglogp, old_values, ...)
+    REFUSED(ce_ppo2_grad(nullptr, 0, 4, nullptr, a, a, a, a, a, a, -1.0f, a, a, nullptr), "n must");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 0, nullptr, a, a, a, a, a, a, -1.0f, a, a, nullptr), "m must");
+    REFUSED(ce_ppo2_grad(nullptr, 4, big + 1, nullptr, a, a, a, a, a, a, -1.0f, a, a, nullptr), "m must");
+    REFUSED(ce_ppo2_grad(nullptr, big + 1, 4, ix, a, a, a, a, a, a, -1.0f, a, a, nullptr), "n must");
+    REFUSED(ce_ppo2_grad(nullptr, 5, 4, nullptr, a, a, a, a, a, a, -1.0f, a, a, nullptr), "no idx");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, nullptr, a, a, a, a, a, -1.0f, a, a, nullptr), "null obs");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, nullptr, a, a, a, a, -1.0f, a, a, nullptr), "null actions");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, nullptr, a, a, a, -1.0f, a, a, nullptr), "null advantages");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, nullptr, a, a, -1.0f, a, a, nullptr), "null returns");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, a, nullptr, a, -1.0f, a, a, nullptr), "null old_neglogp");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, nullptr, -1.0f, a, a, nullptr), "null old_values");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, a, -1.0f, a, nullptr, nullptr), "null stats");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, a, -1.0f, nullptr, a, nullptr), "null grad");
+    REFUSED(ce_ppo2_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, a, -1.0f, a, a, nullptr), "null learner");
+    REFUSED(ce_ppo2_grad(nullptr, 8, 4, ix, a, a, a, a, a, a, -1.0f, a, a, nullptr), "null learner");
+    REFUSED(ce_ppo2_step(nullptr, 0, 4, nullptr, a, a, a, a, a, a, -1.0f, -1.0f, a, nullptr), "n must");
+    REFUSED(ce_ppo2_step(nullptr, 5, 4, nullptr, a, a, a, a, a, a, -1.0f, -1.0f, a, nullptr), "no idx");
+    REFUSED(ce_ppo2_step(nullptr, 4, 4, nullptr, a, a, a, a, nullptr, a, -1.0f, -1.0f, a, nullptr), "null old_neglogp");
+    REFUSED(ce_ppo2_step(nullptr, 4, 4, nullptr, a, a, a, a, a, a, -1.0f, -1.0f, nullptr, nullptr), "null stats");
+    REFUSED(ce_ppo2_step(nullptr, 4, 4, nullptr, a, a, a, a, a, a, -1.0f, -1.0f, a, nullptr), "null learner");
+
+    // ---- ce_a2c_returns(l, k, rows, rewards, rs, dones, ds, last, ret, stream)
+    REFUSED(ce_a2c_returns(nullptr, 0, 4, a, 16, d, 4, a, a, nullptr), "k must");
+    REFUSED(ce_a2c_returns(nullptr, 2, 0, a, 16, d, 4, a, a, nullptr), "rows must");
+    REFUSED(ce_a2c_returns(nullptr, 2, big, a, 4 * big, d, big, a, a, nullptr), "k * rows");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, nullptr, 16, d, 4, a, a, nullptr), "null rewards");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 16, nullptr, 4, a, a, nullptr), "null dones");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 16, d, 4, nullptr, a, nullptr), "null last_values");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 16, d, 4, a, nullptr, nullptr), "null ret");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 18, d, 4, a, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 8, d, 4, a, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 16, d, 3, a, a, nullptr), "done_stride_bytes");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, odd, 16, d, 4, a, a, nullptr), "4-byte aligned");
+    REFUSED(ce_a2c_returns(nullptr, 2, 4, a, 16, d, 4, a, a, nullptr), "null learner");
+
+    // ---- ce_a2c_grad / _step(l, n, m, idx, obs, actions, returns, old_values, ...)
+    REFUSED(ce_a2c_grad(nullptr, 0, 4, nullptr, a, a, a, a, a, a, nullptr), "n must");
+    REFUSED(ce_a2c_grad(nullptr, 4, 0, nullptr, a, a, a, a, a, a, nullptr), "m must");
+    REFUSED(ce_a2c_grad(nullptr, 4, big + 1, nullptr, a, a, a, a, a, a, nullptr), "m must");
+    REFUSED(ce_a2c_grad(nullptr, 5, 4, nullptr, a, a, a, a, a, a, nullptr), "no idx");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, nullptr, a, a, a, a, a, nullptr), "null obs");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, nullptr, a, a, a, a, nullptr), "null actions");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, a, nullptr, a, a, a, nullptr), "null returns");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, a, a, nullptr, a, a, nullptr), "null old_values");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, nullptr, nullptr), "null stats");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, a, a, a, nullptr, a, nullptr), "null grad");
+    REFUSED(ce_a2c_grad(nullptr, 4, 4, nullptr, a, a, a, a, a, a, nullptr), "null learner");
+    REFUSED(ce_a2c_grad(nullptr, 8, 4, ix, a, a, a, a, a, a, nullptr), "null learner");
+    REFUSED(ce_a2c_step(nullptr, 0, 4, nullptr, a, a, a, a, -1.0f, a, nullptr), "n must");
+    REFUSED(ce_a2c_step(nullptr, 5, 4, nullptr, a, a, a, a, -1.0f, a, nullptr), "no idx");
+    REFUSED(ce_a2c_step(nullptr, 4, 4, nullptr, a, a, nullptr, a, -1.0f, a, nullptr), "null returns");
+    REFUSED(ce_a2c_step(nullptr, 4, 4, nullptr, a, a, a, a, -1.0f, nullptr, nullptr), "null stats");
+    REFUSED(ce_a2c_step(nullptr, 4, 4, nullptr, a, a, a, a, -1.0f, a, nullptr), "null learner");
+
+    // ---- ce_a2c_update(l, k, rows, obs, actions, as, values, vs, rewards, rs, dones, ds, last, lr, stats, stream)
+    REFUSED(ce_a2c_update(nullptr, 0, 4, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "k must");
+    REFUSED(ce_a2c_update(nullptr, 2, 0, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "rows must");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, nullptr, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null obs");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, nullptr, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null actions");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, nullptr, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null values");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, nullptr, 16, d, 4, a, -1.0f, a, nullptr), "null rewards");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, nullptr, 4, a, -1.0f, a, nullptr), "null dones");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 4, nullptr, -1.0f, a, nullptr), "null last_values");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, nullptr, nullptr), "null stats");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 8, d, 4, a, -1.0f, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 18, d, 4, a, -1.0f, a, nullptr), "reward_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 12, a, 16, d, 4, a, -1.0f, a, nullptr), "value_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 17, a, 16, d, 4, a, -1.0f, a, nullptr), "value_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 8, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "action_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 34, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "action_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 3, a, -1.0f, a, nullptr), "done_stride_bytes");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, odd, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "4-byte aligned");
+    REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null learner");
+}
+
 int main() {
     EXPECT(ce_abi_version() == CE_ABI_VERSION);
     // ---- host-only draws: edge seeds and shapes
@@ -131,6 +280,7 @@ int main() {
     ce_multi_destroy(nullptr);
     EXPECT(ce_nn_create(nullptr, nullptr, nullptr, nullptr) == CE_EINVAL);
     ce_nn_destroy(nullptr);
+    learner_checks();
     std::printf("failures %d\n", failures);
     return failures ? 1 : 0;
 }
