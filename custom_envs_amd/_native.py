@@ -49,6 +49,8 @@ EXPORTS = (
     'ce_ppo2_gae', 'ce_ppo2_grad', 'ce_ppo2_step',
     'ce_a2c_create', 'ce_a2c_destroy', 'ce_a2c_set_params', 'ce_a2c_get_params',
     'ce_a2c_returns', 'ce_a2c_grad', 'ce_a2c_step', 'ce_a2c_update',
+    'ce_learner_record_bytes', 'ce_ppo2_adv_moments', 'ce_ppo2_partial', 'ce_ppo2_combine',
+    'ce_ppo2_apply', 'ce_a2c_partial', 'ce_a2c_update_partial', 'ce_a2c_combine', 'ce_a2c_apply',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -217,6 +219,17 @@ def _declare(lib):
         'ce_a2c_step': ([vp, i64, i64, vp, vp, vp, vp, vp, f32, vp, vp], ctypes.c_int),
         'ce_a2c_update': ([vp, i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, vp, vp],
                           ctypes.c_int),
+        'ce_learner_record_bytes': ([vp], ctypes.c_int64),
+        'ce_ppo2_adv_moments': ([vp, i64, i64, vp, vp, vp, vp], ctypes.c_int),
+        'ce_ppo2_partial': ([vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp],
+                            ctypes.c_int),
+        'ce_ppo2_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_ppo2_apply': ([vp, i32, vp, i64, f32, vp, vp], ctypes.c_int),
+        'ce_a2c_partial': ([vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_a2c_update_partial': ([vp, i32, i64, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
+                                   vp], ctypes.c_int),
+        'ce_a2c_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_a2c_apply': ([vp, i32, vp, i64, f32, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -30,8 +30,11 @@ One learner per policy: a second learner (of either algorithm) on the same
 policy would overwrite the image from its own master copy.
 
 Out of scope: DDPG, ``MlpLstmPolicy``, ``explained_variance``, SB's
-``Scheduler`` class (pass ``lr=`` per call instead) and multi-GPU gradient
-exchange.
+``Scheduler`` class (pass ``lr=`` per call instead).
+
+On several GPUs a ``distributed.GradientExchange`` attached to the learner
+turns ``grad`` / ``step`` / ``update`` into the step on every rank's rows
+(``partial`` / ``update_partial``, one in-place all-gather, ``apply``).
 """
 from collections import namedtuple
 
@@ -145,6 +148,7 @@ class A2CLearner(Learner):
     PREFIX = 'ce_a2c'
     CONFIG = CeA2cConfig
     BATCH_FIELDS = BATCH_FIELDS
+    STATS = Stats
     _loss_grad = staticmethod(loss_grad_numpy)
 
     def __init__(self, policy, gamma=0.99, ent_coef=0.01, vf_coef=0.25, max_grad_norm=0.5,
@@ -179,16 +183,66 @@ class A2CLearner(Learner):
         """The loss gradient of the rows ``idx`` (None: all) of ``batch``, no
         update.  Returns (grad ``[n_params]`` device tensor, ``Stats``)."""
         import torch
+        if self.exchange is not None:      # the gradient of every rank's rows
+            records, n_total = self._exchange_records(batch, idx, stream)
+            return self.combine(records, n_total, stream=stream)
         head, stats = self._head(batch, idx)
         grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
         self._call('grad', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
         return grad, Stats(stats)
 
+    # ------------------------------------------------------- gradient exchange
+    def partial(self, batch, idx=None, n_total=None, out=None, stream=None):
+        """This rank's share of a step of ``n_total`` rows (None: its own
+        ``n``): the gradient of the rows ``idx`` with the row weight ``1 /
+        n_total`` as one float64 record in ``out`` (``[record_doubles]``;
+        None: a new tensor).  Returns the record."""
+        n_total = self.check_total(self._rows_of(batch, idx), n_total)
+        if out is not None:
+            self.check_record_tensor('out', out, (self.record_doubles,))
+        M, N = self.check_batch(batch, idx)
+        out = self._record_out(out, batch['obs'])
+        ptrs = [batch[n].data_ptr() for n in self.BATCH_FIELDS]
+        self._call('partial', self._h, N, n_total, M, None if idx is None else idx.data_ptr(),
+                   *ptrs, out.data_ptr(), self._stream(stream))
+        return out
+
+    def update_partial(self, result, n_total=None, out=None, stream=None):
+        """``partial`` on a ``collect`` result's records in place: the returns
+        scan and the gradient of ``update`` with the row weight ``1 /
+        n_total`` (``K`` times every rank's rows).  Returns the record."""
+        rewards = result.get('rewards')
+        k, rows = self.rollout_shape(rewards) if rewards is not None else (0, 0)
+        n_total = self.check_total(k * rows, n_total)
+        if out is not None:
+            self.check_record_tensor('out', out, (self.record_doubles,))
+        k, rows = self.check_result(result)
+        out = self._record_out(out, result['obs'])
+        sb = self._stride_bytes
+        self._call(
+            'update_partial', self._h, k, rows, n_total, result['obs'].data_ptr(),
+            result['actions'].data_ptr(), sb(result['actions']), result['values'].data_ptr(),
+            sb(result['values']), result['rewards'].data_ptr(), sb(result['rewards']),
+            result['dones'].data_ptr(), sb(result['dones']), result['last_values'].data_ptr(),
+            out.data_ptr(), self._stream(stream))
+        return out
+
+    def _exchange_records(self, batch, idx, stream):
+        """partial, the gather: (the gathered records, n_total)."""
+        ex = self.exchange
+        n_total = ex.total_rows(self._rows_of(batch, idx))
+        self.partial(batch, idx, n_total=n_total, out=ex.records[ex.rank], stream=stream)
+        return ex.gather_records(), n_total
+
     def step(self, batch, idx=None, stream=None, lr=None):
         """Gradient, global-norm clip, RMSProp and the policy image's repack
         as one stream-ordered call.  ``lr`` overrides the learner's for this
         call (a learning-rate schedule is the caller's ``lr=`` per call).
-        Returns ``Stats``."""
+        Returns ``Stats``.  With a gradient exchange attached it is the step
+        on every rank's rows: partial, gather, apply."""
+        if self.exchange is not None:
+            records, n_total = self._exchange_records(batch, idx, stream)
+            return self.apply(records, n_total, lr=lr, stream=stream)
         head, stats = self._head(batch, idx)
         self._call('step', *head, -1.0 if lr is None else lr, stats.data_ptr(),
                    self._stream(stream))
@@ -231,8 +285,18 @@ class A2CLearner(Learner):
         the gradient over the records in place, reduce, finish, RMSProp and
         the policy image's repack (six launches; no copy, no allocation once
         the returns buffer has its size, no synchronisation).  Returns
-        ``Stats``."""
+        ``Stats``.  With a gradient exchange attached: ``update_partial`` with
+        ``n_total = K`` times every rank's rows, the gather, ``apply``."""
         import torch
+        if self.exchange is not None:
+            ex = self.exchange
+            if result.get('rewards') is None:
+                raise ValueError("result lacks 'rewards'")
+            k, rows = self.rollout_shape(result['rewards'])
+            ex.check_rows(rows)
+            n_total = k * sum(ex.counts)
+            self.update_partial(result, n_total=n_total, out=ex.records[ex.rank], stream=stream)
+            return self.apply(ex.gather_records(), n_total, lr=lr, stream=stream)
         k, rows = self.check_result(result)
         stats = torch.empty(N_STATS, dtype=torch.float32, device=result['obs'].device)
         sb = self._stride_bytes

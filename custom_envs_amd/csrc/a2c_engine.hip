@@ -3,7 +3,10 @@
 // ce_a2c_update on top of the shell both learners share (learner_host.h), and
 // the launches [gradient, reduce, finish, RMSProp, repack] -- ce_a2c_update:
 // the returns scan first, the gradient on the rollout records in place -- on
-// the caller's stream.  Every argument check precedes the first HIP call, and
+// the caller's stream; under a gradient exchange (learner_host.h) the list
+// splits into ce_a2c_partial / ce_a2c_update_partial [(returns,) gradient,
+// partial reduce] and ce_a2c_apply [combine, finish, RMSProp, repack] around
+// the caller's all-gather.  Every argument check precedes the first HIP call, and
 // the checks of the plain arguments precede the check of the handle, so they
 // run without a device.
 #include <hip/hip_runtime.h>
@@ -69,15 +72,15 @@ void enqueue_returns(const ce_a2c *l, int32_t k, int64_t rows, const float *rewa
                        static_cast<long long>(done_stride_bytes), last_values, l->cfg.gamma, ret);
 }
 
-// [gradient, reduce, finish] into grad / stats.  Row s of the m-row batch is
-// row s % rec_rows of record s / rec_rows of actions / old_values.
-void enqueue_grad(const ce_a2c *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
-                  const float *actions, int64_t action_stride, const float *ret,
-                  const float *old_values, int64_t value_stride, int64_t rec_rows, float *grad,
-                  float *stats, hipStream_t stream) {
-    const ce_a2c_config &c = l->cfg;
+// [gradient] of n rows weighted 1 / n_total into the slab; returns the grid.
+// Row s of the m-row batch is row s % rec_rows of record s / rec_rows of
+// actions / old_values.
+int enqueue_grad_kernel(const ce_a2c *l, int64_t n, int64_t n_total, int64_t m,
+                        const int32_t *idx, const float *obs, const float *actions,
+                        int64_t action_stride, const float *ret, const float *old_values,
+                        int64_t value_stride, int64_t rec_rows, hipStream_t stream) {
     ce::A2cGradArgs g{};
-    ce::learner_fill_grad_args(g, l->core, c.vf_coef, n, m, idx, obs);
+    ce::learner_fill_grad_args(g, l->core, l->cfg.vf_coef, n, n_total, m, idx, obs);
     g.rec_rows = static_cast<int>(rec_rows);
     g.action_stride = action_stride;
     g.value_stride = value_stride;
@@ -86,8 +89,58 @@ void enqueue_grad(const ce_a2c *l, int64_t n, int64_t m, const int32_t *idx, con
     g.old_values = old_values;
     hipLaunchKernelGGL(ce::a2c_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
                        l->core.lds_bytes, stream, g);
-    ce::learner_enqueue_reduce_finish<ce::a2c_finish_kernel>(l->core, g.n, g.grid, c.ent_coef,
-                                                             c.vf_coef, grad, stats, stream);
+    return g.grid;
+}
+
+// [gradient, reduce, finish] into grad / stats
+void enqueue_grad(const ce_a2c *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
+                  const float *actions, int64_t action_stride, const float *ret,
+                  const float *old_values, int64_t value_stride, int64_t rec_rows, float *grad,
+                  float *stats, hipStream_t stream) {
+    const int grid = enqueue_grad_kernel(l, n, n, m, idx, obs, actions, action_stride, ret,
+                                         old_values, value_stride, rec_rows, stream);
+    ce::learner_enqueue_reduce_finish<ce::a2c_finish_kernel>(l->core, static_cast<int>(n), grid,
+                                                             l->cfg.ent_coef, l->cfg.vf_coef, grad,
+                                                             stats, stream);
+}
+
+// The checks of ce_a2c_update and ce_a2c_update_partial but the handle's, and
+// then the handle's own (the action stride against act_dim).
+int update_ok(const char *who, const ce_a2c *l, int32_t k, int64_t rows, const float *obs,
+              const float *actions, int64_t action_stride_bytes, const float *values,
+              int64_t value_stride_bytes, const float *rewards, int64_t reward_stride_bytes,
+              const uint8_t *dones, int64_t done_stride_bytes, const float *last_values,
+              const void *out, const char *out_name) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    int rc = ce::learner_records_ok(who, k, rows, rewards, reward_stride_bytes, dones,
+                                    done_stride_bytes, last_values, true);
+    if (rc != CE_OK) return rc;
+    if (!obs) return bad(": null obs");
+    if (!actions) return bad(": null actions");
+    if (!values) return bad(": null values");
+    if (!out) return bad(std::string(": null ") + out_name);
+    if ((rc = ce::learner_stride_ok(who, "value", value_stride_bytes, rows)) != CE_OK) return rc;
+    if (action_stride_bytes < rows * 4 || action_stride_bytes % 4 != 0)
+        return bad(": action_stride_bytes must be a multiple of 4 of at least one record");
+    if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(values)) & 3)
+        return bad(": actions and values must be 4-byte aligned");
+    if (!l) return bad(": null learner");
+    if (action_stride_bytes < rows * l->core.plan.A * 4)
+        return bad(": action_stride_bytes is shorter than one record (rows * act_dim * 4 = " +
+                   std::to_string(rows * l->core.plan.A * 4) + ")");
+    return CE_OK;
+}
+
+// the returns buffer for `total` rows: grows as needed; the steady state
+// allocates nothing
+int reserve_returns(ce_a2c *l, int64_t total) {
+    if (total <= l->ret_cap) return CE_OK;
+    if (l->ret) CE_HIP(hipFree(l->ret));      // waits for the launches that read it
+    l->ret = nullptr;
+    l->ret_cap = 0;
+    CE_HIP(hipMalloc(&l->ret, static_cast<size_t>(total) * sizeof(float)));
+    l->ret_cap = total;
+    return CE_OK;
 }
 
 // [RMSProp, repack] from the core's grad and the |grad|^2 in stats
@@ -199,38 +252,98 @@ int ce_a2c_update(ce_a2c *l, int32_t k, int64_t rows, const float *obs, const fl
                   const float *rewards, int64_t reward_stride_bytes, const uint8_t *dones,
                   int64_t done_stride_bytes, const float *last_values, float lr, float *stats,
                   void *hip_stream) {
-    const char *who = "ce_a2c_update";
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    int rc = ce::learner_records_ok(who, k, rows, rewards, reward_stride_bytes, dones,
-                                    done_stride_bytes, last_values, true);
+    int rc = update_ok("ce_a2c_update", l, k, rows, obs, actions, action_stride_bytes, values,
+                       value_stride_bytes, rewards, reward_stride_bytes, dones, done_stride_bytes,
+                       last_values, stats, "stats");
     if (rc != CE_OK) return rc;
-    if (!obs) return bad(": null obs");
-    if (!actions) return bad(": null actions");
-    if (!values) return bad(": null values");
-    if (!stats) return bad(": null stats");
-    if ((rc = ce::learner_stride_ok(who, "value", value_stride_bytes, rows)) != CE_OK) return rc;
-    if (action_stride_bytes < rows * 4 || action_stride_bytes % 4 != 0)
-        return bad(": action_stride_bytes must be a multiple of 4 of at least one record");
-    if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(values)) & 3)
-        return bad(": actions and values must be 4-byte aligned");
-    if (!l) return bad(": null learner");
-    if (action_stride_bytes < rows * l->core.plan.A * 4)
-        return bad(": action_stride_bytes is shorter than one record (rows * act_dim * 4 = " +
-                   std::to_string(rows * l->core.plan.A * 4) + ")");
     CE_CLEAR_STALE_ERROR();
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int64_t total = int64_t(k) * rows;
-    if (total > l->ret_cap) {    // grows as needed; the steady state allocates nothing
-        if (l->ret) CE_HIP(hipFree(l->ret));      // waits for the launches that read it
-        l->ret = nullptr;
-        l->ret_cap = 0;
-        CE_HIP(hipMalloc(&l->ret, static_cast<size_t>(total) * sizeof(float)));
-        l->ret_cap = total;
-    }
+    if ((rc = reserve_returns(l, total)) != CE_OK) return rc;
     enqueue_returns(l, k, rows, rewards, reward_stride_bytes, dones, done_stride_bytes,
                     last_values, l->ret, stream);
     enqueue_grad(l, total, total, nullptr, obs, actions, action_stride_bytes / 4, l->ret, values,
                  value_stride_bytes / 4, rows, l->core.grad, stats, stream);
+    enqueue_rmsprop(l, lr, stats, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_a2c_partial(ce_a2c *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                   const float *obs, const float *actions, const float *returns,
+                   const float *old_values, double *record, void *hip_stream) {
+    const char *who = "ce_a2c_partial";
+    int rc = ce::learner_rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    if ((rc = ce::learner_partial_ok(who, n, n_total, record)) != CE_OK) return rc;
+    // `record` stands in for stats in the null checks the entry points share
+    rc = batch_ok(who, l, n, m, idx, obs, actions, returns, old_values,
+                  reinterpret_cast<const float *>(record));
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const int grid = enqueue_grad_kernel(l, n, n_total, m, idx, obs, actions, 0, returns,
+                                         old_values, 0, m, stream);
+    ce::learner_enqueue_partial(l->core, static_cast<int>(n), grid, record, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_a2c_update_partial(ce_a2c *l, int32_t k, int64_t rows, int64_t n_total, const float *obs,
+                          const float *actions, int64_t action_stride_bytes, const float *values,
+                          int64_t value_stride_bytes, const float *rewards,
+                          int64_t reward_stride_bytes, const uint8_t *dones,
+                          int64_t done_stride_bytes, const float *last_values, double *record,
+                          void *hip_stream) {
+    const char *who = "ce_a2c_update_partial";
+    int rc = ce::learner_records_ok(who, k, rows, rewards, reward_stride_bytes, dones,
+                                    done_stride_bytes, last_values, true);
+    if (rc != CE_OK) return rc;
+    const int64_t total = int64_t(k) * rows;
+    if ((rc = ce::learner_partial_ok(who, total, n_total, record)) != CE_OK) return rc;
+    rc = update_ok(who, l, k, rows, obs, actions, action_stride_bytes, values, value_stride_bytes,
+                   rewards, reward_stride_bytes, dones, done_stride_bytes, last_values, record,
+                   "record");
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if ((rc = reserve_returns(l, total)) != CE_OK) return rc;
+    enqueue_returns(l, k, rows, rewards, reward_stride_bytes, dones, done_stride_bytes,
+                    last_values, l->ret, stream);
+    const int grid = enqueue_grad_kernel(l, total, n_total, total, nullptr, obs, actions,
+                                         action_stride_bytes / 4, l->ret, values,
+                                         value_stride_bytes / 4, rows, stream);
+    ce::learner_enqueue_partial(l->core, static_cast<int>(total), grid, record, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_a2c_combine(ce_a2c *l, int32_t world, const double *records, int64_t n_total, float *grad,
+                   float *stats, void *hip_stream) {
+    const char *who = "ce_a2c_combine";
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    if (!grad) return fail(CE_EINVAL, std::string(who) + ": null grad");
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    CE_CLEAR_STALE_ERROR();
+    ce::learner_enqueue_combine_finish<ce::a2c_finish_kernel>(
+        l->core, world, records, n_total, l->cfg.ent_coef, l->cfg.vf_coef, grad, stats,
+        static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_a2c_apply(ce_a2c *l, int32_t world, const double *records, int64_t n_total, float lr,
+                 float *stats, void *hip_stream) {
+    const char *who = "ce_a2c_apply";
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    ce::learner_enqueue_combine_finish<ce::a2c_finish_kernel>(
+        l->core, world, records, n_total, l->cfg.ent_coef, l->cfg.vf_coef, l->core.grad, stats,
+        stream);
     enqueue_rmsprop(l, lr, stats, stream);
     CE_HIP(hipGetLastError());
     return CE_OK;

@@ -54,6 +54,7 @@ __global__ __launch_bounds__(256) void a2c_returns_kernel(
 struct A2cGradArgs {
     PolicyPlan p;                    // shape, image offsets and img of the policy
     int n, m;                        // rows of the call; rows idx gathers from (K R in place)
+    int n_total;                     // N of the mean (n unless ranks exchange gradients)
     int tiles, grid;                 // 32-row tiles; workgroups per network
     int img_floats;                  // floats of one partial
     int w_floats, act_floats;        // LDS floats: weight stage, one activation buffer
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void a2c_finish_kernel(const Ppo2FinishArgs f)
     const double gn2 = ppo_block_sum(s, red);
     if (tid < 2 * kPpoRowStats) {
         double t = 0.0;
-        for (int gi = 0; gi < f.grid; ++gi) t += f.stat_slab[gi * 2 * kPpoRowStats + tid];
+        for (int gi = 0; gi < f.grid; ++gi) t += f.stat_slab[static_cast<long long>(gi) * f.stat_stride + tid];
         sums[tid] = t;
     }
     __syncthreads();

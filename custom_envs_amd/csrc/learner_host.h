@@ -11,6 +11,10 @@
 //   destroy   its own buffers, then learner_core_destroy
 //   gradient  learner_fill_grad_args(g, core, ...), its own fields, the launch,
 //             then learner_enqueue_reduce_finish<x_finish_kernel>(...)
+//   exchange  the same launch with the ranks' row count, then
+//             learner_enqueue_partial(...); from the gathered records
+//             learner_enqueue_combine_finish<x_finish_kernel>(...) and its
+//             optimiser ("the gradient exchange" below)
 // Dispatch is static (a kernel that differs is a template parameter); nothing
 // here allocates on a call path, and every argument check precedes the first
 // HIP call.
@@ -178,10 +182,11 @@ inline int learner_records_ok(const char *who, int32_t k, int64_t rows, const fl
 // The fields of a gradient kernel's arguments every learner sets alike
 // (Ppo2GradArgs names them); the loss head's own are the caller's.
 template <class Args>
-void learner_fill_grad_args(Args &g, const LearnerCore &c, float vf_coef, int64_t n, int64_t m,
-                            const int32_t *idx, const float *obs) {
+void learner_fill_grad_args(Args &g, const LearnerCore &c, float vf_coef, int64_t n,
+                            int64_t n_total, int64_t m, const int32_t *idx, const float *obs) {
     g.p = c.plan;
     g.n = static_cast<int>(n);
+    g.n_total = static_cast<int>(n_total);
     g.m = static_cast<int>(m);
     g.tiles = static_cast<int>((n + kPpoTile - 1) / kPpoTile);
     g.grid = std::min(g.tiles, c.grid_max);
@@ -193,6 +198,28 @@ void learner_fill_grad_args(Args &g, const LearnerCore &c, float vf_coef, int64_
     g.obs = obs;
     g.slab = c.slab;
     g.stat_slab = c.stat_slab;
+}
+
+// [finish]: the statistics of n rows from `parts` statistic partials,
+// `stat_stride` doubles apart, and the |grad|^2 blocks in c.sq.
+template <void (*Finish)(Ppo2FinishArgs)>
+void learner_enqueue_finish(const LearnerCore &c, int n, int parts, const double *stat_parts,
+                            int stat_stride, float ent_coef, float vf_coef, float *stats,
+                            hipStream_t stream) {
+    Ppo2FinishArgs f{};
+    f.n = n;
+    f.grid = parts;
+    f.n_sq = c.n_sq;
+    f.A = c.plan.A;
+    f.off_logstd = c.plan.off_logstd;
+    f.stat_stride = stat_stride;
+    f.ent_coef = ent_coef;
+    f.vf_coef = vf_coef;
+    f.img = c.plan.img;
+    f.stat_slab = stat_parts;
+    f.sq = c.sq;
+    f.stats = stats;
+    hipLaunchKernelGGL(Finish, dim3(1), dim3(256), 0, stream, f);
 }
 
 // [reduce, finish] after a gradient kernel of `grid` workgroups per network
@@ -209,19 +236,81 @@ void learner_enqueue_reduce_finish(const LearnerCore &c, int n, int grid, float 
     q.grad = grad;
     q.sq = c.sq;
     ppo2_launch_reduce(q, stream);
-    Ppo2FinishArgs f{};
-    f.n = n;
-    f.grid = grid;
-    f.n_sq = c.n_sq;
-    f.A = c.plan.A;
-    f.off_logstd = c.plan.off_logstd;
-    f.ent_coef = ent_coef;
-    f.vf_coef = vf_coef;
-    f.img = c.plan.img;
-    f.stat_slab = c.stat_slab;
-    f.sq = c.sq;
-    f.stats = stats;
-    hipLaunchKernelGGL(Finish, dim3(1), dim3(256), 0, stream, f);
+    learner_enqueue_finish<Finish>(c, n, grid, c.stat_slab, 2 * kPpoRowStats, ent_coef, vf_coef,
+                                   stats, stream);
+}
+
+// ---- the gradient exchange ---------------------------------------------------
+// W ranks, rank r with n_r rows, take the single learner's step on all N =
+// sum n_r rows.  Each rank runs
+//   partial   [its moments' merge (PPO2), gradient kernel with N, partial
+//             reduce]: its record (ppo_grad_tile.h) into slot r of a
+//             [W][record] buffer
+// the caller all-gathers the buffer in place, and each rank runs
+//   apply     [combine, finish, optimiser, repack] from the W records
+// Every rank adds the same float64 values in rank order, so every rank gets
+// the same bits; at W = 1 they are the bits of [gradient, reduce, finish].
+
+constexpr int64_t kLearnerMaxTotalRows = int64_t(1) << 30;
+constexpr int kLearnerMaxWorld = 1 << 16;
+
+// n_total and the record of a partial call (after learner_rows_ok)
+inline int learner_partial_ok(const char *who, int64_t n, int64_t n_total, const void *record) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (n_total < n || n_total > kLearnerMaxTotalRows)
+        return bad(": n_total must be in [n, 2^30], got " + std::to_string(n_total) + " for n = " +
+                   std::to_string(n));
+    if (!record) return bad(": null record");
+    if (reinterpret_cast<uintptr_t>(record) & 7) return bad(": the record must be 8-byte aligned");
+    return CE_OK;
+}
+
+// world, the gathered records, n_total and stats of an apply / combine call
+inline int learner_apply_ok(const char *who, int32_t world, const void *records, int64_t n_total,
+                            const void *stats) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (world < 1 || world > kLearnerMaxWorld)
+        return bad(": world must be in [1, 2^16], got " + std::to_string(world));
+    if (n_total < 1 || n_total > kLearnerMaxTotalRows)
+        return bad(": n_total must be in [1, 2^30], got " + std::to_string(n_total));
+    if (!records) return bad(": null records");
+    if (reinterpret_cast<uintptr_t>(records) & 7) return bad(": the records must be 8-byte aligned");
+    if (!stats) return bad(": null stats");
+    return CE_OK;
+}
+
+// [partial reduce] after a gradient kernel of `grid` workgroups per network
+// over this rank's n rows: the slab and the statistic sums into `record`.
+inline void learner_enqueue_partial(const LearnerCore &c, int n, int grid, double *record,
+                                    hipStream_t stream) {
+    Ppo2PartialArgs q{};
+    q.p = c.plan;
+    q.grid = grid;
+    q.n = n;
+    q.slab = c.slab;
+    q.stat_slab = c.stat_slab;
+    q.record = record;
+    ppo2_launch_partial(q, stream);
+}
+
+// [combine, finish] from the gathered records: grad, and the statistics of
+// all n_total rows into stats.
+template <void (*Finish)(Ppo2FinishArgs)>
+void learner_enqueue_combine_finish(const LearnerCore &c, int world, const double *records,
+                                    int64_t n_total, float ent_coef, float vf_coef, float *grad,
+                                    float *stats, hipStream_t stream) {
+    Ppo2CombineArgs q{};
+    q.n_params = c.plan.n_params;
+    q.off_logstd_flat = c.plan.seg_src[c.plan.n_segs - 1];
+    q.world = world;
+    q.record_doubles = ppo_record_doubles(c.plan.n_params);
+    q.ent_coef = ent_coef;
+    q.records = records;
+    q.grad = grad;
+    q.sq = c.sq;
+    ppo2_launch_combine(q, stream);
+    learner_enqueue_finish<Finish>(c, static_cast<int>(n_total), world, records + c.plan.n_params,
+                                   q.record_doubles, ent_coef, vf_coef, stats, stream);
 }
 
 }  // namespace ce

@@ -2,7 +2,10 @@
 // include/custom_envs_amd.h): Adam's moments, the step count and the advantage
 // statistics on top of the shell both learners share (learner_host.h), and
 // the launches [advantage statistics, gradient, reduce, finish, Adam, repack]
-// on the caller's stream.  Every argument check precedes the first HIP call,
+// on the caller's stream; under a gradient exchange (learner_host.h) the list
+// splits into ce_ppo2_partial [moments' merge, gradient, partial reduce] and
+// ce_ppo2_apply [combine, finish, Adam, repack] around the caller's
+// all-gather.  Every argument check precedes the first HIP call,
 // and the checks of the plain arguments precede the check of the handle, so
 // they run without a device.
 #include <hip/hip_runtime.h>
@@ -25,6 +28,14 @@ namespace ce {
 
 void ppo2_launch_reduce(const Ppo2ReduceArgs &q, hipStream_t stream) {
     hipLaunchKernelGGL(ppo2_reduce_kernel, dim3((q.p.n_params + 255) / 256), dim3(256), 0, stream, q);
+}
+
+void ppo2_launch_partial(const Ppo2PartialArgs &q, hipStream_t stream) {
+    hipLaunchKernelGGL(ppo2_partial_kernel, dim3((q.p.n_params + 255) / 256), dim3(256), 0, stream, q);
+}
+
+void ppo2_launch_combine(const Ppo2CombineArgs &q, hipStream_t stream) {
+    hipLaunchKernelGGL(ppo2_combine_kernel, dim3((q.n_params + 255) / 256), dim3(256), 0, stream, q);
 }
 
 }  // namespace ce
@@ -68,17 +79,15 @@ int batch_ok(const char *who, const ce_ppo2 *l, int64_t n, int64_t m, const int3
     return CE_OK;
 }
 
-// [advantage statistics, gradient, reduce, finish] into grad / stats
-void enqueue_grad(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
-                  const float *actions, const float *adv, const float *ret,
-                  const float *old_neglogp, const float *old_values, float cliprange,
-                  float *grad, float *stats, hipStream_t stream) {
+// [gradient] of n rows weighted 1 / n_total, normalised by l->advstat, into
+// the slab; returns the grid
+int enqueue_grad_kernel(const ce_ppo2 *l, int64_t n, int64_t n_total, int64_t m,
+                        const int32_t *idx, const float *obs, const float *actions,
+                        const float *adv, const float *ret, const float *old_neglogp,
+                        const float *old_values, float cliprange, hipStream_t stream) {
     const ce_ppo2_config &c = l->cfg;
-    hipLaunchKernelGGL(ce::ppo2_advstat_kernel, dim3(1), dim3(ce::kPpoStatBlock), 0, stream,
-                       static_cast<int>(n), static_cast<int>(m), idx, adv, c.normalize_adv,
-                       l->advstat);
     ce::Ppo2GradArgs g{};
-    ce::learner_fill_grad_args(g, l->core, c.vf_coef, n, m, idx, obs);
+    ce::learner_fill_grad_args(g, l->core, c.vf_coef, n, n_total, m, idx, obs);
     g.cliprange = cliprange > 0.0f ? cliprange : c.cliprange;
     // a per-call cliprange moves the policy clip only
     g.cliprange_vf = c.cliprange_vf;
@@ -90,8 +99,38 @@ void enqueue_grad(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, co
     g.advstat = l->advstat;
     hipLaunchKernelGGL(ce::ppo2_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
                        l->core.lds_bytes, stream, g);
-    ce::learner_enqueue_reduce_finish<ce::ppo2_finish_kernel>(l->core, g.n, g.grid, c.ent_coef,
-                                                              c.vf_coef, grad, stats, stream);
+    return g.grid;
+}
+
+// [advantage statistics, gradient, reduce, finish] into grad / stats
+void enqueue_grad(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const float *obs,
+                  const float *actions, const float *adv, const float *ret,
+                  const float *old_neglogp, const float *old_values, float cliprange,
+                  float *grad, float *stats, hipStream_t stream) {
+    const ce_ppo2_config &c = l->cfg;
+    hipLaunchKernelGGL(ce::ppo2_advstat_kernel, dim3(1), dim3(ce::kPpoStatBlock), 0, stream,
+                       static_cast<int>(n), static_cast<int>(m), idx, adv, c.normalize_adv,
+                       l->advstat);
+    const int grid = enqueue_grad_kernel(l, n, n, m, idx, obs, actions, adv, ret, old_neglogp,
+                                         old_values, cliprange, stream);
+    ce::learner_enqueue_reduce_finish<ce::ppo2_finish_kernel>(l->core, static_cast<int>(n), grid,
+                                                              c.ent_coef, c.vf_coef, grad, stats,
+                                                              stream);
+}
+
+// [Adam, repack] from the core's grad and the |grad|^2 in stats; one more step
+void enqueue_adam(ce_ppo2 *l, float lr, const float *stats, hipStream_t stream) {
+    const ce_ppo2_config &c = l->cfg;
+    ce::LearnerCore &core = l->core;
+    const long long t = ++l->t;
+    const double lr_t = (lr > 0.0f ? lr : c.lr) * std::sqrt(1.0 - std::pow(double(c.beta2), double(t))) /
+                        (1.0 - std::pow(double(c.beta1), double(t)));
+    hipLaunchKernelGGL(ce::ppo2_adam_kernel, dim3((core.plan.n_params + 255) / 256), dim3(256), 0,
+                       stream, core.plan.n_params, core.grad, stats, c.max_grad_norm,
+                       static_cast<float>(lr_t), c.beta1, c.beta2,
+                       static_cast<float>(1.0 - double(c.beta1)),
+                       static_cast<float>(1.0 - double(c.beta2)), c.eps, core.params, l->m, l->v);
+    ce::policy_repack(core.policy, core.params, stream);
 }
 
 }  // namespace
@@ -196,19 +235,103 @@ int ce_ppo2_step(ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const flo
     if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR();
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    ce::LearnerCore &core = l->core;
     enqueue_grad(l, n, m, idx, obs, actions, advantages, returns, old_neglogp, old_values,
-                 cliprange, core.grad, stats, stream);
-    const ce_ppo2_config &c = l->cfg;
-    const long long t = ++l->t;
-    const double lr_t = (lr > 0.0f ? lr : c.lr) * std::sqrt(1.0 - std::pow(double(c.beta2), double(t))) /
-                        (1.0 - std::pow(double(c.beta1), double(t)));
-    hipLaunchKernelGGL(ce::ppo2_adam_kernel, dim3((core.plan.n_params + 255) / 256), dim3(256), 0,
-                       stream, core.plan.n_params, core.grad, stats, c.max_grad_norm,
-                       static_cast<float>(lr_t), c.beta1, c.beta2,
-                       static_cast<float>(1.0 - double(c.beta1)),
-                       static_cast<float>(1.0 - double(c.beta2)), c.eps, core.params, l->m, l->v);
-    ce::policy_repack(core.policy, core.params, stream);
+                 cliprange, l->core.grad, stats, stream);
+    enqueue_adam(l, lr, stats, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int64_t ce_learner_record_bytes(const ce_policy *policy) {
+    if (!policy) {
+        fail(CE_EINVAL, "ce_learner_record_bytes: null policy");
+        return -1;
+    }
+    return int64_t(ce::ppo_record_doubles(ce::policy_plan(policy).n_params)) * 8;
+}
+
+int ce_ppo2_adv_moments(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx,
+                        const float *advantages, double *out3, void *hip_stream) {
+    const char *who = "ce_ppo2_adv_moments";
+    const int rc = ce::learner_rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    if (!advantages) return fail(CE_EINVAL, std::string(who) + ": null advantages");
+    if (!out3) return fail(CE_EINVAL, std::string(who) + ": null output");
+    if (reinterpret_cast<uintptr_t>(out3) & 7)
+        return fail(CE_EINVAL, std::string(who) + ": the output must be 8-byte aligned");
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    CE_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ce::ppo2_advmoments_kernel, dim3(1), dim3(ce::kPpoStatBlock), 0,
+                       static_cast<hipStream_t>(hip_stream), static_cast<int>(n),
+                       static_cast<int>(m), idx, advantages, out3);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ppo2_partial(ce_ppo2 *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                    const float *obs, const float *actions, const float *advantages,
+                    const float *returns, const float *old_neglogp, const float *old_values,
+                    float cliprange, int32_t world, const double *moments, double *record,
+                    void *hip_stream) {
+    const char *who = "ce_ppo2_partial";
+    int rc = ce::learner_rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    if ((rc = ce::learner_partial_ok(who, n, n_total, record)) != CE_OK) return rc;
+    if (world < 1 || world > ce::kLearnerMaxWorld)
+        return fail(CE_EINVAL, std::string(who) + ": world must be in [1, 2^16], got " +
+                                   std::to_string(world));
+    if (reinterpret_cast<uintptr_t>(moments) & 7)
+        return fail(CE_EINVAL, std::string(who) + ": the moments must be 8-byte aligned");
+    // `record` stands in for stats in the null checks the entry points share
+    rc = batch_ok(who, l, n, m, idx, obs, actions, advantages, returns, old_neglogp, old_values,
+                  reinterpret_cast<const float *>(record));
+    if (rc != CE_OK) return rc;
+    if (l->cfg.normalize_adv && !moments)
+        return fail(CE_EINVAL, std::string(who) + ": the learner normalises advantages and "
+                                                  "got no moments");
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (l->cfg.normalize_adv)
+        hipLaunchKernelGGL(ce::ppo2_advmerge_kernel, dim3(1), dim3(64), 0, stream, world, moments,
+                           l->advstat);
+    else
+        hipLaunchKernelGGL(ce::ppo2_advstat_kernel, dim3(1), dim3(ce::kPpoStatBlock), 0, stream,
+                           static_cast<int>(n), static_cast<int>(m), idx, advantages, 0,
+                           l->advstat);
+    const int grid = enqueue_grad_kernel(l, n, n_total, m, idx, obs, actions, advantages, returns,
+                                         old_neglogp, old_values, cliprange, stream);
+    ce::learner_enqueue_partial(l->core, static_cast<int>(n), grid, record, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ppo2_combine(ce_ppo2 *l, int32_t world, const double *records, int64_t n_total,
+                    float *grad, float *stats, void *hip_stream) {
+    const char *who = "ce_ppo2_combine";
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    if (!grad) return fail(CE_EINVAL, std::string(who) + ": null grad");
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    CE_CLEAR_STALE_ERROR();
+    ce::learner_enqueue_combine_finish<ce::ppo2_finish_kernel>(
+        l->core, world, records, n_total, l->cfg.ent_coef, l->cfg.vf_coef, grad, stats,
+        static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ppo2_apply(ce_ppo2 *l, int32_t world, const double *records, int64_t n_total, float lr,
+                  float *stats, void *hip_stream) {
+    const char *who = "ce_ppo2_apply";
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    CE_CLEAR_STALE_ERROR();
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    ce::learner_enqueue_combine_finish<ce::ppo2_finish_kernel>(
+        l->core, world, records, n_total, l->cfg.ent_coef, l->cfg.vf_coef, l->core.grad, stats,
+        stream);
+    enqueue_adam(l, lr, stats, stream);
     CE_HIP(hipGetLastError());
     return CE_OK;
 }

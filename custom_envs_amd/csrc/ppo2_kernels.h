@@ -75,10 +75,53 @@ __global__ __launch_bounds__(kPpoStatBlock) void ppo2_advstat_kernel(
     }
 }
 
+// Under a gradient exchange the normalisation is over every rank's rows.
+// ppo2_advmoments_kernel: ppo2_advstat_kernel's two passes over this rank's
+// gathered advantages, left as the triple (n_r, mean_r, M2_r = sum (a -
+// mean_r)^2) in float64.  ppo2_advmerge_kernel: the `world` triples merged in
+// rank order by Chan's formula (merge_moments_numpy states it), one thread,
+// into {mean, 1 / (sqrt(M2 / N) + 1e-8)}.  At world 1 no merge step runs and
+// the two floats are ppo2_advstat_kernel's.
+__global__ __launch_bounds__(kPpoStatBlock) void ppo2_advmoments_kernel(
+    int n, int m, const int32_t *idx, const float *adv, double *out3) {
+    __shared__ double red[kPpoStatBlock];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kPpoStatBlock) s += adv[ppo_src_row(idx, i, m)];
+    const double mean = ppo_block_sum(s, red) / n;
+    s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kPpoStatBlock) {
+        const double d = adv[ppo_src_row(idx, i, m)] - mean;
+        s += d * d;
+    }
+    const double m2 = ppo_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        out3[0] = n;
+        out3[1] = mean;
+        out3[2] = m2;
+    }
+}
+
+__global__ __launch_bounds__(64) void ppo2_advmerge_kernel(int world, const double *moments,
+                                                           float *out) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0) return;
+    double cnt = moments[0], mean = moments[1], m2 = moments[2];
+    for (int r = 1; r < world; ++r) {
+        const double nr = moments[3 * r], delta = moments[3 * r + 1] - mean;
+        const double tot = cnt + nr;
+        mean = mean + delta * nr / tot;
+        m2 = m2 + moments[3 * r + 2] + delta * delta * cnt * nr / tot;
+        cnt = tot;
+    }
+    out[0] = static_cast<float>(mean);
+    out[1] = static_cast<float>(1.0 / (sqrt(m2 / cnt) + 1e-8));
+}
+
 // ------------------------------------------------------------------ gradient
 struct Ppo2GradArgs {
     PolicyPlan p;                    // shape, image offsets and img of the policy
     int n, m;                        // rows of the call; rows of the arrays idx gathers from
+    int n_total;                     // N of the mean (n unless ranks exchange gradients)
     int tiles, grid;                 // 32-row tiles; workgroups per network
     int img_floats;                  // floats of one partial
     int w_floats, act_floats;        // LDS floats: weight stage, one activation buffer
@@ -155,6 +198,52 @@ __global__ __launch_bounds__(256) void ppo2_reduce_kernel(const Ppo2ReduceArgs q
     if (threadIdx.x == 0) q.sq[blockIdx.x] = sq;
 }
 
+// ------------------------------------------------------- partial, combine
+// (Ppo2PartialArgs, Ppo2CombineArgs and the record: ppo_grad_tile.h)
+// The reduce kernel's grid.  Block 0 also folds the statistic sums over the G
+// workgroups (the finish kernels' loop) and writes the row count.
+__global__ __launch_bounds__(256) void ppo2_partial_kernel(const Ppo2PartialArgs q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < q.p.n_params) {
+        int s = 0;
+        while (s + 1 < q.p.n_segs && q.p.seg_src[s + 1] <= p) ++s;
+        const int i = p - q.p.seg_src[s], cols = q.p.seg_cols[s];
+        const int r = i / cols, c = i - r * cols;
+        const float *at = q.slab + q.p.seg_dst[s] + r * q.p.seg_cols_pad[s] + c;
+        double sum = 0.0;
+        for (int gi = 0; gi < q.grid; ++gi) sum += at[static_cast<long long>(gi) * q.p.img_floats];
+        q.record[p] = sum;
+    }
+    if (blockIdx.x == 0) {
+        const int tid = threadIdx.x;
+        if (tid < 2 * kPpoRowStats) {
+            double t = 0.0;
+            for (int gi = 0; gi < q.grid; ++gi) t += q.stat_slab[gi * 2 * kPpoRowStats + tid];
+            q.record[q.p.n_params + tid] = t;
+        } else if (tid < ppo_record_doubles(q.p.n_params) - q.p.n_params) {
+            // the row count, then zeros to the record's padded end
+            q.record[q.p.n_params + tid] = tid == 2 * kPpoRowStats ? static_cast<double>(q.n) : 0.0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ppo2_combine_kernel(const Ppo2CombineArgs q) {
+    __shared__ double red[256];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    double sq = 0.0;
+    if (p < q.n_params) {
+        double sum = 0.0;
+        for (int r = 0; r < q.world; ++r)
+            sum += q.records[static_cast<long long>(r) * q.record_doubles + p];
+        if (p >= q.off_logstd_flat) sum -= q.ent_coef;
+        const float gf = static_cast<float>(sum);
+        q.grad[p] = gf;
+        sq = static_cast<double>(gf) * gf;
+    }
+    sq = ppo_block_sum(sq, red);
+    if (threadIdx.x == 0) q.sq[blockIdx.x] = sq;
+}
+
 // The six statistics and |grad|^2 from the partials, one workgroup.
 __global__ __launch_bounds__(256) void ppo2_finish_kernel(const Ppo2FinishArgs f) {
     __shared__ double red[256];
@@ -165,7 +254,7 @@ __global__ __launch_bounds__(256) void ppo2_finish_kernel(const Ppo2FinishArgs f
     const double gn2 = ppo_block_sum(s, red);
     if (tid < 2 * kPpoRowStats) {
         double t = 0.0;
-        for (int gi = 0; gi < f.grid; ++gi) t += f.stat_slab[gi * 2 * kPpoRowStats + tid];
+        for (int gi = 0; gi < f.grid; ++gi) t += f.stat_slab[static_cast<long long>(gi) * f.stat_stride + tid];
         sums[tid] = t;
     }
     __syncthreads();

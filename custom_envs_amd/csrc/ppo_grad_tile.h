@@ -11,8 +11,11 @@
 //                               (float64): statistics, returns the row weight
 //                               w = d loss / d neglogp
 //
-// and the fields p, n, m, tiles, grid, img_floats, w_floats, act_floats, idx,
-// obs, slab, stat_slab as Ppo2GradArgs names them.
+// and the fields p, n, n_total, m, tiles, grid, img_floats, w_floats,
+// act_floats, idx, obs, slab, stat_slab as Ppo2GradArgs names them.  n bounds
+// the live rows; n_total is the N of the loss's mean, 1 / N the row weight: n
+// itself for a learner alone, the ranks' rows together under a gradient
+// exchange (learner_host.h).
 //
 // Grid (G, 2) x 256 threads, G = min(tiles, limit).  blockIdx.y picks the
 // network as in policy_mlp_kernel; workgroup x walks the 32-row tiles x,
@@ -135,7 +138,7 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
     const int li = lane & 31, h = lane >> 5;
     const int net = blockIdx.y;
     const int L = a.n_hidden;
-    const float inv_n = 1.0f / static_cast<float>(g.n);
+    const float inv_n = 1.0f / static_cast<float>(g.n_total);
 
     ppo_f32x16 dw[kPlanLayers][4] = {};
     float db[kPlanLayers] = {};
@@ -411,9 +414,44 @@ struct Ppo2ReduceArgs {
 };
 void ppo2_launch_reduce(const Ppo2ReduceArgs &q, hipStream_t stream);
 
-// What a finish kernel reads: the partials' statistics and |grad|^2 blocks.
+// ------------------------------------------------- the gradient exchange
+// One rank's record, what crosses GPUs (learner_host.h has the launch lists):
+//   [n_params f64 | 2 kPpoRowStats f64 | n_r as f64], padded to 256 B
+// the per-parameter float64 sums over the G partials in flat parameter order,
+// before the reduce kernel's rounding and without its -ent_coef; the statistic
+// sums of stat_slab over G; the rows of this rank.
+constexpr int kPpoRecordTail = 2 * kPpoRowStats + 1;
+__host__ __device__ constexpr int ppo_record_doubles(int n_params) {
+    return (n_params + kPpoRecordTail + 31) / 32 * 32;
+}
+
+// ppo2_partial_kernel: ppo2_reduce_kernel's sum, unrounded, into `record`.
+struct Ppo2PartialArgs {
+    PolicyPlan p;
+    int grid, n;
+    const float *slab;
+    const double *stat_slab;
+    double *record;  // [ppo_record_doubles(n_params)]
+};
+void ppo2_launch_partial(const Ppo2PartialArgs &q, hipStream_t stream);
+
+// ppo2_combine_kernel: grad[p] = the `world` records' values added in rank
+// order in float64 (-ent_coef on logstd), rounded once; sq as the reduce
+// kernel's.  At world 1 these are the reduce kernel's bits.
+struct Ppo2CombineArgs {
+    int n_params, off_logstd_flat, world, record_doubles;
+    float ent_coef;
+    const double *records;   // [world][record_doubles]
+    float *grad;
+    double *sq;
+};
+void ppo2_launch_combine(const Ppo2CombineArgs &q, hipStream_t stream);
+
+// What a finish kernel reads: `grid` statistic partials, stat_stride doubles
+// apart (the workgroups' of stat_slab, or the ranks' inside their records),
+// and the |grad|^2 blocks.
 struct Ppo2FinishArgs {
-    int n, grid, n_sq, A, off_logstd;
+    int n, grid, n_sq, A, off_logstd, stat_stride;
     float ent_coef, vf_coef;
     const float *img;
     const double *stat_slab, *sq;

@@ -318,3 +318,98 @@ class ShardedEnvs:
                                            group=self.group, async_op=async_op)
         res = GatheredOutputs(self.layout, self.gathered[slot], self.counts, self.derived)
         return (res, work) if async_op else res
+
+
+class GradientExchange:
+    """The gradient exchange of a data-parallel learner (``PPO2Learner`` or
+    ``A2CLearner``): every rank acts and differentiates on its own rows with
+    its own replica of the policy, and only the gradient crosses GPUs.
+
+    Constructing one attaches it (``learner.exchange``); from then on the
+    learner's ``grad`` / ``step`` / ``update`` are the single learner's on the
+    concatenation of the ranks' rows: its kernels write this rank's float64
+    record straight into slot ``rank`` of ``records`` ``[world][record]``, ONE
+    in-place ``all_gather_into_tensor`` on the caller's current stream gives
+    every rank every record (RCCL under ``nccl``; gloo in the one-GPU
+    rehearsals and the CPU tests), and every rank adds them in rank order, so
+    the replicas stay bit-identical.  PPO2 with advantage normalisation
+    gathers ``moments`` ``[world][3]`` the same way first.
+
+    ``counts``: every rank's env rows (``shard_range`` gives them; default:
+    equal shards).  The rows of one call must be in proportion to them on
+    every rank -- ``K * counts[r]`` of an ``update``, ``K * counts[r] /
+    nminibatches`` of PPO2's minibatches -- which is how each rank knows the
+    global row count without asking.  ``collective``: run the collective even
+    at world 1; default: only when world > 1.  ``device``: where the buffers
+    live; default: the learner's GPU (the CPU for a shape-only learner).
+
+    The replicas must start equal: the same seed, or ``broadcast_params``.
+    """
+
+    def __init__(self, learner, rank, world, group=None, counts=None, collective=None,
+                 device=None):
+        world, rank = int(world), int(rank)
+        if world <= 0 or not 0 <= rank < world:
+            raise ValueError('bad rank/world')
+        counts = [1] * world if counts is None else [int(c) for c in counts]
+        if len(counts) != world or min(counts) < 1:
+            raise ValueError('counts must give every one of the %d ranks at least one row, got %s'
+                             % (world, counts))
+        self.learner, self.rank, self.world, self.group = learner, rank, world, group
+        self.counts = counts
+        self.collective = world > 1 if collective is None else bool(collective)
+        if device is None:
+            device = torch.device('cuda', learner.device) if learner._h is not None \
+                else torch.device('cpu')
+        self.records = torch.zeros((world, learner.record_doubles), dtype=torch.float64,
+                                   device=device)
+        self.moments = torch.zeros((world, 3), dtype=torch.float64, device=device)
+        learner.exchange = self
+
+    @property
+    def bytes_per_step(self):
+        """Bytes every rank receives per gather of the records."""
+        return self.records.numel() * 8
+
+    def check_rows(self, rows):
+        """The env rows of this rank's rollout against ``counts``."""
+        if int(rows) != self.counts[self.rank]:
+            raise ValueError('rank %d holds %d rows, counts says %d'
+                             % (self.rank, rows, self.counts[self.rank]))
+
+    def total_rows(self, n):
+        """The rows of every rank together when this rank's call has ``n``."""
+        mine, total = self.counts[self.rank], 0
+        for r, c in enumerate(self.counts):
+            if (n * c) % mine:
+                raise ValueError('%d rows on rank %d (of %d) leave rank %d (of %d) a fraction'
+                                 % (n, self.rank, mine, r, c))
+            total += n * c // mine
+        return total
+
+    def _gather(self, buf):
+        if self.collective:
+            import torch.distributed as dist
+            # in place: send = recv + rank * count, as ShardedEnvs.gather
+            dist.all_gather_into_tensor(buf.view(-1), buf[self.rank], group=self.group)
+        return buf
+
+    def gather_records(self):
+        """Every rank's record on every rank; returns ``records``."""
+        return self._gather(self.records)
+
+    def gather_moments(self):
+        return self._gather(self.moments)
+
+    def broadcast_params(self, src=0):
+        """Rank ``src``'s master parameters to every replica, on the device."""
+        import torch.distributed as dist
+        flat = torch.empty(self.learner.n_params, dtype=torch.float32, device=self.records.device)
+        self.learner.get_params(out=flat)
+        if self.world > 1 or self.collective:
+            dist.broadcast(flat, src, group=self.group)
+        self.learner.set_params(flat)
+
+    def detach(self):
+        if self.learner.exchange is self:
+            self.learner.exchange = None

@@ -10,6 +10,12 @@ A new learner writes its hyper-parameters and config struct, its loss head in
 a ``loss_grad_numpy``, its optimiser statement, and the methods that call its
 own entry points (``grad``, ``step``, ...); ``Learner`` gives it the handle,
 the parameters, the validation of batches and rollout records, and ``close``.
+
+The gradient exchange of the data-parallel learners (``distributed.
+GradientExchange``) is here as far as both learners share it: the record's
+layout (``record_doubles``, ``pack_record_numpy``), the statement of the
+combine kernel (``combine_records_numpy``) and ``Learner.combine`` / ``apply``;
+each learner adds its ``partial``.
 """
 import ctypes
 
@@ -85,6 +91,42 @@ def clip_by_global_norm_numpy(grad, max_grad_norm, dt=None):
         norm = np.sqrt(np.sum(grad * grad))
         grad = grad * min(dt(1), dt(max_grad_norm) / (norm + dt(1e-6)))
     return grad
+
+
+# ---------------------------------------------------- the gradient exchange
+ROW_STATS = 4        # per-row statistic sums a workgroup keeps per network (kPpoRowStats)
+RECORD_TAIL = 2 * ROW_STATS + 1      # the statistic sums of both networks, then n_r
+
+
+def record_doubles(n_params):
+    """Float64 entries of one rank's record ``[n_params sums | 2 * ROW_STATS
+    statistic sums | n_r]``, padded to a multiple of 256 B."""
+    return (int(n_params) + RECORD_TAIL + 31) // 32 * 32
+
+
+def pack_record_numpy(grad_sum, stat_sums, n):
+    """One rank's record from its float64 per-parameter sums (the rows'
+    gradient terms already weighted 1 / N, no entropy term), its
+    ``2 * ROW_STATS`` statistic sums and its row count."""
+    grad_sum = np.asarray(grad_sum, np.float64).reshape(-1)
+    rec = np.zeros(record_doubles(grad_sum.size), np.float64)
+    rec[:grad_sum.size] = grad_sum
+    rec[grad_sum.size:grad_sum.size + 2 * ROW_STATS] = np.asarray(stat_sums, np.float64)
+    rec[grad_sum.size + 2 * ROW_STATS] = n
+    return rec
+
+
+def combine_records_numpy(records, n_params, act_dim, ent_coef, dtype=np.float64):
+    """The statement of the combine kernel: the gradient of all the ranks'
+    rows from their records ``[W][>= n_params]``, added in rank order in
+    float64, the entropy term's ``-ent_coef`` on ``logstd`` (the last
+    ``act_dim`` parameters) once, then rounded to ``dtype``."""
+    records = np.asarray(records, np.float64)
+    grad = np.zeros(n_params, np.float64)
+    for rec in records:                # rank order: every rank adds the same way
+        grad = grad + rec[:n_params]
+    grad[n_params - act_dim:] -= np.float64(ent_coef)
+    return grad.astype(dtype)
 
 
 # --------------------------------------------------------------------- learner
@@ -249,6 +291,85 @@ class Learner:
         ptrs = [batch[n].data_ptr() for n in self.BATCH_FIELDS]
         head = [self._h, N, M, None if idx is None else idx.data_ptr()] + ptrs
         return head, stats
+
+    # ------------------------------------------------------- gradient exchange
+    # Each learner has its ``partial`` (the rows of this rank into its record);
+    # what starts from the gathered records is the same for both.
+    exchange = None      # a distributed.GradientExchange attaches itself here
+    STATS = Stats
+
+    @property
+    def record_doubles(self):
+        return record_doubles(self.n_params)
+
+    @staticmethod
+    def _rows_of(batch, idx):
+        """The rows of a call before anything else is checked."""
+        t = idx if idx is not None else batch.get('obs')
+        return int(t.shape[0]) if t is not None and t.dim() >= 1 else 0
+
+    @staticmethod
+    def check_total(n, n_total):
+        """``n_total`` (None: ``n``) as an int no smaller than ``n``."""
+        n_total = int(n) if n_total is None else int(n_total)
+        if n_total < n:
+            raise ValueError('n_total = %d is less than the %d rows of this call' % (n_total, n))
+        return n_total
+
+    def check_record_tensor(self, name, t, shape):
+        """A float64 tensor the exchange kernels read or write: dtype, shape,
+        contiguity, then (with a handle) the device."""
+        import torch
+        if not hasattr(t, 'data_ptr') or t.dtype != torch.float64:
+            raise ValueError('%s must be a float64 tensor, got %s'
+                             % (name, getattr(t, 'dtype', type(t).__name__)))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s must have shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+        if self._h is not None:
+            self.policy.check_device(name, t)
+
+    def _record_out(self, out, like):
+        """The record a ``partial`` call writes: ``out`` checked, or a new one."""
+        import torch
+        if out is None:
+            return torch.zeros(self.record_doubles, dtype=torch.float64, device=like.device)
+        self.check_record_tensor('out', out, (self.record_doubles,))
+        return out
+
+    def _records_head(self, records, n_total):
+        """The checked leading arguments of ``combine`` / ``apply`` and the
+        statistics tensor the call writes."""
+        import torch
+        if not hasattr(records, 'dim') or records.dim() != 2:
+            raise ValueError('records must have shape [world][%d]' % self.record_doubles)
+        world = int(records.shape[0])
+        self.check_record_tensor('records', records, (world, self.record_doubles))
+        n_total = int(n_total)
+        if world < 1 or n_total < 1:
+            raise ValueError('records of %d ranks and n_total = %d' % (world, n_total))
+        stats = torch.empty(N_STATS, dtype=torch.float32, device=records.device)
+        return [self._h, world, records.data_ptr(), n_total], stats
+
+    def combine(self, records, n_total, stream=None):
+        """The gradient and statistics of all ``n_total`` rows from the ranks'
+        records ``[world][record_doubles]``, no update.  Returns (grad,
+        ``Stats``)."""
+        import torch
+        head, stats = self._records_head(records, n_total)
+        grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
+        self._call('combine', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
+        return grad, self.STATS(stats)
+
+    def apply(self, records, n_total, lr=None, stream=None):
+        """Combine, finish, the optimiser's step (one) and the repack from the
+        ranks' records.  Returns ``Stats``."""
+        head, stats = self._records_head(records, n_total)
+        self._call('apply', *head, -1.0 if lr is None else lr, stats.data_ptr(),
+                   self._stream(stream))
+        self.policy._host_params = None
+        return self.STATS(stats)
 
     def close(self):
         if getattr(self, '_h', None):

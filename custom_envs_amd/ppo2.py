@@ -22,6 +22,10 @@ The three ``*_numpy`` functions are the executable statement of the semantics
 the current parameters, not the rollout's noise form: the parameters have
 moved since the action was drawn.
 
+``adv_moments_numpy`` and ``merge_moments_numpy`` state how ranks that
+exchange gradients (``distributed.GradientExchange``) normalise advantages
+over all their rows: per-rank two-pass moments, merged in rank order.
+
 ``PPO2Learner`` owns the master flat parameters, Adam's ``m`` / ``v`` and the
 step count on the policy's device and writes every update through to the
 policy's image, so the next ``forward_device`` / ``rollout_policy`` sees it.
@@ -146,6 +150,31 @@ def adam_step_numpy(params, grad, m, v, t, lr, max_grad_norm=0.5, beta1=0.9, bet
     return params - lr_t * m / (np.sqrt(v) + dt(eps)), m, v
 
 
+def adv_moments_numpy(advantages):
+    """What ``ppo2_advmoments_kernel`` leaves for one rank: ``(n, mean, M2 =
+    sum (a - mean)^2)`` in float64, by the two-pass formula."""
+    a = np.asarray(advantages, np.float64).reshape(-1)
+    mean = a.sum() / a.size
+    d = a - mean
+    return np.array([a.size, mean, np.sum(d * d)], np.float64)
+
+
+def merge_moments_numpy(moments):
+    """The statement of ``ppo2_advmerge_kernel``: the ranks' ``[W][3]``
+    triples merged in rank order by Chan's formula.  Returns ``(mean, 1 /
+    (sqrt(M2 / N) + 1e-8))`` in float64: the normalisation of all N
+    advantages.  One triple passes through untouched."""
+    moments = np.asarray(moments, np.float64).reshape(-1, 3)
+    cnt, mean, m2 = moments[0]
+    for nr, mean_r, m2_r in moments[1:]:
+        delta = mean_r - mean
+        tot = cnt + nr
+        mean = mean + delta * nr / tot
+        m2 = m2 + m2_r + delta * delta * cnt * nr / tot
+        cnt = tot
+    return mean, 1.0 / (np.sqrt(m2 / cnt) + 1e-8)
+
+
 # --------------------------------------------------------------------- learner
 class Stats(learner.Stats):
     """The statistics of one ``grad`` / ``step`` call as a device tensor
@@ -166,6 +195,7 @@ class PPO2Learner(Learner):
     PREFIX = 'ce_ppo2'
     CONFIG = CePpo2Config
     BATCH_FIELDS = BATCH_FIELDS
+    STATS = Stats
     _loss_grad = staticmethod(loss_grad_numpy)
 
     def __init__(self, policy, gamma=0.99, lam=0.95, cliprange=0.2, cliprange_vf=None,
@@ -210,16 +240,84 @@ class PPO2Learner(Learner):
         """The loss gradient of the rows ``idx`` (None: all) of ``batch``, no
         update.  Returns (grad ``[n_params]`` device tensor, ``Stats``)."""
         import torch
+        if self.exchange is not None:      # the gradient of every rank's rows
+            records, n_total = self._exchange_records(batch, idx, stream, cliprange)
+            return self.combine(records, n_total, stream=stream)
         head, stats = self._head(batch, idx)
         grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
         self._call('grad', *head, -1.0 if cliprange is None else cliprange, grad.data_ptr(),
                    stats.data_ptr(), self._stream(stream))
         return grad, Stats(stats)
 
+    # ------------------------------------------------------- gradient exchange
+    def adv_moments(self, batch, idx=None, out=None, stream=None):
+        """``(n, mean, M2)`` of the advantages of the rows ``idx`` (None: all)
+        as three float64 on the device (``out`` or a new tensor): this rank's
+        share of the global normalisation (``merge_moments_numpy``)."""
+        import torch
+        M, N = self.check_batch(batch, idx)
+        if out is None:
+            out = torch.zeros(3, dtype=torch.float64, device=batch['obs'].device)
+        else:
+            self.check_record_tensor('out', out, (3,))
+        self._call('adv_moments', self._h, N, M, None if idx is None else idx.data_ptr(),
+                   batch['advantages'].data_ptr(), out.data_ptr(), self._stream(stream))
+        return out
+
+    def partial(self, batch, idx=None, n_total=None, moments=None, out=None, stream=None,
+                cliprange=None):
+        """This rank's share of a step of ``n_total`` rows (None: its own
+        ``n``): the gradient of the rows ``idx`` with the row weight ``1 /
+        n_total``, normalised by the merged ``moments`` (``[world][3]``
+        float64, every rank's ``adv_moments``; None with ``n_total == n``:
+        this call's own), as one float64 record in ``out`` (``[record_doubles]``;
+        None: a new tensor).  Returns the record."""
+        n_total = self.check_total(self._rows_of(batch, idx), n_total)
+        if out is not None:
+            self.check_record_tensor('out', out, (self.record_doubles,))
+        M, N = self.check_batch(batch, idx)
+        world = 1
+        if not self.hp.normalize_adv:
+            moments = None
+        elif moments is None:
+            if n_total != N:
+                raise ValueError('moments of every rank are needed to normalise over n_total = %d '
+                                 'rows (this call has %d)' % (n_total, N))
+            moments = self.adv_moments(batch, idx, stream=stream).reshape(1, 3)
+        else:
+            if not hasattr(moments, 'dim') or moments.dim() != 2:
+                raise ValueError('moments must have shape [world][3]')
+            world = int(moments.shape[0])
+            self.check_record_tensor('moments', moments, (world, 3))
+        out = self._record_out(out, batch['obs'])
+        ptrs = [batch[n].data_ptr() for n in self.BATCH_FIELDS]
+        self._call('partial', self._h, N, n_total, M, None if idx is None else idx.data_ptr(),
+                   *ptrs, -1.0 if cliprange is None else cliprange, world,
+                   None if moments is None else moments.data_ptr(), out.data_ptr(),
+                   self._stream(stream))
+        return out
+
+    def _exchange_records(self, batch, idx, stream, cliprange):
+        """partial, the gather(s): (the gathered records, n_total)."""
+        ex = self.exchange
+        n_total = ex.total_rows(self._rows_of(batch, idx))
+        moments = None
+        if self.hp.normalize_adv:
+            self.adv_moments(batch, idx, out=ex.moments[ex.rank], stream=stream)
+            moments = ex.gather_moments()
+        self.partial(batch, idx, n_total=n_total, moments=moments, out=ex.records[ex.rank],
+                     stream=stream, cliprange=cliprange)
+        return ex.gather_records(), n_total
+
     def step(self, batch, idx=None, stream=None, lr=None, cliprange=None):
         """Gradient, global-norm clip, Adam and the policy image's repack as
         one stream-ordered call.  ``lr`` / ``cliprange`` override the
-        learner's for this call.  Returns ``Stats``."""
+        learner's for this call.  Returns ``Stats``.  With a gradient exchange
+        attached it is the step on every rank's rows: [moments, gather,]
+        partial, gather, apply."""
+        if self.exchange is not None:
+            records, n_total = self._exchange_records(batch, idx, stream, cliprange)
+            return self.apply(records, n_total, lr=lr, stream=stream)
         head, stats = self._head(batch, idx)
         self._call('step', *head, -1.0 if lr is None else lr,
                    -1.0 if cliprange is None else cliprange, stats.data_ptr(),
@@ -242,7 +340,11 @@ class PPO2Learner(Learner):
         """The whole PPO2 update of one rollout: GAE, then ``noptepochs``
         passes of ``nminibatches`` ``step`` calls over slices of one
         ``torch.randperm`` per epoch (drawn on the device from ``generator``).
-        Nothing is read back; returns the ``Stats`` of every step, in order."""
+        Nothing is read back; returns the ``Stats`` of every step, in order.
+        With a gradient exchange attached every rank splits its own ``K * R_r``
+        rows with its own ``generator``, and ``K * R_r`` must divide by
+        ``nminibatches`` on every rank (checked on every rank, before any
+        launch)."""
         import torch
         for name in ('obs', 'actions', 'values', 'neglogps', 'rewards', 'dones', 'last_values'):
             if result.get(name) is None:
@@ -255,6 +357,14 @@ class PPO2Learner(Learner):
         if total % nminibatches:
             raise ValueError('K * R = %d rows do not split into %d minibatches'
                              % (total, nminibatches))
+        if self.exchange is not None:
+            # decided for every rank on every rank, so none enters a
+            # collective alone
+            self.exchange.check_rows(rows)
+            for r, c in enumerate(self.exchange.counts):
+                if (k * c) % nminibatches:
+                    raise ValueError('rank %d: K * R = %d rows do not split into %d minibatches'
+                                     % (r, k * c, nminibatches))
         for name, tail in (('obs', (self.policy.obs_dim,)), ('actions', (self.policy.act_dim,)),
                            ('neglogps', ())):
             t = result[name]

@@ -548,7 +548,8 @@ int ce_ppo2_step(ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx, const flo
  * Every argument check precedes the first HIP call, and the checks of the
  * plain arguments precede the check of the handle.
  * Not here: DDPG, MlpLstmPolicy, explained_variance, a learning-rate
- * scheduler (pass lr per call), multi-GPU gradient exchange.
+ * scheduler (pass lr per call).  The gradient exchange across GPUs is the
+ * last section of this header.
  */
 typedef struct ce_a2c ce_a2c;
 
@@ -603,6 +604,61 @@ int ce_a2c_update(ce_a2c *l, int32_t k, int64_t rows, const float *obs, const fl
                   const float *rewards, int64_t reward_stride_bytes, const uint8_t *dones,
                   int64_t done_stride_bytes, const float *last_values, float lr, float *stats,
                   void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Data-parallel learners: the gradient exchange across GPUs.  W ranks, rank r
+ * holding n_r rows, take the single learner's step on all n_total = sum n_r
+ * rows (the mean is 1 / n_total; PPO2 normalises advantages over all of them).
+ * A _partial call ends with this rank's record ready to gather; an _apply call
+ * starts from the W gathered records.  The collective in between is the
+ * caller's (custom_envs_amd/distributed.py: GradientExchange).
+ *
+ * A record is ce_learner_record_bytes(policy) bytes of float64, a multiple of
+ * 256: [n_params sums over this rank's rows, in flat parameter order, before
+ * any rounding and without the entropy term | 8 statistic sums | n_r].
+ * `records` is [world][record], rank r's record in slot r.  Every rank adds
+ * the records in rank order in float64, so every rank computes the same bits,
+ * and at world 1 _partial + _apply leave the bits of _step.  Records and
+ * moments are device pointers, 8-byte aligned.  Stream-ordered, no
+ * synchronisation, no allocation (ce_a2c_update_partial's returns buffer
+ * aside, as ce_a2c_update's).
+ */
+int64_t ce_learner_record_bytes(const ce_policy *policy);   /* -1: null policy */
+/* out3 = (n, mean, sum (a - mean)^2) of the n gathered advantages, float64. */
+int ce_ppo2_adv_moments(const ce_ppo2 *l, int64_t n, int64_t m, const int32_t *idx,
+                        const float *advantages, double *out3, void *hip_stream);
+/* ce_ppo2_grad's rows with the row weight 1 / n_total (n_total >= n), into
+ * `record`.  moments: [world][3], every rank's ce_ppo2_adv_moments triple,
+ * merged in rank order (Chan) into the normalisation; NULL only when the
+ * learner does not normalise advantages. */
+int ce_ppo2_partial(ce_ppo2 *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                    const float *obs, const float *actions, const float *advantages,
+                    const float *returns, const float *old_neglogp, const float *old_values,
+                    float cliprange, int32_t world, const double *moments, double *record,
+                    void *hip_stream);
+/* grad [n_params] and stats [8] of all n_total rows from the records; no update. */
+int ce_ppo2_combine(ce_ppo2 *l, int32_t world, const double *records, int64_t n_total,
+                    float *grad, float *stats, void *hip_stream);
+/* ce_ppo2_combine, then the clip, Adam (one step) and the repack. */
+int ce_ppo2_apply(ce_ppo2 *l, int32_t world, const double *records, int64_t n_total, float lr,
+                  float *stats, void *hip_stream);
+/* ce_a2c_grad's rows with the row weight 1 / n_total, into `record`. */
+int ce_a2c_partial(ce_a2c *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                   const float *obs, const float *actions, const float *returns,
+                   const float *old_values, double *record, void *hip_stream);
+/* ce_a2c_update's returns scan and gradient on the rollout records in place,
+ * with the row weight 1 / n_total (n_total >= k * rows), into `record`. */
+int ce_a2c_update_partial(ce_a2c *l, int32_t k, int64_t rows, int64_t n_total, const float *obs,
+                          const float *actions, int64_t action_stride_bytes, const float *values,
+                          int64_t value_stride_bytes, const float *rewards,
+                          int64_t reward_stride_bytes, const uint8_t *dones,
+                          int64_t done_stride_bytes, const float *last_values, double *record,
+                          void *hip_stream);
+int ce_a2c_combine(ce_a2c *l, int32_t world, const double *records, int64_t n_total, float *grad,
+                   float *stats, void *hip_stream);
+/* ce_a2c_combine, then the clip, RMSProp and the repack. */
+int ce_a2c_apply(ce_a2c *l, int32_t world, const double *records, int64_t n_total, float lr,
+                 float *stats, void *hip_stream);
 
 #ifdef __cplusplus
 }
