@@ -1,39 +1,39 @@
 // C-ABI implementation of the MI355X Optimize-v0 engine (include/custom_envs_amd.h).
 //
-// Host responsibilities: own the device copy of the dataset and the per-env
+// ce_create is plan -> allocate -> upload -> seed.  The plan (engine_plan.h)
+// is everything decided from the config and the CE_* switches before any
+// device call: which of the five kernel families runs (ce::Path), with which
+// instance, sizes and names; every later entry point switches on plan.path.
+// The rest is the host's part: own the device copy of the dataset (one image
+// per path, built on the host by the *_build_image functions) and the per-env
 // state (struct-of-arrays, one contiguous [E][P] slab per quantity so a
 // wave's P values are one coalesced segment), stage host actions/outputs
 // through pinned buffers (engine_host.h, shared with the other engines), and
-// launch one fused step kernel per VecEnv.step (optimize_kernels.h).  The
-// env RNG is native (seeding.cpp): W0 and the reset permutation are drawn
-// once per seed and uploaded, because use_random_state never advances the
-// env RNG (custom_envs/utils/utils_math.py:9-22), so every reset replays the
-// same draws.
+// launch one fused step kernel per VecEnv.step.  The env RNG is native
+// (seeding.cpp): W0 and the reset permutation are drawn once per seed and
+// uploaded, because use_random_state never advances the env RNG
+// (custom_envs/utils/utils_math.py:9-22), so every reset replays the same
+// draws.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
-#include <algorithm>
-#include <thread>
-
 #include "engine_host.h"
-#include "mlp_kernels.h"
-#include "net_engine.h"
-#include "optimize_kernels.h"
-#include "optimize_mfma.h"
+#include "engine_plan.h"   // and through it the kernel headers of every path but the pair kernel's
 #include "optimize_pair_kernel.h"
 #include "seeding.h"
 
 namespace {
 
 using ce::fail;
-
-using StepFn = void (*)(const void *args, int grid, size_t lds, hipStream_t stream);
+using ce::KernelEntry;
+using ce::Path;
+using ce::StepFn;
 
 template <typename T, int F, int K, bool STAGED>
 void launch_step(const void *args, int grid, size_t lds, hipStream_t stream) {
@@ -59,12 +59,6 @@ void launch_reset(const void *args, int grid, size_t, hipStream_t stream) {
                        stream, *static_cast<const ce::StepArgs<T> *>(args));
 }
 
-struct KernelEntry {
-    int precision, F, K;
-    StepFn step_staged, step_global, reset;
-    StepFn step_pair[2];   // U = 1, 2 (nullptr where the shape has no pair path)
-};
-
 // Shapes with a compiled register-path instance.
 #define CE_SHAPES(X) \
     X(2, 2) X(4, 2) X(4, 3) X(5, 2) X(8, 2) X(10, 2) X(16, 2) X(20, 2) X(10, 3) X(10, 4) X(3, 3)
@@ -80,72 +74,108 @@ struct KernelEntry {
 
 const KernelEntry kKernels[] = {CE_SHAPES(CE_ENTRY)};
 
-const KernelEntry *find_kernel(int precision, int F, int K) {
+}  // namespace
+
+const KernelEntry *ce::find_kernel(int precision, int F, int K) {
     for (const auto &k : kKernels)
         if (k.precision == precision && k.F == F && k.K == K) return &k;
     return nullptr;
 }
 
-
-}  // namespace
-
 struct ce_engine {
     ce_config cfg{};
-    int P = 0, obs_dim = 0;
-    bool mlp = false;  // CE_PROBLEM_MLP
-    ce::NetPlan *net = nullptr;   // CE_PROBLEM_MLP on the layered path (net_engine.hip)
-    ce::NetGeom net_geo{};        // its weight-image geometry: W / W0 are [E][Pimg] images
-    std::vector<int> dims;        // network: F, hidden..., K
-    bool mlp_split = false;  // two launches per step (CE_MLP_SPLIT=1 or CE_MLP_PHASES)
-    int mlp_phases = 3;  // bit 0: train kernel, bit 1: info kernel (CE_MLP_PHASES, profiling)
-    size_t tsize = 8;  // element size of W / W0
-    size_t gsize = 8;  // element size of G (grad_hist)
-    const KernelEntry *kern = nullptr;
+    ce::EnginePlan plan;          // what ce_create decided (engine_plan.h)
     // stream, staging buffers, step_many bookkeeping; host.compact:
     // ce_set_compact_outputs; host.persist: the persistent K-step kernel
     // (optimize_lr_persist.h) is available for the shape
     ce::Host<ce_outputs> host;
+    ce::NetPlan *net = nullptr;   // Path::Net: the layered path's work buffers (net_engine.hip)
     // device state
-    void *X = nullptr;
-    float *Xs = nullptr;   // MLP: dataset in MFMA operand order (mlp_kernels.h)
-    int32_t *label = nullptr;
+    void *X = nullptr;            // the path's dataset image
+    float *Xs = nullptr;          // MlpFused: the dataset in MFMA operand order (mlp_kernels.h)
+    int32_t *label = nullptr;     // MlpFused, Net
     void *W = nullptr, *G = nullptr, *W0 = nullptr;
     double *L = nullptr;
     int32_t *step = nullptr;
     int32_t *perm = nullptr, *order = nullptr, *order_sel = nullptr;
-    bool staged = false;      // dataset fits the per-block LDS stage
-    StepFn pair = nullptr;    // two-envs-per-wave step kernel, when the shape has one
-    int gen_ft = 0;           // > 0: the runtime-shape MFMA kernel with this many feature tiles
-    bool lr_mfma = false;     // two-class full-batch MFMA kernel (optimize_lr_mfma.h)
-    std::string kernel_name;  // what ce_step_kernel reports
-    size_t stage_bytes = 0;
-    int lr_waves = 0;         // CE_LR_WAVES: force the two-class MFMA kernel's wave count
-    int gen_tail = 1;         // CE_GEN_TAIL=0: the runtime-shape kernel's last feature on MFMA too
-    int gen_cat = 1;          // CE_GEN_CAT=0: full batch on the one-env-per-wave kernel
-    int lr_mode_cap = 3;      // CE_LR_MODE: cap on the two-class MFMA kernel's row-loop mode
-    std::string many_name;    // what ce_step_many_kernel reports when persistent
     unsigned long long *diag = nullptr;   // CE_DIAG builds: per-wave phase stamps
 };
 
 namespace {
 
-template <typename T>
-ce::StepArgs<T> make_args(const ce_engine *e, const float *act, const ce_outputs &o,
-                          bool compact = false) {
-    ce::StepArgs<T> a;
+// The register kernels' image, [rows | labels]: row-major rows padded to
+// ce::row_stride elements (zeros in the pad), then the int32 labels at the
+// next 16-byte boundary, in one buffer staged with one copy.  Two-class
+// shapes store s_y x with s_y = +1 (y = 0) / -1 (y = 1) (ce::signed_rows,
+// optimize_kernels.h): exact, and it folds the label into the row's dot
+// product.
+std::vector<unsigned char> register_build_image(int F, int K, int N, size_t tsize,
+                                                const double *x, const int32_t *y) {
+    const size_t RS = ce::row_stride(F, static_cast<int>(tsize));
+    const size_t xbytes = ce::align16(N * RS * tsize);
+    const bool sign_fold = ce::signed_rows(F, K);
+    std::vector<unsigned char> blob(ce::align16(xbytes + 4 * static_cast<size_t>(N)), 0);
+    for (size_t r = 0; r < static_cast<size_t>(N); ++r)
+        for (size_t f = 0; f < static_cast<size_t>(F); ++f) {
+            const double v = (sign_fold && y[r] != 0) ? -x[r * F + f] : x[r * F + f];
+            const float v32 = static_cast<float>(v);
+            if (tsize == sizeof(double)) std::memcpy(&blob[(r * RS + f) * 8], &v, 8);
+            else std::memcpy(&blob[(r * RS + f) * 4], &v32, 4);
+        }
+    std::memcpy(&blob[xbytes], y, 4 * static_cast<size_t>(N));
+    return blob;
+}
+
+// The MLP problem's image: the [N][F] float32 rows, then (the fused kernel
+// only) the same rows in MFMA operand order, MlpArgs::Xs (mlp_kernels.h).
+std::vector<unsigned char> mlp_build_image(size_t F, size_t N, const double *x, bool operand_copy) {
+    std::vector<unsigned char> bytes((operand_copy ? 2 : 1) * N * F * sizeof(float));
+    float *x32 = reinterpret_cast<float *>(bytes.data()), *xs = x32 + N * F;
+    for (size_t i = 0; i < N * F; ++i) x32[i] = static_cast<float>(x[i]);
+    const size_t chunks = F / 8;
+    for (size_t t = 0; operand_copy && t < N / 32; ++t)
+        for (size_t c = 0; c < chunks; ++c)
+            for (size_t l = 0; l < 64; ++l)
+                for (size_t j = 0; j < 4; ++j)
+                    xs[((t * chunks + c) * 64 + l) * 4 + j] =
+                        x32[(32 * t + (l & 31)) * F + 8 * c + 4 * (l >> 5) + j];
+    return bytes;
+}
+
+// The dataset image of the plan's path, as ce_create uploads it.
+std::vector<unsigned char> dataset_image(const ce_config &c, const ce::EnginePlan &p,
+                                         const double *x, const int32_t *y) {
+    switch (p.path) {
+    case Path::Register:
+        return register_build_image(c.n_features, c.n_classes, c.n_rows, p.tsize, x, y);
+    case Path::Gen:
+        return ce::gen_build_image(c.n_features, c.n_rows, x, y);
+    case Path::LrMfma: {
+        std::vector<unsigned char> bytes(ce::lr_image_doubles(c.n_features, c.n_rows) * sizeof(double));
+        ce::lr_build_image(c.n_features, c.n_rows, x, y, reinterpret_cast<double *>(bytes.data()));
+        return bytes;
+    }
+    case Path::MlpFused:
+    case Path::Net:
+        return mlp_build_image(c.n_features, c.n_rows, x, p.path == Path::MlpFused);
+    }
+    return {};
+}
+
+// The fields StepArgs, MlpArgs and NetArgs share.
+template <typename A>
+void fill_shared_args(A &a, const ce_engine *e, const float *act, const ce_outputs &o) {
     a.E = e->cfg.num_envs;
     a.N = e->cfg.n_rows;
-    a.B = e->cfg.batch_size;
-    a.max_steps = e->cfg.max_steps;
-    a.auto_reset = e->cfg.auto_reset;
     a.F = e->cfg.n_features;
     a.K = e->cfg.n_classes;
-    a.data = static_cast<const unsigned char *>(e->X);
-    a.W = static_cast<T *>(e->W);
-    a.G = static_cast<T *>(e->G);
+    a.max_steps = e->cfg.max_steps;
+    a.auto_reset = e->cfg.auto_reset;
+    a.W = static_cast<decltype(a.W)>(e->W);
+    a.G = static_cast<decltype(a.G)>(e->G);
+    a.W0 = static_cast<decltype(a.W0)>(e->W0);
     a.L = e->L;
     a.step = e->step;
-    a.W0 = static_cast<const T *>(e->W0);
     a.perm = e->perm;
     a.order = e->order;
     a.order_sel = e->order_sel;
@@ -156,139 +186,106 @@ ce::StepArgs<T> make_args(const ce_engine *e, const float *act, const ce_outputs
     a.objective = o.objective;
     a.accuracy = o.accuracy;
     a.episode_len = o.episode_len;
+}
+
+// compact: the caller's device outputs are in the compact form
+// (ce_set_compact_outputs; only the two-class MFMA path writes it)
+template <typename T>
+ce::StepArgs<T> make_args(const ce_engine *e, const float *act, const ce_outputs &o,
+                          bool compact = false) {
+    ce::StepArgs<T> a;
+    fill_shared_args(a, e, act, o);
+    const ce::Switches &sw = e->plan.sw;
+    const int P = e->plan.P;
+    a.B = e->cfg.batch_size;
+    a.data = static_cast<const unsigned char *>(e->X);
     a.diag = e->diag;
     a.inv_B = 1.0 / static_cast<double>(e->cfg.batch_size);
-    const int P = e->cfg.n_features * e->cfg.n_classes;
     a.p_mul = (65536 + P - 1) / P;
-    a.lr_waves = e->lr_waves;
-    a.gen_tail = e->gen_tail;
-    a.gen_cat = e->gen_cat;
-    a.lr_mode_cap = e->lr_mode_cap;
+    a.lr_waves = sw.lr_waves;
+    a.gen_tail = sw.gen_tail;
+    a.gen_cat = sw.gen_cat;
+    a.lr_mode_cap = sw.lr_mode_cap;
     a.obs_stride = compact ? P + 1 : 2 * P + 1;
     a.obs_lo = compact ? P : 0;
     return a;
 }
 
-int grid_of(const ce_engine *e) {
-    return (e->cfg.num_envs + ce::kWavesPerBlock - 1) / ce::kWavesPerBlock;
-}
-
 ce::MlpArgs make_mlp_args(const ce_engine *e, const float *act, const ce_outputs &o) {
     ce::MlpArgs a;
-    a.E = e->cfg.num_envs;
-    a.N = e->cfg.n_rows;
-    a.F = e->cfg.n_features;
-    a.K = e->cfg.n_classes;
-    a.P = e->P;
-    a.max_steps = e->cfg.max_steps;
-    a.auto_reset = e->cfg.auto_reset;
+    fill_shared_args(a, e, act, o);
+    a.P = e->plan.P;
     a.X = static_cast<const float *>(e->X);
     a.Xs = e->Xs;
-    a.diag = e->diag;
     a.label = e->label;
-    a.W = static_cast<float *>(e->W);
-    a.W0 = static_cast<const float *>(e->W0);
-    a.G = static_cast<double *>(e->G);
-    a.L = e->L;
-    a.step = e->step;
-    a.perm = e->perm;
-    a.order = e->order;
-    a.order_sel = e->order_sel;
-    a.act = act;
-    a.obs = o.obs;
-    a.reward = o.reward;
-    a.done = o.done;
-    a.objective = o.objective;
-    a.accuracy = o.accuracy;
-    a.episode_len = o.episode_len;
+    a.diag = e->diag;
     return a;
 }
 
 ce::NetArgs make_net_args(const ce_engine *e, const float *act, const ce_outputs &o) {
     ce::NetArgs a{};
-    a.E = e->cfg.num_envs;
-    a.N = e->cfg.n_rows;
-    a.F = e->cfg.n_features;
-    a.K = e->cfg.n_classes;
+    fill_shared_args(a, e, act, o);
+    const std::vector<int> &dims = e->plan.dims;
     a.B = e->cfg.batch_size;
-    a.P = e->P;
-    a.max_steps = e->cfg.max_steps;
-    a.auto_reset = e->cfg.auto_reset;
-    a.n_hidden = static_cast<int>(e->dims.size()) - 2;
-    for (int l = 0; l < a.n_hidden; ++l) a.hidden[l] = e->dims[l + 1];
+    a.P = e->plan.P;
+    a.n_hidden = static_cast<int>(dims.size()) - 2;
+    for (int l = 0; l < a.n_hidden; ++l) a.hidden[l] = dims[l + 1];
     a.X = static_cast<const float *>(e->X);
     a.label = e->label;
-    a.W = static_cast<float *>(e->W);
-    a.W0 = static_cast<const float *>(e->W0);
-    a.G = static_cast<double *>(e->G);
-    a.L = e->L;
-    a.step = e->step;
-    a.perm = e->perm;
-    a.order = e->order;
-    a.order_sel = e->order_sel;
-    a.act = act;
-    a.obs = o.obs;
-    a.reward = o.reward;
-    a.done = o.done;
-    a.objective = o.objective;
-    a.accuracy = o.accuracy;
-    a.episode_len = o.episode_len;
     return a;
 }
 
-// compact: the caller's device outputs are in the compact form
-// (ce_set_compact_outputs; only the two-class MFMA path writes it)
+// One workgroup per env; `even` / `odd`: the kernel's <true> / <false>
+// instance (P even: pair accesses aligned in every env).
+using MlpKernel = void (*)(ce::MlpArgs);
+void launch_mlp(MlpKernel even, MlpKernel odd, const ce::MlpArgs &a, hipStream_t stream) {
+    const MlpKernel kernel = (a.P & 1) == 0 ? even : odd;
+    hipLaunchKernelGGL(kernel, dim3(a.E), dim3(ce::kMlpBlock), 0, stream, a);
+}
+
 int launch(const ce_engine *e, bool reset, const float *act, const ce_outputs &o,
            hipStream_t stream, bool compact = false) {
-    if (e->net) {
+    const ce::EnginePlan &p = e->plan;
+    switch (p.path) {
+    case Path::Net: {
         const ce::NetArgs a = make_net_args(e, act, o);
         return reset ? ce::net_reset(e->net, a, stream) : ce::net_step(e->net, a, stream);
     }
-    if (e->mlp) {
+    case Path::MlpFused: {
         const ce::MlpArgs a = make_mlp_args(e, act, o);
-        const dim3 grid(e->cfg.num_envs), block(ce::kMlpBlock);
-        const bool even = (e->P & 1) == 0;   // pair accesses aligned in every env
         if (reset) {
-            hipLaunchKernelGGL(ce::mlp_reset_kernel, grid, block, 0, stream, a);
-        } else if (!e->mlp_split) {
-            if (even) hipLaunchKernelGGL(ce::mlp_step_kernel<true>, grid, block, 0, stream, a);
-            else hipLaunchKernelGGL(ce::mlp_step_kernel<false>, grid, block, 0, stream, a);
+            launch_mlp(ce::mlp_reset_kernel, ce::mlp_reset_kernel, a, stream);
+        } else if (!p.sw.mlp_split) {
+            launch_mlp(ce::mlp_step_kernel<true>, ce::mlp_step_kernel<false>, a, stream);
         } else {
-            if (e->mlp_phases & 1) {
-                if (even) hipLaunchKernelGGL(ce::mlp_train_kernel<true>, grid, block, 0, stream, a);
-                else hipLaunchKernelGGL(ce::mlp_train_kernel<false>, grid, block, 0, stream, a);
-            }
-            if (e->mlp_phases & 2) {
-                if (even) hipLaunchKernelGGL(ce::mlp_info_kernel<true>, grid, block, 0, stream, a);
-                else hipLaunchKernelGGL(ce::mlp_info_kernel<false>, grid, block, 0, stream, a);
-            }
+            if (p.sw.mlp_phases & 1)
+                launch_mlp(ce::mlp_train_kernel<true>, ce::mlp_train_kernel<false>, a, stream);
+            if (p.sw.mlp_phases & 2)
+                launch_mlp(ce::mlp_info_kernel<true>, ce::mlp_info_kernel<false>, a, stream);
         }
         return CE_OK;
     }
-    if (e->lr_mfma) {
-        auto a = make_args<double>(e, act, o, compact);
-        if (reset)
-            ce::gen_launch_reset(a, stream);
-        else
-            ce::lr_launch_step(a, stream);
+    case Path::LrMfma:
+    case Path::Gen: {   // compact is never set off the LrMfma path
+        const auto a = make_args<double>(e, act, o, compact);
+        if (reset) ce::gen_launch_reset(a, stream);
+        else if (p.path == Path::LrMfma) ce::lr_launch_step(a, stream);
+        else ce::gen_launch_step(a, stream);
         return CE_OK;
     }
-    if (e->gen_ft) {
-        auto a = make_args<double>(e, act, o);
-        if (reset)
-            ce::gen_launch_reset(a, stream);
-        else
-            ce::gen_launch_step(a, stream);
+    case Path::Register: {
+        const StepFn fn = reset ? p.kern->reset
+                                : p.pair ? p.pair : p.staged ? p.kern->step_staged : p.kern->step_global;
+        const int grid = (e->cfg.num_envs + ce::kWavesPerBlock - 1) / ce::kWavesPerBlock;
+        if (e->cfg.precision == CE_F64) {
+            const auto a = make_args<double>(e, act, o);
+            fn(&a, grid, p.stage_bytes, stream);
+        } else {
+            const auto a = make_args<float>(e, act, o);
+            fn(&a, grid, p.stage_bytes, stream);
+        }
         return CE_OK;
     }
-    StepFn fn = reset ? e->kern->reset
-                      : (e->pair ? e->pair : (e->staged ? e->kern->step_staged : e->kern->step_global));
-    if (e->cfg.precision == CE_F64) {
-        auto a = make_args<double>(e, act, o);
-        fn(&a, grid_of(e), e->stage_bytes, stream);
-    } else {
-        auto a = make_args<float>(e, act, o);
-        fn(&a, grid_of(e), e->stage_bytes, stream);
     }
     return CE_OK;
 }
@@ -310,63 +307,117 @@ struct OptOps {
     }
     // one policy row per env
     static void policy_shape(const ce_engine *e, int *obs_dim, int *act_dim, int64_t *rows) {
-        *obs_dim = e->obs_dim;
-        *act_dim = e->P;
+        *obs_dim = e->plan.obs_dim;
+        *act_dim = e->plan.P;
         *rows = e->cfg.num_envs;
     }
 };
 
-// Convert host float64 values to a device array of `elem`-byte floats.
+// Host float64 values <-> a device array of `elem`-byte floats (through a
+// float32 copy where elem is 4); both wait for the copy.
 int upload_typed(ce_engine *e, void *dst, const double *src, size_t count, size_t elem) {
-    if (elem == sizeof(double)) {
-        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, e->host.stream));
-    } else {
-        std::vector<float> tmp(count);
-        for (size_t i = 0; i < count; ++i) tmp[i] = static_cast<float>(src[i]);
-        CE_HIP(hipMemcpyAsync(dst, tmp.data(), count * sizeof(float), hipMemcpyHostToDevice,
-                              e->host.stream));
-        CE_HIP(hipStreamSynchronize(e->host.stream));
-    }
+    const std::vector<float> tmp(src, src + (elem == sizeof(float) ? count : 0));
+    const void *from = tmp.empty() ? static_cast<const void *>(src) : tmp.data();
+    CE_HIP(hipMemcpyAsync(dst, from, count * elem, hipMemcpyHostToDevice, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
     return CE_OK;
 }
 
 int download_typed(ce_engine *e, double *dst, const void *src, size_t count, size_t elem) {
-    if (elem == sizeof(double)) {
-        CE_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, e->host.stream));
-        CE_HIP(hipStreamSynchronize(e->host.stream));
-    } else {
-        std::vector<float> tmp(count);
-        CE_HIP(hipMemcpyAsync(tmp.data(), src, count * sizeof(float), hipMemcpyDeviceToHost,
-                              e->host.stream));
-        CE_HIP(hipStreamSynchronize(e->host.stream));
-        for (size_t i = 0; i < count; ++i) dst[i] = tmp[i];
-    }
+    std::vector<float> tmp(elem == sizeof(float) ? count : 0);
+    void *to = tmp.empty() ? static_cast<void *>(dst) : tmp.data();
+    CE_HIP(hipMemcpyAsync(to, src, count * elem, hipMemcpyDeviceToHost, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
+    std::copy(tmp.begin(), tmp.end(), dst);
     return CE_OK;
 }
 
-// The network path's weight images <-> the flat float64 vectors of ce_state
-int net_download(ce_engine *e, double *dst, const void *img) {
-    const size_t E = e->cfg.num_envs, P = e->P, PI = static_cast<size_t>(e->net_geo.Pimg);
+// E flat float32 weight vectors -> the network path's zero-padded images
+int upload_net_images(ce_engine *e, void *img, const float *flat) {
+    const size_t E = e->cfg.num_envs, P = e->plan.P, PI = e->plan.wstride;
+    std::vector<float> tmp(E * PI);
+    for (size_t i = 0; i < E; ++i) ce::net_flat_to_image(e->plan.geo, &flat[i * P], &tmp[i * PI]);
+    CE_HIP(hipMemcpyAsync(img, tmp.data(), E * PI * sizeof(float), hipMemcpyHostToDevice, e->host.stream));
+    CE_HIP(hipStreamSynchronize(e->host.stream));
+    return CE_OK;
+}
+
+// W or W0 <-> the flat [E][P] float64 vectors of ce_state: the network
+// path's weight images, every other path's typed slab
+int download_weights(ce_engine *e, double *dst, const void *src) {
+    const size_t E = e->cfg.num_envs, P = e->plan.P, PI = e->plan.wstride;
+    if (e->plan.path != Path::Net) return download_typed(e, dst, src, E * P, e->plan.tsize);
     std::vector<float> tmp(E * PI), flat(P);
-    CE_HIP(hipMemcpyAsync(tmp.data(), img, E * PI * sizeof(float), hipMemcpyDeviceToHost, e->host.stream));
+    CE_HIP(hipMemcpyAsync(tmp.data(), src, E * PI * sizeof(float), hipMemcpyDeviceToHost, e->host.stream));
     CE_HIP(hipStreamSynchronize(e->host.stream));
     for (size_t i = 0; i < E; ++i) {
-        ce::net_image_to_flat(e->net_geo, &tmp[i * PI], flat.data());
+        ce::net_image_to_flat(e->plan.geo, &tmp[i * PI], flat.data());
         for (size_t p = 0; p < P; ++p) dst[i * P + p] = flat[p];
     }
     return CE_OK;
 }
 
-int net_upload(ce_engine *e, void *img, const double *src) {
-    const size_t E = e->cfg.num_envs, P = e->P, PI = static_cast<size_t>(e->net_geo.Pimg);
-    std::vector<float> tmp(E * PI), flat(P);
-    for (size_t i = 0; i < E; ++i) {
-        for (size_t p = 0; p < P; ++p) flat[p] = static_cast<float>(src[i * P + p]);
-        ce::net_flat_to_image(e->net_geo, flat.data(), &tmp[i * PI]);
+int upload_weights(ce_engine *e, void *dst, const double *src) {
+    const size_t E = e->cfg.num_envs, P = e->plan.P;
+    if (e->plan.path != Path::Net) return upload_typed(e, dst, src, E * P, e->plan.tsize);
+    std::vector<float> flat(E * P);
+    for (size_t i = 0; i < E * P; ++i) flat[i] = static_cast<float>(src[i]);
+    return upload_net_images(e, dst, flat.data());
+}
+
+// ce_create's device allocations after host.create, zeroed where a kernel
+// reads them before it writes them.  `image_bytes`: the dataset image's.
+// A failure returns its status; ce_create tears down.
+int allocate_state(ce_engine *e, size_t image_bytes) {
+    const ce::EnginePlan &p = e->plan;
+    const size_t E = e->cfg.num_envs, N = e->cfg.n_rows, P = p.P;
+    const bool mlp = p.path == Path::MlpFused || p.path == Path::Net;
+    const size_t xbytes = p.path == Path::MlpFused ? image_bytes / 2 : image_bytes;
+    CE_HIP(hipMalloc(&e->X, xbytes));
+    if (p.path == Path::MlpFused) CE_HIP(hipMalloc(&e->Xs, xbytes));
+    if (mlp) CE_HIP(hipMalloc(&e->label, N * sizeof(int32_t)));
+    if (p.path == Path::Gen && ce::gen_set_lds_limits() != CE_OK) return CE_EHIP;
+    CE_HIP(hipMalloc(&e->W, E * p.wstride * p.tsize));
+    CE_HIP(hipMalloc(&e->G, E * P * p.gsize));
+    CE_HIP(hipMalloc(&e->W0, E * p.wstride * p.tsize));
+    if (p.path == Path::Net) {   // the images' padding stays zero
+        CE_HIP(hipMemset(e->W, 0, E * p.wstride * p.tsize));
+        CE_HIP(hipMemset(e->W0, 0, E * p.wstride * p.tsize));
     }
-    CE_HIP(hipMemcpyAsync(img, tmp.data(), E * PI * sizeof(float), hipMemcpyHostToDevice, e->host.stream));
-    CE_HIP(hipStreamSynchronize(e->host.stream));
+    CE_HIP(hipMalloc(&e->L, E * sizeof(double)));
+    CE_HIP(hipMalloc(&e->step, E * sizeof(int32_t)));
+    if (e->cfg.batch_size < e->cfg.n_rows) {
+        CE_HIP(hipMalloc(&e->perm, E * N * sizeof(int32_t)));
+        CE_HIP(hipMalloc(&e->order, 2 * E * N * sizeof(int32_t)));
+        CE_HIP(hipMalloc(&e->order_sel, E * sizeof(int32_t)));
+        std::vector<int32_t> ident(E * N);
+        for (size_t i = 0; i < E; ++i)
+            for (size_t r = 0; r < N; ++r) ident[i * N + r] = static_cast<int32_t>(r);
+        CE_HIP(hipMemcpy(e->order, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
+        CE_HIP(hipMemcpy(e->perm, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
+        CE_HIP(hipMemset(e->order_sel, 0, E * sizeof(int32_t)));
+    }
+#ifdef CE_DIAG
+    CE_HIP(hipMalloc(&e->diag, E * ce::kStamps * sizeof(unsigned long long)));
+#endif
+    CE_HIP(hipMemset(e->G, 0, E * P * p.gsize));
+    CE_HIP(hipMemset(e->L, 0, E * sizeof(double)));
+    CE_HIP(hipMemset(e->step, 0, E * sizeof(int32_t)));
     return CE_OK;
+}
+
+// The dataset image to X (the fused MLP's second half to Xs) and the MLP
+// problem's labels.
+int upload_dataset(ce_engine *e, const std::vector<unsigned char> &image, const int32_t *labels) {
+    const Path path = e->plan.path;
+    const size_t xbytes = path == Path::MlpFused ? image.size() / 2 : image.size();
+    bool ok = hipMemcpy(e->X, image.data(), xbytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && path == Path::MlpFused)
+        ok = hipMemcpy(e->Xs, image.data() + xbytes, xbytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && (path == Path::MlpFused || path == Path::Net))
+        ok = hipMemcpy(e->label, labels, e->cfg.n_rows * sizeof(int32_t), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    return ok ? CE_OK : fail(CE_EHIP, "ce_create: dataset upload failed");
 }
 
 }  // namespace
@@ -397,276 +448,34 @@ int ce_create(const ce_config *cfg, const double *features, const int32_t *label
               ce_engine **out) {
     if (!cfg || !features || !labels || !out) return fail(CE_EINVAL, "ce_create: null argument");
     *out = nullptr;
-    if (cfg->abi_version != CE_ABI_VERSION)
-        return fail(CE_EINVAL, "ce_create: ABI version mismatch");
-    if (cfg->problem != CE_PROBLEM_SOFTMAX && cfg->problem != CE_PROBLEM_MLP)
-        return fail(CE_EUNSUPPORTED, "ce_create: unknown problem");
-    if (cfg->precision != CE_F64 && cfg->precision != CE_F32)
-        return fail(CE_EINVAL, "ce_create: unknown precision");
-    if (cfg->num_envs <= 0 || cfg->n_rows <= 0 || cfg->n_features <= 0 || cfg->n_classes <= 0)
-        return fail(CE_EINVAL, "ce_create: sizes must be positive");
-    if (cfg->batch_size <= 0 || cfg->batch_size > cfg->n_rows)
-        return fail(CE_EINVAL, "ce_create: batch_size must be in [1, n_rows]");
-    if (cfg->max_steps <= 0) return fail(CE_EINVAL, "ce_create: max_steps must be positive");
-    const bool mlp = cfg->problem == CE_PROBLEM_MLP;
-    const KernelEntry *kern = nullptr;
-    bool lr_path = false;
-    bool net_path = false;
-    std::vector<int> dims;
-    if (mlp) {
-        if (cfg->precision != CE_F32)
-            return fail(CE_EUNSUPPORTED, "ce_create: the MLP problem computes in float32");
-        if (cfg->n_layers < 0 || cfg->n_layers > ce::kNetMaxHidden)
-            return fail(CE_EUNSUPPORTED, "ce_create: the network takes 1 to 4 hidden layers");
-        dims.push_back(cfg->n_features);
-        if (cfg->n_layers == 0) dims.push_back(cfg->n_hidden);
-        for (int l = 0; l < cfg->n_layers; ++l) dims.push_back(cfg->hidden[l]);
-        dims.push_back(cfg->n_classes);
-        for (int d : dims)
-            if (d <= 0) return fail(CE_EINVAL, "ce_create: network widths must be positive");
-        // the fused config-3 kernel (mlp_kernels.h: 784 -> 64 -> 10, B = 32)
-        // where its shape holds; every other network on the layered path
-        // (net_engine.hip); CE_MLP_NET=1 forces the layered path (tests)
-        const char *fn = std::getenv("CE_MLP_NET");
-        const bool fused = !(fn && fn[0] == '1') && dims.size() == 3 &&
-                           dims[1] == ce::kMlpHidden && cfg->batch_size == ce::kMlpBatch &&
-                           cfg->n_features % 8 == 0 && cfg->n_classes <= ce::kMlpMaxK &&
-                           cfg->n_rows % 64 == 0 && cfg->batch_size < cfg->n_rows;
-        net_path = !fused;
-        if (net_path) {   // the hand-written network kernels' limits (net_engine.h)
-            ce::NetGeom geo;
-            const int rc = ce::net_geometry(static_cast<int>(dims.size()) - 2, dims.data(), &geo);
-            if (rc != CE_OK) return rc;
-        }
-    } else {
-        // a register-path instance when the shape has one (unless CE_GENERIC=1
-        // forces the runtime-shape kernel, for tests), else the MFMA kernel
-        const char *force = std::getenv("CE_GENERIC");
-        const bool generic = force && force[0] == '1';
-        // The two-class full-batch float64 shapes (the benchmark's) run on
-        // the MFMA kernel with envs along N (optimize_lr_mfma.h): 6.09 us
-        // per 4096-env step against 6.3 for the two-envs-per-wave register
-        // kernel.  CE_LR_MFMA=0 (or CE_PAIR_U) selects the
-        // register kernel instead.
-        const char *lrm = std::getenv("CE_LR_MFMA");
-        lr_path = !generic && !(lrm && lrm[0] == '0') && !std::getenv("CE_PAIR_U") &&
-                  cfg->precision == CE_F64 && cfg->batch_size == cfg->n_rows &&
-                  cfg->num_envs < (1 << 24) &&      // its packed E | F << 24 argument
-                  ce::lr_shape_ok(cfg->n_features, cfg->n_classes);
-        if (!generic && !lr_path)
-            kern = find_kernel(cfg->precision, cfg->n_features, cfg->n_classes);
-        if (!kern && !lr_path) {
-            if (cfg->precision != CE_F64 || cfg->n_features > ce::kGenMaxF ||
-                cfg->n_classes > ce::kGenMaxClasses)
-                return fail(CE_EUNSUPPORTED,
-                            "ce_create: no kernel for F=" + std::to_string(cfg->n_features) +
-                                " K=" + std::to_string(cfg->n_classes) +
-                                (cfg->precision != CE_F64
-                                     ? " in float32 (any F <= 64, K <= 16 runs in float64)"
-                                     : " (the float64 MFMA kernel takes F <= 64, K <= 16)"));
-        }
-    }
-    for (int i = 0; i < cfg->n_rows; ++i)
-        if (labels[i] < 0 || labels[i] >= cfg->n_classes)
-            return fail(CE_EINVAL, "ce_create: label out of range");
-
+    ce::EnginePlan plan;
+    int rc = ce::plan_engine(cfg, labels, ce::read_switches(), &plan);
+    if (rc != CE_OK) return rc;
     ce_engine *e = new (std::nothrow) ce_engine();
     if (!e) return fail(CE_ENOMEM, "ce_create: host allocation failed");
-    e->cfg = *cfg;
-    e->kern = kern;
-    e->mlp = mlp;
-    e->dims = dims;
-    // ce_step_many: up to 32 steps are plain launches, longer runs a cached
-    // hipGraph.  Measured (4096 envs, pair kernel): 20 steps 7.7 us per step
-    // direct vs 8.0 graph; 100 and 2000 steps equal.
-    e->host.many_direct = 32;
-    // the strided form and the K-step kernel (which stores the observation
-    // block as 16-byte units) take a 16-byte aligned obs only
-    e->host.obs_align = 16;
-    if (const char *md = std::getenv("CE_MANY_DIRECT")) e->host.many_direct = std::atoi(md);
-    if (const char *lw = std::getenv("CE_LR_WAVES")) e->lr_waves = std::atoi(lw);
-    if (const char *gt = std::getenv("CE_GEN_TAIL")) e->gen_tail = std::atoi(gt);
-    if (const char *gc = std::getenv("CE_GEN_CAT")) e->gen_cat = std::atoi(gc);
-    if (const char *lm = std::getenv("CE_LR_MODE")) e->lr_mode_cap = std::atoi(lm);
-    // experiment switch: launch one phase only, to time each kernel alone
-    if (const char *ph = std::getenv("CE_MLP_PHASES")) {
-        if (std::strcmp(ph, "train") == 0) e->mlp_phases = 1;
-        if (std::strcmp(ph, "info") == 0) e->mlp_phases = 2;
-        e->mlp_split = true;
-    }
-    if (const char *sp = std::getenv("CE_MLP_SPLIT")) e->mlp_split = e->mlp_split || sp[0] == '1';
-    if (mlp) {
-        const int64_t P = ce::net_params(cfg->n_features, cfg->n_classes,
-                                         static_cast<int>(dims.size()) - 2, dims.data() + 1);
-        if (P > (int64_t(1) << 30)) {
-            delete e;
-            return fail(CE_EUNSUPPORTED, "ce_create: network too large (P > 2^30)");
-        }
-        e->P = static_cast<int>(P);
-        e->tsize = sizeof(float);
-        e->gsize = sizeof(double);
-    } else {
-        e->P = cfg->n_features * cfg->n_classes;
-        e->tsize = cfg->precision == CE_F64 ? sizeof(double) : sizeof(float);
-        e->gsize = e->tsize;
-    }
-    e->obs_dim = 2 * e->P + 1;
-    auto bail = [&](int code) {
+    const auto bail = [&](int code) {
         ce_destroy(e);
         return code;
     };
-    int rc;
-    const size_t E = cfg->num_envs, N = cfg->n_rows, F = cfg->n_features, P = e->P;
-    rc = e->host.create(cfg->device, E * P * sizeof(float),
-                        {E * e->obs_dim * sizeof(float), E * sizeof(float), E * sizeof(float),
+    e->cfg = *cfg;
+    e->plan = std::move(plan);
+    const ce::EnginePlan &p = e->plan;
+    e->host.many_direct = p.sw.many_direct;
+    // the strided form and the K-step kernel (which stores the observation
+    // block as 16-byte units) take a 16-byte aligned obs only
+    e->host.obs_align = 16;
+    e->host.persist = p.persist;
+    const size_t E = cfg->num_envs;
+    rc = e->host.create(cfg->device, E * p.P * sizeof(float),
+                        {E * p.obs_dim * sizeof(float), E * sizeof(float), E * sizeof(float),
                          E * sizeof(float), E * sizeof(int32_t), E});
     if (rc != CE_OK) return bail(rc);
-    if (mlp) {
-        CE_TRY(hipMalloc(&e->X, N * F * sizeof(float)));
-        if (!net_path) CE_TRY(hipMalloc(&e->Xs, N * F * sizeof(float)));
-        CE_TRY(hipMalloc(&e->label, N * sizeof(int32_t)));
-    } else if (lr_path) {
-        e->lr_mfma = true;
-        CE_TRY(hipMalloc(&e->X, ce::lr_image_doubles(cfg->n_features, cfg->n_rows) *
-                                    sizeof(double)));
-    } else if (!kern) {
-        e->gen_ft = (cfg->n_features + 15) / 16;
-        CE_TRY(hipMalloc(&e->X, static_cast<size_t>(ce::gen_rows_padded_of(cfg->n_rows)) *
-                                    ce::gen_stride_of(cfg->n_features) * sizeof(double)));
-        if (ce::gen_set_lds_limits() != CE_OK) return bail(CE_EHIP);
-    } else {
-        CE_TRY(hipMalloc(&e->X, ce::stage_bytes_total(cfg->n_features, cfg->n_rows,
-                                                      static_cast<int>(e->tsize))));
-    }
-    // the network path keeps W / W0 as per-env weight images (net_kernels.h),
-    // zero-padded; G stays in the flat parameter order
-    size_t wper = P;
-    if (net_path) {
-        (void)ce::net_geometry(static_cast<int>(dims.size()) - 2, dims.data(), &e->net_geo);
-        wper = static_cast<size_t>(e->net_geo.Pimg);
-    }
-    CE_TRY(hipMalloc(&e->W, E * wper * e->tsize));
-    CE_TRY(hipMalloc(&e->G, E * P * e->gsize));
-    CE_TRY(hipMalloc(&e->W0, E * wper * e->tsize));
-    if (net_path) {
-        CE_TRY(hipMemset(e->W, 0, E * wper * e->tsize));
-        CE_TRY(hipMemset(e->W0, 0, E * wper * e->tsize));
-    }
-    CE_TRY(hipMalloc(&e->L, E * sizeof(double)));
-    CE_TRY(hipMalloc(&e->step, E * sizeof(int32_t)));
-    if (cfg->batch_size < cfg->n_rows) {
-        CE_TRY(hipMalloc(&e->perm, E * N * sizeof(int32_t)));
-        CE_TRY(hipMalloc(&e->order, 2 * E * N * sizeof(int32_t)));
-        CE_TRY(hipMalloc(&e->order_sel, E * sizeof(int32_t)));
-        std::vector<int32_t> ident(E * N);
-        for (size_t i = 0; i < E; ++i)
-            for (size_t r = 0; r < N; ++r) ident[i * N + r] = static_cast<int32_t>(r);
-        CE_TRY(hipMemcpy(e->order, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
-        CE_TRY(hipMemcpy(e->perm, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
-        CE_TRY(hipMemset(e->order_sel, 0, E * sizeof(int32_t)));
-    }
-#ifdef CE_DIAG
-    CE_TRY(hipMalloc(&e->diag, E * ce::kStamps * sizeof(unsigned long long)));
-#endif
-    CE_TRY(hipMemset(e->G, 0, E * P * e->gsize));
-    CE_TRY(hipMemset(e->L, 0, E * sizeof(double)));
-    CE_TRY(hipMemset(e->step, 0, E * sizeof(int32_t)));
-    if (mlp) {
-        std::vector<float> x32(N * F);
-        for (size_t i = 0; i < N * F; ++i) x32[i] = static_cast<float>(features[i]);
-        CE_TRY(hipMemcpy(e->X, x32.data(), N * F * sizeof(float), hipMemcpyHostToDevice));
-        if (!net_path) {   // the fused kernel's operand-ordered copy
-            std::vector<float> xs(N * F);
-            const size_t chunks = F / 8;
-            for (size_t t = 0; t < N / 32; ++t)
-                for (size_t c = 0; c < chunks; ++c)
-                    for (size_t l = 0; l < 64; ++l)
-                        for (size_t j = 0; j < 4; ++j)
-                            xs[((t * chunks + c) * 64 + l) * 4 + j] =
-                                x32[(32 * t + (l & 31)) * F + 8 * c + 4 * (l >> 5) + j];
-            CE_TRY(hipMemcpy(e->Xs, xs.data(), N * F * sizeof(float), hipMemcpyHostToDevice));
-        }
-        CE_TRY(hipMemcpy(e->label, labels, N * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (net_path) {
-            const ce::NetArgs a = make_net_args(e, nullptr, e->host.region(e->host.d_out));
-            if ((rc = ce::net_create(&e->net, a, cfg->device)) != CE_OK) return bail(rc);
-            std::string name = "net<";
-            for (size_t i = 0; i < dims.size(); ++i) name += (i ? "," : "") + std::to_string(dims[i]);
-            // ":mfma": the hand-written MFMA kernels of net_kernels.h; ":wide":
-            // a hidden layer wider than 256, the tiled kernels of net_wide.h
-            e->kernel_name = name + (e->net_geo.wide ? ">:wide" : ">:mfma");
-        }
-    }
-    if (e->lr_mfma) {
-        std::vector<double> img(ce::lr_image_doubles(cfg->n_features, cfg->n_rows));
-        ce::lr_build_image(cfg->n_features, cfg->n_rows, features, labels, img.data());
-        if (hipMemcpy(e->X, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            return bail(fail(CE_EHIP, "ce_create: dataset upload failed"));
-        e->kernel_name = ce::lr_kernel_name(cfg->num_envs, cfg->n_rows, cfg->n_features,
-                                            e->lr_waves, e->lr_mode_cap);
-        e->host.persist = ce::lr_persist_ok(cfg->n_rows);
-        if (e->host.persist) e->many_name = ce::lr_persist_name(cfg->n_rows, cfg->n_features);
-    } else if (e->gen_ft) {
-        // [Npad][RS] float64: F features, zeros to 16 FT + 1, the label as a
-        // double in the last column; rows N..Npad-1 are zeros with label -1
-        const int RS = ce::gen_stride_of(cfg->n_features);
-        const size_t npad = ce::gen_rows_padded_of(cfg->n_rows);
-        std::vector<double> img(npad * RS, 0.0);
-        for (size_t r = 0; r < npad; ++r) {
-            if (r < N)
-                for (size_t f = 0; f < F; ++f) img[r * RS + f] = features[r * F + f];
-            img[r * RS + RS - 1] = r < N ? static_cast<double>(labels[r]) : -1.0;
-        }
-        if (hipMemcpy(e->X, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            return bail(fail(CE_EHIP, "ce_create: dataset upload failed"));
-        e->kernel_name = ce::gen_kernel_name(cfg->num_envs, cfg->n_rows, cfg->batch_size,
-                                             cfg->n_features, cfg->n_classes, e->gen_cat);
-    } else if (!mlp) {
-    // [rows | labels]: row-major rows padded to ce::row_stride elements (zeros
-    // in the pad), then the int32 labels, in one buffer staged with one copy.
-    // Two-class shapes store s_y x with s_y = +1 (y = 0) / -1 (y = 1)
-    // (ce::signed_rows, optimize_kernels.h): exact, and it folds the label
-    // into the row's dot product.
-    const size_t RS = ce::row_stride(cfg->n_features, static_cast<int>(e->tsize));
-    const size_t xbytes = ce::align16(N * RS * e->tsize);
-    const bool sign_fold = ce::signed_rows(cfg->n_features, cfg->n_classes);
-    std::vector<unsigned char> blob(ce::align16(xbytes + 4 * N), 0);
-    for (size_t r = 0; r < N; ++r)
-        for (size_t f = 0; f < F; ++f) {
-            const double v = (sign_fold && labels[r] != 0) ? -features[r * F + f]
-                                                           : features[r * F + f];
-            if (cfg->precision == CE_F64) {
-                std::memcpy(&blob[(r * RS + f) * 8], &v, 8);
-            } else {
-                const float v32 = static_cast<float>(v);
-                std::memcpy(&blob[(r * RS + f) * 4], &v32, 4);
-            }
-        }
-    std::memcpy(&blob[xbytes], labels, 4 * N);
-    if (hipMemcpy(e->X, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(CE_EHIP, "ce_create: dataset upload failed"));
-    e->stage_bytes = ce::stage_bytes_total(cfg->n_features, cfg->n_rows, static_cast<int>(e->tsize));
-    e->staged = e->stage_bytes <= ce::kStageLimit;
-    if (const char *ns = std::getenv("CE_NO_STAGE"))   // experiment switch: rows from L1/L2
-        if (ns[0] == '1') e->staged = false;
-    // Two envs per wave where the shape allows it.  U = rows each lane keeps
-    // in flight: 2 for float64 (its dependent-issue latency, ~10 cycles,
-    // needs the second chain at 2 waves per SIMD), 1 for float32; measured
-    // at 4096 envs.  CE_PAIR_U = 0 / 1 / 2 overrides (0 = one
-    // env per wave).
-    {
-        int u = cfg->precision == CE_F64 ? 2 : 1;
-        if (const char *pu = std::getenv("CE_PAIR_U")) u = std::atoi(pu);
-        if (e->staged && (u == 1 || u == 2)) e->pair = e->kern->step_pair[u - 1];
-        const std::string args = std::string(cfg->precision == CE_F64 ? "double" : "float") +
-                                 "," + std::to_string(cfg->n_features);
-        e->kernel_name = e->pair ? "optimize_pair_kernel<" + args + "," + std::to_string(u) + ">"
-                                 : "optimize_step_kernel<" + args + "," +
-                                       std::to_string(cfg->n_classes) +
-                                       (e->staged ? ",true>" : ",false>");
-    }
+    const std::vector<unsigned char> image = dataset_image(*cfg, p, features, labels);
+    if ((rc = allocate_state(e, image.size())) != CE_OK) return bail(rc);
+    if ((rc = upload_dataset(e, image, labels)) != CE_OK) return bail(rc);
+    if (p.path == Path::Net) {
+        const ce::NetArgs a = make_net_args(e, nullptr, e->host.region(e->host.d_out));
+        if ((rc = ce::net_create(&e->net, a, cfg->device)) != CE_OK) return bail(rc);
     }
     // Unseeded envs behave like np_random(None): os.urandom seeds.  The host
     // side normally seeds explicitly; default to seed = env index here.
@@ -692,62 +501,48 @@ int ce_set_stream(ce_engine *e, void *stream) { return ce::host_set_stream(e, st
 
 int ce_set_compact_outputs(ce_engine *e, int32_t on) {
     if (!e) return fail(CE_EINVAL, "null engine");
-    if (on && !e->lr_mfma)
+    if (on && e->plan.path != Path::LrMfma)
         return fail(CE_EUNSUPPORTED, "ce_set_compact_outputs: only the two-class full-batch "
                                      "float64 kernel (" + std::string("optimize_lr_mfma_kernel") +
-                                     ") writes the compact form; this engine runs " + e->kernel_name);
+                                     ") writes the compact form; this engine runs " +
+                                     e->plan.kernel_name);
     if (e->host.compact != (on != 0)) e->host.graphs.release();   // captured launches carry the form
     e->host.compact = on != 0;
     return CE_OK;
 }
 
 int ce_num_envs(const ce_engine *e) { return e ? e->cfg.num_envs : CE_EINVAL; }
-int ce_obs_dim(const ce_engine *e) { return e ? e->obs_dim : CE_EINVAL; }
-int ce_act_dim(const ce_engine *e) { return e ? e->P : CE_EINVAL; }
+int ce_obs_dim(const ce_engine *e) { return e ? e->plan.obs_dim : CE_EINVAL; }
+int ce_act_dim(const ce_engine *e) { return e ? e->plan.P : CE_EINVAL; }
 
 int ce_seed(ce_engine *e, const uint64_t *seeds, int32_t n) {
     if (!e || !seeds) return fail(CE_EINVAL, "ce_seed: null argument");
     if (n != e->cfg.num_envs) return fail(CE_EINVAL, "ce_seed: need one seed per env");
-    const size_t E = n, P = e->P, N = e->cfg.n_rows;
+    const ce::EnginePlan &p = e->plan;
+    const size_t E = n, P = p.P, N = e->cfg.n_rows;
     const bool with_perm = e->perm != nullptr;
-    if (e->mlp) {
-        std::vector<float> w0(E * P);
-        std::vector<int32_t> perm(with_perm ? E * N : 0);
-        const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        const size_t nt = std::min<size_t>(hw, E);
-        std::vector<std::thread> pool;
-        for (size_t t = 0; t < nt; ++t)
-            pool.emplace_back([&, t] {
-                for (size_t i = t; i < E; i += nt)
-                    ce::reset_draws_net(seeds[i], static_cast<int>(e->dims.size()),
-                                        e->dims.data(), static_cast<int>(N), &w0[i * P],
-                                        with_perm ? &perm[i * N] : nullptr);
-            });
-        for (auto &th : pool) th.join();
-        if (e->net) {   // the weight images (net_kernels.h)
-            const size_t PI = static_cast<size_t>(e->net_geo.Pimg);
-            std::vector<float> img(E * PI);
-            for (size_t i = 0; i < E; ++i) ce::net_flat_to_image(e->net_geo, &w0[i * P], &img[i * PI]);
-            CE_HIP(hipMemcpyAsync(e->W0, img.data(), E * PI * sizeof(float), hipMemcpyHostToDevice,
-                                  e->host.stream));
-            CE_HIP(hipStreamSynchronize(e->host.stream));
+    const bool mlp = p.path == Path::MlpFused || p.path == Path::Net;
+    std::vector<int32_t> perm(with_perm ? E * N : 0);
+    std::vector<float> w32(mlp ? E * P : 0);    // the draws, alive until the last copy is done
+    std::vector<double> w64(mlp ? 0 : E * P);
+    int rc;
+    if (mlp) {
+        ce::for_each_strided(E, [&](size_t i) {
+            ce::reset_draws_net(seeds[i], static_cast<int>(p.dims.size()), p.dims.data(),
+                                static_cast<int>(N), &w32[i * P], with_perm ? &perm[i * N] : nullptr);
+        });
+        if (p.path == Path::Net) {
+            if ((rc = upload_net_images(e, e->W0, w32.data())) != CE_OK) return rc;
         } else {
-            CE_HIP(hipMemcpyAsync(e->W0, w0.data(), E * P * sizeof(float), hipMemcpyHostToDevice,
+            CE_HIP(hipMemcpyAsync(e->W0, w32.data(), E * P * sizeof(float), hipMemcpyHostToDevice,
                                   e->host.stream));
         }
-        if (with_perm)
-            CE_HIP(hipMemcpyAsync(e->perm, perm.data(), E * N * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, e->host.stream));
-        CE_HIP(hipStreamSynchronize(e->host.stream));
-        return CE_OK;
+    } else {
+        for (size_t i = 0; i < E; ++i)
+            ce::reset_draws(seeds[i], e->cfg.n_features, e->cfg.n_classes, static_cast<int>(N),
+                            &w64[i * P], with_perm ? &perm[i * N] : nullptr);
+        if ((rc = upload_typed(e, e->W0, w64.data(), E * P, p.tsize)) != CE_OK) return rc;
     }
-    std::vector<double> w0(E * P);
-    std::vector<int32_t> perm(with_perm ? E * N : 0);
-    for (size_t i = 0; i < E; ++i)
-        ce::reset_draws(seeds[i], e->cfg.n_features, e->cfg.n_classes, static_cast<int>(N),
-                        &w0[i * P], with_perm ? &perm[i * N] : nullptr);
-    int rc = upload_typed(e, e->W0, w0.data(), E * P, e->tsize);
-    if (rc != CE_OK) return rc;
     if (with_perm)
         CE_HIP(hipMemcpyAsync(e->perm, perm.data(), E * N * sizeof(int32_t),
                               hipMemcpyHostToDevice, e->host.stream));
@@ -793,10 +588,11 @@ int ce_rollout_policy(ce_engine *e, const ce_policy *p, int32_t k, const float *
 
 int ce_set_persistent(ce_engine *e, int32_t on) { return ce::host_set_persistent(e, on); }
 
+const char *ce_step_kernel(const ce_engine *e) { return e ? e->plan.kernel_name.c_str() : ""; }
+
 const char *ce_step_many_kernel(const ce_engine *e) {
     if (!e) return "";
-    if (e->host.persistent()) return e->many_name.c_str();
-    return ce_step_kernel(e);
+    return e->host.persistent() ? e->plan.many_name.c_str() : e->plan.kernel_name.c_str();
 }
 
 int64_t ce_stale_error_count(void) { return ce::stale_errors().count.load(); }
@@ -815,12 +611,34 @@ int ce_test_note_stale_error(int32_t code) {
     return CE_OK;
 }
 
-const char *ce_step_kernel(const ce_engine *e) {
-    if (!e) return "";
-    if (e->mlp && !e->net)
-        return e->mlp_split ? "mlp_train_kernel+mlp_info_kernel"
-                            : "mlp_step_kernel";
-    return e->kernel_name.c_str();
+// Test hook (not part of include/custom_envs_amd.h): what ce_create would
+// decide for this config under the current CE_* switches, without a device.
+// Returns plan_engine's status; on CE_OK the names ce_step_kernel and (with
+// the K-step kernel on) ce_step_many_kernel would report, in `cap`-byte buffers.
+int ce_test_plan(const ce_config *cfg, const int32_t *labels, char *step_name, char *many_name,
+                 int32_t cap) {
+    ce::EnginePlan plan;
+    const int rc = ce::plan_engine(cfg, labels, ce::read_switches(), &plan);
+    if (rc != CE_OK) return rc;
+    if (step_name && cap > 0) std::snprintf(step_name, cap, "%s", plan.kernel_name.c_str());
+    if (many_name && cap > 0) std::snprintf(many_name, cap, "%s", plan.many_name.c_str());
+    return CE_OK;
+}
+
+// Test hook (not part of include/custom_envs_amd.h): the dataset image
+// ce_create would upload for this config (the fused MLP's: the float32 rows,
+// then the operand-ordered copy).  Returns its byte count, or plan_engine's
+// failed status; writes the image when `out` has room for it.
+int64_t ce_test_dataset_image(const ce_config *cfg, const double *features, const int32_t *labels,
+                              void *out, int64_t cap) {
+    if (!features) return fail(CE_EINVAL, "ce_create: null argument");
+    ce::EnginePlan plan;
+    const int rc = ce::plan_engine(cfg, labels, ce::read_switches(), &plan);
+    if (rc != CE_OK) return rc;
+    const std::vector<unsigned char> image = dataset_image(*cfg, plan, features, labels);
+    const int64_t bytes = static_cast<int64_t>(image.size());
+    if (out && cap >= bytes) std::memcpy(out, image.data(), image.size());
+    return bytes;
 }
 
 int ce_host_outputs(ce_engine *e, ce_outputs *view) { return ce::host_outputs(e, view); }
@@ -838,18 +656,13 @@ int ce_diag_stamps(ce_engine *e, unsigned long long *out) {
 
 int ce_get_state(ce_engine *e, const ce_state *st) {
     if (!e || !st) return fail(CE_EINVAL, "null argument");
-    const size_t E = e->cfg.num_envs, P = e->P, N = e->cfg.n_rows;
+    const size_t E = e->cfg.num_envs, P = e->plan.P, N = e->cfg.n_rows;
     int rc;
     CE_HIP(hipStreamSynchronize(e->host.stream));
-    if (e->net) {
-        if (st->weights && (rc = net_download(e, st->weights, e->W)) != CE_OK) return rc;
-        if (st->init_weights && (rc = net_download(e, st->init_weights, e->W0)) != CE_OK) return rc;
-    } else {
-        if (st->weights && (rc = download_typed(e, st->weights, e->W, E * P, e->tsize)) != CE_OK) return rc;
-        if (st->init_weights && (rc = download_typed(e, st->init_weights, e->W0, E * P, e->tsize)) != CE_OK)
-            return rc;
-    }
-    if (st->grad_hist && (rc = download_typed(e, st->grad_hist, e->G, E * P, e->gsize)) != CE_OK) return rc;
+    if (st->weights && (rc = download_weights(e, st->weights, e->W)) != CE_OK) return rc;
+    if (st->init_weights && (rc = download_weights(e, st->init_weights, e->W0)) != CE_OK) return rc;
+    if (st->grad_hist && (rc = download_typed(e, st->grad_hist, e->G, E * P, e->plan.gsize)) != CE_OK)
+        return rc;
     if (st->loss_hist) CE_HIP(hipMemcpy(st->loss_hist, e->L, E * sizeof(double), hipMemcpyDeviceToHost));
     if (st->step) CE_HIP(hipMemcpy(st->step, e->step, E * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (st->order) {
@@ -865,18 +678,13 @@ int ce_get_state(ce_engine *e, const ce_state *st) {
 
 int ce_set_state(ce_engine *e, const ce_state *st) {
     if (!e || !st) return fail(CE_EINVAL, "null argument");
-    const size_t E = e->cfg.num_envs, P = e->P, N = e->cfg.n_rows;
+    const size_t E = e->cfg.num_envs, P = e->plan.P, N = e->cfg.n_rows;
     int rc;
     CE_HIP(hipStreamSynchronize(e->host.stream));
-    if (e->net) {
-        if (st->weights && (rc = net_upload(e, e->W, st->weights)) != CE_OK) return rc;
-        if (st->init_weights && (rc = net_upload(e, e->W0, st->init_weights)) != CE_OK) return rc;
-    } else {
-        if (st->weights && (rc = upload_typed(e, e->W, st->weights, E * P, e->tsize)) != CE_OK) return rc;
-        if (st->init_weights && (rc = upload_typed(e, e->W0, st->init_weights, E * P, e->tsize)) != CE_OK)
-            return rc;
-    }
-    if (st->grad_hist && (rc = upload_typed(e, e->G, st->grad_hist, E * P, e->gsize)) != CE_OK) return rc;
+    if (st->weights && (rc = upload_weights(e, e->W, st->weights)) != CE_OK) return rc;
+    if (st->init_weights && (rc = upload_weights(e, e->W0, st->init_weights)) != CE_OK) return rc;
+    if (st->grad_hist && (rc = upload_typed(e, e->G, st->grad_hist, E * P, e->plan.gsize)) != CE_OK)
+        return rc;
     if (st->loss_hist) CE_HIP(hipMemcpy(e->L, st->loss_hist, E * sizeof(double), hipMemcpyHostToDevice));
     if (st->step) CE_HIP(hipMemcpy(e->step, st->step, E * sizeof(int32_t), hipMemcpyHostToDevice));
     if (st->order) {

@@ -18,12 +18,15 @@
 // Dispatch is static (templates on Ops); nothing here allocates on a call path.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <thread>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "policy_engine.h"
@@ -86,6 +89,35 @@ O advance(const O &o, int64_t bytes) {
 }
 
 inline bool aligned(const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
+// OptEnvRunner's rows: the agent names "parameter-i" sorted as strings
+// (optvecenv.py:10-14,22-23).  row_agent[r] is the agent on output row r,
+// agent_row its inverse.
+inline void sorted_agent_rows(size_t P, std::vector<int32_t> *row_agent,
+                              std::vector<int32_t> *agent_row) {
+    std::vector<std::string> names(P);
+    for (size_t i = 0; i < P; ++i) names[i] = "parameter-" + std::to_string(i);
+    row_agent->resize(P);
+    agent_row->resize(P);
+    for (size_t i = 0; i < P; ++i) (*row_agent)[i] = static_cast<int32_t>(i);
+    std::sort(row_agent->begin(), row_agent->end(),
+              [&](int32_t x, int32_t y) { return names[x] < names[y]; });
+    for (size_t r = 0; r < P; ++r) (*agent_row)[(*row_agent)[r]] = static_cast<int32_t>(r);
+}
+
+// fn(i) for every i < n on up to 16 host threads, thread t taking i = t,
+// t + threads, ...: the per-env seed draws (a thread past n would draw nothing)
+template <typename Fn>
+void for_each_strided(size_t n, Fn &&fn) {
+    const size_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    const size_t nt = std::min(hw, n);
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < nt; ++t)
+        pool.emplace_back([&fn, n, nt, t] {
+            for (size_t i = t; i < n; i += nt) fn(i);
+        });
+    for (auto &th : pool) th.join();
+}
 
 // What every engine holds besides its own device state.
 template <typename O>

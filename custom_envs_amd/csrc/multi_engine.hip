@@ -201,13 +201,9 @@ int ce_multi_create(const ce_multi_config *cfg, ce_multi_engine **out) {
     CE_TRY(hipMalloc(&e->ow, H * P * E * sizeof(float)));
     CE_TRY(hipMalloc(&e->sa, H * P * E * sizeof(double)));
     CE_TRY(hipMalloc(&e->step, E * sizeof(int32_t)));
-    // OptEnvRunner rows: agent names sorted as strings (optvecenv.py:10-14,22-23)
-    std::vector<std::string> names(P);
-    for (size_t i = 0; i < P; ++i) names[i] = "parameter-" + std::to_string(i);
-    std::vector<int32_t> order(P);
-    for (size_t i = 0; i < P; ++i) order[i] = static_cast<int32_t>(i);
-    std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return names[x] < names[y]; });
-    for (size_t r = 0; r < P; ++r) e->agent_row[order[r]] = static_cast<int32_t>(r);
+    std::vector<int32_t> order, row;
+    ce::sorted_agent_rows(P, &order, &row);
+    std::copy(row.begin(), row.end(), e->agent_row);
     *out = e;
     return CE_OK;
 }

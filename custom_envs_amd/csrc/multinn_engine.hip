@@ -222,14 +222,8 @@ int ce_nn_create(const ce_nn_config *cfg, const float *features, const int32_t *
         CE_TRY(hipMemcpy(e->order, ident.data(), E * N * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     {
-        // OptEnvRunner rows: agent names sorted as strings (optvecenv.py:10-14,22-23)
-        std::vector<std::string> names(P);
-        for (long i = 0; i < P; ++i) names[i] = "parameter-" + std::to_string(i);
-        std::vector<int32_t> order(P), row(P);
-        for (long i = 0; i < P; ++i) order[i] = static_cast<int32_t>(i);
-        std::sort(order.begin(), order.end(),
-                  [&](int32_t x, int32_t y) { return names[x] < names[y]; });
-        for (long r = 0; r < P; ++r) row[order[r]] = static_cast<int32_t>(r);
+        std::vector<int32_t> order, row;
+        ce::sorted_agent_rows(P, &order, &row);
         CE_TRY(hipMemcpy(e->agent_row, row.data(), P * sizeof(int32_t), hipMemcpyHostToDevice));
         CE_TRY(hipMemcpy(e->row_agent, order.data(), P * sizeof(int32_t), hipMemcpyHostToDevice));
     }
@@ -293,16 +287,10 @@ int ce_nn_seed(ce_nn_engine *e, const uint64_t *seeds, int32_t n) {
     std::vector<float> th(E * Ps, 0.0f);
     std::vector<int32_t> rp(E * N), ep(E * N);
     const int n_dims = a.L + 2;
-    const unsigned workers = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> pool;
-    for (unsigned w = 0; w < workers; ++w) {
-        pool.emplace_back([&, w]() {
-            for (size_t i = w; i < E; i += workers)
-                ce::reset_draws_nn(seeds[i], n_dims, a.dims, a.N, th.data() + i * Ps,
-                                   rp.data() + i * N, ep.data() + i * N);
-        });
-    }
-    for (auto &t : pool) t.join();
+    ce::for_each_strided(E, [&](size_t i) {
+        ce::reset_draws_nn(seeds[i], n_dims, a.dims, a.N, th.data() + i * Ps, rp.data() + i * N,
+                           ep.data() + i * N);
+    });
     // stream-ordered after any step still reading theta0 / the permutations
     // (the engine stream is non-blocking, so null-stream copies would race)
     CE_HIP(hipStreamSynchronize(e->host.stream));

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "optimize_kernels.h"
 
@@ -16,6 +17,10 @@ constexpr int kGenMaxClasses = 16;
 // Bytes of one [Npad][RS] float64 dataset image row and the padded row count.
 int gen_stride_of(int n_features);
 int gen_rows_padded_of(int n_rows);
+// The image's bytes: per row the F features, zeros to 16 FT + 1, the label as
+// a double in the last column; rows N..Npad-1 are zeros with label -1.
+std::vector<unsigned char> gen_build_image(int n_features, int n_rows, const double *features,
+                                           const int32_t *labels);
 // Raise the dynamic-LDS limit of every instance (double-buffered row blocks).
 int gen_set_lds_limits();
 void gen_launch_step(const StepArgs<double> &a, hipStream_t stream);

@@ -203,6 +203,18 @@ std::string lr_kernel_name(int n_envs, int n_rows, int n_features, int lr_waves,
 
 int gen_stride_of(int n_features) { return gen_stride(gen_ft(n_features)); }
 int gen_rows_padded_of(int n_rows) { return gen_rows_padded(n_rows); }
+
+std::vector<unsigned char> gen_build_image(int F, int N, const double *x, const int32_t *y) {
+    const size_t RS = gen_stride_of(F), npad = gen_rows_padded_of(N);
+    std::vector<unsigned char> bytes(npad * RS * sizeof(double), 0);
+    double *img = reinterpret_cast<double *>(bytes.data());
+    for (size_t r = 0; r < npad; ++r) {
+        if (r < static_cast<size_t>(N))
+            for (int f = 0; f < F; ++f) img[r * RS + f] = x[r * F + f];
+        img[r * RS + RS - 1] = r < static_cast<size_t>(N) ? static_cast<double>(y[r]) : -1.0;
+    }
+    return bytes;
+}
 int gen_set_lds_limits() {
     for (const auto &c : kCatShapes)
         CE_HIP(hipFuncSetAttribute(c.kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -104,6 +104,29 @@ def check_rollout(spec, num_envs, k, actions, act_count, fields, record_bytes,
     return {n: v[0] for n, v in fields.items() if n != '_buffer'}
 
 
+def make_config(n_rows, n_features, n_classes, num_envs, batch_size=None, max_steps=40,
+                precision=None, device=0, auto_reset=True, model='linear', hidden=64):
+    """The ``ce_config`` of an ``OptimizeEngine`` with these arguments (the
+    engine plans its kernel path from it and the CE_* environment switches)."""
+    if model not in MODELS:
+        raise ValueError('model must be one of %s' % sorted(MODELS))
+    if precision is None:
+        precision = 'f32' if model == 'mlp' else 'f64'
+    layers = (int(hidden),) if np.isscalar(hidden) else tuple(int(h) for h in hidden)
+    if model == 'mlp' and not 1 <= len(layers) <= 4:
+        raise ValueError('hidden: 1 to 4 layer widths')
+    cfg = CeConfig(abi_version=_native.ABI_VERSION, problem=MODELS[model],
+                   precision=PRECISIONS[precision], device=int(device),
+                   num_envs=int(num_envs), n_rows=n_rows, n_features=n_features,
+                   n_classes=n_classes, batch_size=n_rows if batch_size is None else int(batch_size),
+                   max_steps=int(max_steps), auto_reset=1 if auto_reset else 0,
+                   n_hidden=layers[0] if model == 'mlp' else 0,
+                   n_layers=len(layers) if model == 'mlp' and len(layers) > 1 else 0)
+    for i, width in enumerate(layers if model == 'mlp' else ()):
+        cfg.hidden[i] = width
+    return cfg
+
+
 class OptimizeEngine:
     """E Optimize-v0 environments advanced in lock step on one GPU."""
 
@@ -113,8 +136,6 @@ class OptimizeEngine:
         float64 by default) or 'mlp' (the OptimizeNN network: F -> hidden...
         relu -> K softmax, float32; ``hidden`` a width or up to 4
         widths; hidden=64 with batch_size=32 is config 3's fused kernel)."""
-        if model not in MODELS:
-            raise ValueError('model must be one of %s' % sorted(MODELS))
         if precision is None:
             precision = 'f32' if model == 'mlp' else 'f64'
         lib = _native.load()
@@ -123,6 +144,8 @@ class OptimizeEngine:
         n_rows, n_features = features.shape
         if len(labels) != n_rows:
             raise ValueError('features and targets differ in length')
+        cfg = make_config(n_rows, n_features, n_classes, num_envs, batch_size, max_steps,
+                          precision, device, auto_reset, model, hidden)
         self.num_envs = int(num_envs)
         self.n_rows, self.n_features, self.n_classes = n_rows, n_features, n_classes
         self.batch_size = n_rows if batch_size is None else int(batch_size)
@@ -133,18 +156,6 @@ class OptimizeEngine:
         self.model = model
         self.hidden = int(hidden) if np.isscalar(hidden) else tuple(int(h) for h in hidden)
         self.device = int(device)
-        layers = (self.hidden,) if isinstance(self.hidden, int) else self.hidden
-        if model == 'mlp' and not 1 <= len(layers) <= 4:
-            raise ValueError('hidden: 1 to 4 layer widths')
-        cfg = CeConfig(abi_version=_native.ABI_VERSION, problem=MODELS[model],
-                       precision=PRECISIONS[precision], device=self.device,
-                       num_envs=self.num_envs, n_rows=n_rows, n_features=n_features,
-                       n_classes=n_classes, batch_size=self.batch_size,
-                       max_steps=self.max_steps, auto_reset=1 if auto_reset else 0,
-                       n_hidden=layers[0] if model == 'mlp' else 0,
-                       n_layers=len(layers) if model == 'mlp' and len(layers) > 1 else 0)
-        for i, width in enumerate(layers if model == 'mlp' else ()):
-            cfg.hidden[i] = width
         self._labels = np.ascontiguousarray(labels, dtype=np.int32)
         handle = ctypes.c_void_p()
         check(lib.ce_create(ctypes.byref(cfg), features.ctypes.data, self._labels.ctypes.data,

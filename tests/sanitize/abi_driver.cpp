@@ -1,6 +1,7 @@
 // Host-code sanitizer driver (ASan + UBSan, CPU only; no GPU call succeeds
 // here): every host-only C-ABI entry point with realistic and edge shapes,
-// and every entry point's argument validation with bad arguments.  The
+// every entry point's argument validation with bad arguments, and ce_create's
+// plan with the host-side dataset image builders (the library's test hooks).  The
 // draws are printed (one line per array, hex float bits / ints) so the
 // pytest wrapper (tests/test_sanitize.py) compares them with the numpy
 // oracle; any sanitizer report aborts the process with a non-zero status.
@@ -179,6 +180,79 @@ static void learner_checks() {
     REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null learner");
 }
 
+// The library's test hooks (csrc/engine.hip; not part of the public header).
+extern "C" int ce_test_plan(const ce_config *cfg, const int32_t *labels, char *step_name,
+                            char *many_name, int32_t cap);
+extern "C" int64_t ce_test_dataset_image(const ce_config *cfg, const double *features,
+                                         const int32_t *labels, void *out, int64_t cap);
+
+static ce_config plan_config(int problem, int precision, int N, int F, int K, int B) {
+    ce_config c{};
+    c.abi_version = CE_ABI_VERSION;
+    c.problem = problem;
+    c.precision = precision;
+    c.num_envs = 4;
+    c.n_rows = N;
+    c.n_features = F;
+    c.n_classes = K;
+    c.batch_size = B;
+    c.max_steps = 40;
+    c.auto_reset = 1;
+    c.n_hidden = 64;
+    return c;
+}
+
+// Plan the config and build its dataset image into an exactly sized heap
+// buffer (ASan guards both ends); the kernel name must start with `kernel`.
+static void plan_and_image(const ce_config &c, const char *kernel) {
+    std::vector<double> X(static_cast<size_t>(c.n_rows) * c.n_features);
+    std::vector<int32_t> y(c.n_rows);
+    for (size_t i = 0; i < X.size(); ++i) X[i] = 0.25 * static_cast<double>(i % 7) - 0.5;
+    for (int r = 0; r < c.n_rows; ++r) y[r] = r % c.n_classes;
+    char step[128], many[128];
+    EXPECT(ce_test_plan(&c, y.data(), step, many, sizeof(step)) == CE_OK);
+    EXPECT(std::strncmp(step, kernel, std::strlen(kernel)) == 0);
+    const int64_t bytes = ce_test_dataset_image(&c, X.data(), y.data(), nullptr, 0);
+    EXPECT(bytes > 0);
+    if (bytes <= 0) return;
+    std::vector<unsigned char> img(bytes);
+    EXPECT(ce_test_dataset_image(&c, X.data(), y.data(), img.data(), bytes) == bytes);
+    EXPECT(ce_test_dataset_image(&c, X.data(), y.data(), img.data(), bytes - 1) == bytes);
+}
+
+// ce_create's plan and its host-side image builders (no device needed): the
+// smallest shapes that exercise each pad, per path.
+static void plan_checks() {
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 5, 3, 3, 5), "optimize_step_kernel<double,3,3");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F32, 5, 3, 3, 5), "optimize_step_kernel<float,3,3");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 5, 2, 2, 3), "optimize_pair_kernel<double,2");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 1, 17, 5, 1), "optimize_mfma_kernel<5>");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 65, 17, 5, 65), "optimize_mfma_kernel<5>");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 1, 1, 2, 1), "optimize_lr_mfma_kernel<1,");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 256, 10, 2, 256), "optimize_lr_mfma_kernel<3,");
+    plan_and_image(plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 300, 13, 2, 300), "optimize_lr_mfma_kernel<4,");
+    plan_and_image(plan_config(CE_PROBLEM_MLP, CE_F32, 64, 8, 10, 32), "mlp_step_kernel");
+    plan_and_image(plan_config(CE_PROBLEM_MLP, CE_F32, 128, 16, 10, 32), "mlp_step_kernel");
+    ce_config net = plan_config(CE_PROBLEM_MLP, CE_F32, 100, 12, 7, 20);
+    net.n_layers = 4;
+    net.hidden[0] = 96;
+    net.hidden[1] = 33;
+    net.hidden[2] = 7;
+    net.hidden[3] = 48;
+    plan_and_image(net, "net<12,96,33,7,48,7>:mfma");
+    net.hidden[1] = 300;
+    plan_and_image(net, "net<12,96,300,7,48,7>:wide");
+    char name[8];
+    ce_config lr = plan_config(CE_PROBLEM_SOFTMAX, CE_F64, 256, 10, 2, 256);
+    std::vector<int32_t> y(256, 1);
+    EXPECT(ce_test_plan(&lr, y.data(), name, nullptr, sizeof(name)) == CE_OK);   // a short buffer
+    EXPECT(std::strcmp(name, "optimiz") == 0);
+    y[255] = 2;
+    EXPECT(ce_test_plan(&lr, y.data(), name, name, sizeof(name)) == CE_EINVAL);
+    EXPECT(ce_test_plan(nullptr, nullptr, nullptr, nullptr, 0) == CE_EINVAL);
+    EXPECT(ce_test_dataset_image(&lr, nullptr, y.data(), nullptr, 0) == CE_EINVAL);
+}
+
 int main() {
     EXPECT(ce_abi_version() == CE_ABI_VERSION);
     // ---- host-only draws: edge seeds and shapes
@@ -281,6 +355,7 @@ int main() {
     EXPECT(ce_nn_create(nullptr, nullptr, nullptr, nullptr) == CE_EINVAL);
     ce_nn_destroy(nullptr);
     learner_checks();
+    plan_checks();
     std::printf("failures %d\n", failures);
     return failures ? 1 : 0;
 }

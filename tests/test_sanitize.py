@@ -4,7 +4,9 @@ sanitizers on the host side only (tests/sanitize/build.py), driving every
 host-only entry point (seeding.cpp: SHA-512, MT19937, the legacy gauss /
 uniform / shuffle draws) over edge seeds and shapes, and the argument
 validation of every C-ABI entry point (ce_create's checks and the network
-geometry's included).  A sanitizer report aborts the driver; the draws it
+geometry's included), and ce_create's plan with the host-side dataset image
+builders through the library's test hooks (ce_test_plan,
+ce_test_dataset_image).  A sanitizer report aborts the driver; the draws it
 prints must equal the numpy oracle's.  CPU only: no GPU call succeeds here.
 """
 import os
