@@ -51,6 +51,8 @@ EXPORTS = (
     'ce_a2c_returns', 'ce_a2c_grad', 'ce_a2c_step', 'ce_a2c_update',
     'ce_learner_record_bytes', 'ce_ppo2_adv_moments', 'ce_ppo2_partial', 'ce_ppo2_combine',
     'ce_ppo2_apply', 'ce_a2c_partial', 'ce_a2c_update_partial', 'ce_a2c_combine', 'ce_a2c_apply',
+    'ce_ddpg_n_params', 'ce_ddpg_create', 'ce_ddpg_destroy', 'ce_ddpg_set_params',
+    'ce_ddpg_get_params', 'ce_ddpg_act', 'ce_ddpg_target', 'ce_ddpg_grad', 'ce_ddpg_step',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -122,6 +124,18 @@ class CeA2cConfig(ctypes.Structure):
             ('grid_limit', ctypes.c_int32)]
 
 
+CE_DDPG_MAX_ACT = 64
+
+
+class CeDdpgConfig(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in (
+        'abi_version', 'device', 'obs_dim', 'act_dim', 'n_hidden')] +
+        [('hidden', ctypes.c_int32 * 4), ('grid_limit', ctypes.c_int32)] +
+        [(name, ctypes.c_double) for name in (
+            'gamma', 'tau', 'actor_lr', 'critic_lr', 'beta1', 'beta2', 'eps', 'obs_lo', 'obs_hi')] +
+        [('scale', ctypes.c_float * CE_DDPG_MAX_ACT)])
+
+
 class CeState(ctypes.Structure):
     _fields_ = [('weights', ctypes.c_void_p), ('grad_hist', ctypes.c_void_p),
                 ('loss_hist', ctypes.c_void_p), ('step', ctypes.c_void_p),
@@ -133,7 +147,7 @@ _lib = None
 
 def _declare(lib):
     vp, i32, u32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64
-    f32 = ctypes.c_float
+    f32, f64 = ctypes.c_float, ctypes.c_double
     sig = {
         'ce_abi_version': ([], ctypes.c_int),
         'ce_last_error': ([], ctypes.c_char_p),
@@ -230,6 +244,16 @@ def _declare(lib):
                                    vp], ctypes.c_int),
         'ce_a2c_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
         'ce_a2c_apply': ([vp, i32, vp, i64, f32, vp, vp], ctypes.c_int),
+        'ce_ddpg_n_params': ([ctypes.POINTER(CeDdpgConfig)], ctypes.c_int),
+        'ce_ddpg_create': ([ctypes.POINTER(CeDdpgConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_ddpg_destroy': ([vp], None),
+        'ce_ddpg_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_ddpg_get_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
+        'ce_ddpg_act': ([vp, vp, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_ddpg_target': ([vp, i64, i64, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_ddpg_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_ddpg_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp],
+                         ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

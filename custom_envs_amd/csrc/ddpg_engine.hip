@@ -1,0 +1,430 @@
+// C-ABI implementation of the DDPG learner (ce_ddpg_* in
+// include/custom_envs_amd.h): owns the flat parameters, the targets, Adam's
+// moments, the two padded images the tile kernels stage from
+// (ddpg_kernels.h) and the slab of gradient partials, and enqueues on the
+// caller's stream
+//   ce_ddpg_act     [act]
+//   ce_ddpg_target  [target]
+//   ce_ddpg_grad    [target, gradient, reduce, statistics]
+//   ce_ddpg_step    [target, gradient, reduce, statistics, update]    (five)
+// where update is Adam on both blocks, the soft update and both images'
+// repack.  Every argument check precedes the first HIP call, and the checks of
+// the plain arguments precede the check of the handle, so they run without a
+// device.  Nothing is allocated on a call path (the targets y of a grad / step
+// call go into the caller's [n] buffer); status codes, never throws.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+
+#include "common.h"
+#include "ddpg_kernels.h"
+
+struct ce_ddpg {
+    ce_ddpg_config cfg{};
+    ce::DdpgPlan plan{};
+    int grid_max = 0;            // workgroups per branch the slab holds
+    long long t = 0;             // Adam's step count, shared by both blocks
+    size_t lds_grad = 0, lds_act = 0;
+    float *params = nullptr, *target = nullptr, *m = nullptr, *v = nullptr;
+    float *img = nullptr, *timg = nullptr;
+    float *grad = nullptr, *slab = nullptr, *scale = nullptr;
+    double *stat_slab = nullptr;
+    float *d_flat = nullptr;     // staging of a host-pointer set_params
+};
+
+namespace {
+
+using ce::fail;
+
+constexpr int64_t kMaxRows = int64_t(1) << 24;
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// shape limits and hyper-parameters (no HIP call); `who` prefixes the message
+int shape_ok(const char *who, const ce_ddpg_config *c) {
+    const std::string w(who);
+    if (!c) return fail(CE_EINVAL, w + ": null config");
+    if (c->abi_version != CE_ABI_VERSION) return fail(CE_EINVAL, w + ": ABI version mismatch");
+    if (c->obs_dim <= 0 || c->act_dim <= 0 || c->n_hidden < 0)
+        return fail(CE_EINVAL, w + ": obs_dim and act_dim must be positive");
+    if (c->n_hidden < 1 || c->n_hidden > ce::kDdpgMaxHidden)
+        return fail(CE_EUNSUPPORTED, w + ": the DDPG networks take 1 or 2 hidden layers, got " +
+                                         std::to_string(c->n_hidden));
+    if (c->obs_dim > ce::kDdpgMaxD)
+        return fail(CE_EUNSUPPORTED, w + ": obs_dim " + std::to_string(c->obs_dim) +
+                                         " exceeds the limit of 128");
+    if (c->act_dim > ce::kDdpgMaxA)
+        return fail(CE_EUNSUPPORTED, w + ": act_dim " + std::to_string(c->act_dim) +
+                                         " exceeds the limit of 64");
+    for (int l = 0; l < c->n_hidden; ++l)
+        if (c->hidden[l] != 32 && c->hidden[l] != 64)
+            return fail(CE_EUNSUPPORTED, w + ": hidden width " + std::to_string(c->hidden[l]) +
+                                             " is neither 32 nor 64");
+    return CE_OK;
+}
+
+int config_ok(const char *who, const ce_ddpg_config *c) {
+    const int rc = shape_ok(who, c);
+    if (rc != CE_OK) return rc;
+    const std::string w(who);
+    if (!(c->gamma >= 0.0 && c->gamma <= 1.0)) return fail(CE_EINVAL, w + ": gamma must be in [0, 1]");
+    if (!(c->tau >= 0.0 && c->tau <= 1.0)) return fail(CE_EINVAL, w + ": tau must be in [0, 1]");
+    if (!(c->actor_lr > 0.0) || !(c->critic_lr > 0.0))
+        return fail(CE_EINVAL, w + ": actor_lr and critic_lr must be positive");
+    if (!(c->beta1 >= 0.0 && c->beta1 < 1.0) || !(c->beta2 >= 0.0 && c->beta2 < 1.0))
+        return fail(CE_EINVAL, w + ": beta1 and beta2 must be in [0, 1)");
+    if (!(c->eps > 0.0)) return fail(CE_EINVAL, w + ": eps must be positive");
+    if (!(c->obs_lo < c->obs_hi)) return fail(CE_EINVAL, w + ": obs_lo must be below obs_hi");
+    if (c->grid_limit < 0) return fail(CE_EINVAL, w + ": grid_limit must not be negative");
+    for (int i = 0; i < c->act_dim; ++i)
+        if (!std::isfinite(c->scale[i])) return fail(CE_EINVAL, w + ": scale must be finite");
+    return CE_OK;
+}
+
+// the images' layout, the flat vector's segments and the LDS sizes
+ce::DdpgPlan make_plan(const ce_ddpg_config &c) {
+    ce::DdpgPlan a{};
+    a.D = c.obs_dim;
+    a.A = c.act_dim;
+    a.n_hidden = c.n_hidden;
+    a.obs_lo = static_cast<float>(c.obs_lo);
+    a.obs_hi = static_cast<float>(c.obs_hi);
+    int img = 0, src = 0, seg = 0, wmax = 0, kmax = 0;
+    auto add = [&](int rows, int cols, int rows_pad, int cols_pad) {
+        a.seg_dst[seg] = img;
+        a.seg_src[seg] = src;
+        a.seg_cols[seg] = cols;
+        a.seg_cols_pad[seg] = cols_pad;
+        ++seg;
+        src += rows * cols;
+        const int at = img;
+        img += rows_pad * cols_pad;
+        return at;
+    };
+    for (int net = 0; net < 2; ++net) {
+        if (net == 1) a.n_actor = src;
+        int in = c.obs_dim;
+        for (int l = 0; l <= c.n_hidden; ++l) {
+            const int out = l < c.n_hidden ? c.hidden[l] : (net == 0 ? c.act_dim : 1);
+            const int ip = round_up(in, 4), op = round_up(out, 32);
+            a.out_dim[net][l] = out;
+            a.in_pad[net][l] = ip;
+            a.out_pad[net][l] = op;
+            a.off_w[net][l] = add(in, out, ip, op);
+            a.off_b[net][l] = add(1, out, 1, op);
+            // dZ W^T reads whole 32-row chunks of the stage
+            wmax = std::max(wmax, round_up(ip, 32) * (op + 1));
+            kmax = std::max(kmax, ip);
+            in = (net == 1 && l == 0) ? out + c.act_dim : out;      // the concat
+        }
+    }
+    a.n_segs = seg;
+    a.n_params = src;
+    a.img_floats = img;
+    a.w_floats = round_up(wmax, 4);
+    a.act_floats = kmax * ce::kDdpgLd;
+    return a;
+}
+
+size_t lds_bytes(const ce::DdpgPlan &a, int bufs) {
+    const int sech2 = bufs == ce::kDdpgBufs ? a.out_pad[0][a.n_hidden] * ce::kDdpgLd : 0;
+    return static_cast<size_t>(a.w_floats + bufs * a.act_floats + ce::kDdpgRowFloats + sech2) *
+           sizeof(float);
+}
+
+int params_ok(const char *who, const ce_ddpg *l, const void *flat, int64_t n, const char *got) {
+    if (!flat) return fail(CE_EINVAL, std::string(who) + ": null parameter vector");
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
+    if (n != l->plan.n_params)
+        return fail(CE_EINVAL, std::string(who) + got + std::to_string(n) +
+                                   " parameters, the agent has " + std::to_string(l->plan.n_params));
+    return CE_OK;
+}
+
+// n rows gathered by idx (null: the first n) out of an m-row batch
+int rows_ok(const char *who, int64_t n, int64_t m, const int32_t *idx) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (n < 1) return bad(": n must be at least 1, got " + std::to_string(n));
+    if (m < 1 || m > kMaxRows) return bad(": m must be in [1, 2^24], got " + std::to_string(m));
+    if (n > kMaxRows) return bad(": n must be at most 2^24");
+    if (!idx && n > m) return bad(": n exceeds m and there is no idx to gather by");
+    return CE_OK;
+}
+
+int batch_ok(const char *who, const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx,
+             const float *obs0, const float *actions, const float *rewards, const float *obs1,
+             const uint8_t *dones, const float *y, const float *stats) {
+    const int rc = rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    const auto null = [who](const char *what) { return fail(CE_EINVAL, std::string(who) + ": null " + what); };
+    if (!obs0) return null("obs0");
+    if (!actions) return null("actions");
+    if (!rewards) return null("rewards");
+    if (!obs1) return null("obs1");
+    if (!dones) return null("dones");
+    if (!y) return null("y buffer");
+    if (!stats) return null("stats");
+    if (!l) return null("learner");
+    return CE_OK;
+}
+
+void enqueue_target(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,
+                    const float *rewards, const uint8_t *dones, float *y, hipStream_t stream) {
+    ce::DdpgTargetArgs g{};
+    g.p = l->plan;
+    g.n = static_cast<int>(n);
+    g.m = static_cast<int>(m);
+    g.gamma = static_cast<float>(l->cfg.gamma);
+    g.timg = l->timg;
+    g.idx = idx;
+    g.obs1 = obs1;
+    g.rewards = rewards;
+    g.dones = dones;
+    g.y = y;
+    const unsigned tiles = static_cast<unsigned>((n + ce::kDdpgTile - 1) / ce::kDdpgTile);
+    hipLaunchKernelGGL(ce::ddpg_target_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_grad,
+                       stream, g);
+}
+
+// [target, gradient, reduce, statistics] into y / grad / stats
+void enqueue_grad(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                  const float *actions, const float *rewards, const float *obs1,
+                  const uint8_t *dones, float *y, float *grad, float *stats, hipStream_t stream) {
+    enqueue_target(l, n, m, idx, obs1, rewards, dones, y, stream);
+    ce::DdpgGradArgs g{};
+    g.p = l->plan;
+    g.n = static_cast<int>(n);
+    g.m = static_cast<int>(m);
+    g.tiles = static_cast<int>((n + ce::kDdpgTile - 1) / ce::kDdpgTile);
+    g.grid = std::min(g.tiles, l->grid_max);
+    g.img = l->img;
+    g.idx = idx;
+    g.obs0 = obs0;
+    g.actions = actions;
+    g.y = y;
+    g.slab = l->slab;
+    g.stat_slab = l->stat_slab;
+    hipLaunchKernelGGL(ce::ddpg_grad_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock), l->lds_grad,
+                       stream, g);
+    ce::DdpgReduceArgs q{};
+    q.p = l->plan;
+    q.grid = g.grid;
+    q.slab = l->slab;
+    q.grad = grad;
+    const int np = l->plan.n_params;
+    hipLaunchKernelGGL(ce::ddpg_reduce_kernel, dim3((np + 255) / 256), dim3(256), 0, stream, q);
+    hipLaunchKernelGGL(ce::ddpg_stats_kernel, dim3(1), dim3(256), 0, stream, g.n, g.grid, np,
+                       l->plan.n_actor, l->stat_slab, grad, stats);
+}
+
+// [update] from l->grad: Adam on both blocks, one more step; soft update; images.
+// A rate below zero means the config's; zero leaves that block where it is.
+void enqueue_update(ce_ddpg *l, double actor_lr, double critic_lr, hipStream_t stream) {
+    const ce_ddpg_config &c = l->cfg;
+    const double t = static_cast<double>(++l->t);
+    const double corr = std::sqrt(1.0 - std::pow(c.beta2, t)) / (1.0 - std::pow(c.beta1, t));
+    ce::DdpgUpdateArgs u{};
+    u.p = l->plan;
+    u.lr_t_actor = static_cast<float>((actor_lr >= 0.0 ? actor_lr : c.actor_lr) * corr);
+    u.lr_t_critic = static_cast<float>((critic_lr >= 0.0 ? critic_lr : c.critic_lr) * corr);
+    u.beta1 = static_cast<float>(c.beta1);
+    u.beta2 = static_cast<float>(c.beta2);
+    u.omb1 = static_cast<float>(1.0 - c.beta1);
+    u.omb2 = static_cast<float>(1.0 - c.beta2);
+    u.eps = static_cast<float>(c.eps);
+    u.tau = static_cast<float>(c.tau);
+    u.omt = static_cast<float>(1.0 - c.tau);
+    u.grad = l->grad;
+    u.params = l->params;
+    u.target = l->target;
+    u.m = l->m;
+    u.v = l->v;
+    u.img = l->img;
+    u.timg = l->timg;
+    hipLaunchKernelGGL(ce::ddpg_update_kernel, dim3((l->plan.n_params + 255) / 256), dim3(256), 0,
+                       stream, u);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ce_ddpg_n_params(const ce_ddpg_config *cfg) {
+    const int rc = shape_ok("ce_ddpg_n_params", cfg);
+    if (rc != CE_OK) return rc;
+    return make_plan(*cfg).n_params;
+}
+
+int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out) {
+    if (!out) return fail(CE_EINVAL, "ce_ddpg_create: null output handle");
+    *out = nullptr;
+    const int rc = config_ok("ce_ddpg_create", cfg);
+    if (rc != CE_OK) return rc;
+    ce_ddpg *l = new (std::nothrow) ce_ddpg();
+    if (!l) return fail(CE_ENOMEM, "ce_ddpg_create: host allocation failed");
+    l->cfg = *cfg;
+    l->plan = make_plan(*cfg);
+    l->lds_grad = lds_bytes(l->plan, ce::kDdpgBufs);
+    l->lds_act = lds_bytes(l->plan, ce::kDdpgActBufs);
+    auto bail = [&](int code) {
+        ce_ddpg_destroy(l);
+        return code;
+    };
+    const ce::DdpgPlan &a = l->plan;
+    CE_TRY(hipSetDevice(cfg->device));
+    hipDeviceProp_t prop;
+    CE_TRY(hipGetDeviceProperties(&prop, cfg->device));
+    l->grid_max = cfg->grid_limit > 0 ? cfg->grid_limit : std::max(1, prop.multiProcessorCount);
+    // the dynamic LDS of the three tile kernels, once, from the limits' need
+    for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_kernel),
+                          reinterpret_cast<const void *>(ce::ddpg_target_kernel),
+                          reinterpret_cast<const void *>(ce::ddpg_grad_kernel)})
+        CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(ce::kDdpgMaxLdsBytes)));
+    const size_t np = static_cast<size_t>(a.n_params) * sizeof(float);
+    const size_t ni = static_cast<size_t>(a.img_floats) * sizeof(float);
+    for (float **q : {&l->params, &l->target, &l->m, &l->v, &l->grad, &l->d_flat}) {
+        CE_TRY(hipMalloc(q, np));
+        CE_TRY(hipMemset(*q, 0, np));
+    }
+    for (float **q : {&l->img, &l->timg}) {
+        CE_TRY(hipMalloc(q, ni));
+        CE_TRY(hipMemset(*q, 0, ni));       // the padding stays zero
+    }
+    CE_TRY(hipMalloc(&l->slab, static_cast<size_t>(l->grid_max) * ni));
+    CE_TRY(hipMalloc(&l->stat_slab,
+                     static_cast<size_t>(l->grid_max) * 2 * ce::kDdpgRowStats * sizeof(double)));
+    CE_TRY(hipMalloc(&l->scale, ce::kDdpgMaxA * sizeof(float)));
+    CE_TRY(hipMemcpy(l->scale, cfg->scale, ce::kDdpgMaxA * sizeof(float), hipMemcpyHostToDevice));
+    CE_TRY(hipDeviceSynchronize());
+    *out = l;
+    return CE_OK;
+}
+
+void ce_ddpg_destroy(ce_ddpg *l) {
+    if (!l) return;
+    for (void *q : {static_cast<void *>(l->params), static_cast<void *>(l->target),
+                    static_cast<void *>(l->m), static_cast<void *>(l->v),
+                    static_cast<void *>(l->img), static_cast<void *>(l->timg),
+                    static_cast<void *>(l->grad), static_cast<void *>(l->slab),
+                    static_cast<void *>(l->scale), static_cast<void *>(l->stat_slab),
+                    static_cast<void *>(l->d_flat)})
+        if (q) (void)hipFree(q);
+    delete l;
+}
+
+int ce_ddpg_set_params(ce_ddpg *l, const float *flat, int64_t n, uint32_t flags, void *hip_stream) {
+    const char *who = "ce_ddpg_set_params";
+    const int rc = params_ok(who, l, flat, n, ": got ");
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    const float *src = flat;
+    if (!dev) {
+        CE_HIP(hipMemcpyAsync(l->d_flat, flat, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        CE_HIP(hipStreamSynchronize(stream));      // `flat` may be pageable
+        src = l->d_flat;
+    }
+    const bool both = (flags & CE_DDPG_TARGET) == 0;
+    hipLaunchKernelGGL(ce::ddpg_pack_kernel, dim3((l->plan.n_params + 255) / 256), dim3(256), 0,
+                       stream, l->plan, src, both ? l->params : nullptr, l->target,
+                       both ? l->img : nullptr, l->timg);
+    CE_HIP(hipGetLastError());
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));
+    return CE_OK;
+}
+
+int ce_ddpg_get_params(ce_ddpg *l, float *flat, int64_t n, uint32_t flags, void *hip_stream) {
+    const char *who = "ce_ddpg_get_params";
+    const int rc = params_ok(who, l, flat, n, ": got room for ");
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    const float *src = (flags & CE_DDPG_TARGET) ? l->target : l->params;
+    CE_HIP(hipMemcpyAsync(flat, src, n * sizeof(float),
+                          dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));
+    return CE_OK;
+}
+
+int ce_ddpg_act(const ce_ddpg *l, const float *obs, const float *noise, int64_t rows,
+                float *action, float *env_action, void *hip_stream) {
+    const char *who = "ce_ddpg_act";
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (rows < 1 || rows > kMaxRows)
+        return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
+    if (!obs) return bad(": null obs");
+    if (!action) return bad(": null action output");
+    if (!env_action) return bad(": null env_action output");
+    if (!l) return bad(": null learner");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    ce::DdpgActArgs g{};
+    g.p = l->plan;
+    g.rows = static_cast<int>(rows);
+    g.img = l->img;
+    g.scale = l->scale;
+    g.obs = obs;
+    g.noise = noise;
+    g.action = action;
+    g.env_action = env_action;
+    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
+    hipLaunchKernelGGL(ce::ddpg_act_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
+                       static_cast<hipStream_t>(hip_stream), g);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_target(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,
+                   const float *rewards, const uint8_t *dones, float *y, void *hip_stream) {
+    const char *who = "ce_ddpg_target";
+    const int rc = rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    const auto null = [who](const char *what) { return fail(CE_EINVAL, std::string(who) + ": null " + what); };
+    if (!obs1) return null("obs1");
+    if (!rewards) return null("rewards");
+    if (!dones) return null("dones");
+    if (!y) return null("y output");
+    if (!l) return null("learner");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    enqueue_target(l, n, m, idx, obs1, rewards, dones, y, static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_grad(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                 const float *actions, const float *rewards, const float *obs1,
+                 const uint8_t *dones, float *y, float *grad, float *stats, void *hip_stream) {
+    const char *who = "ce_ddpg_grad";
+    if (!grad) return fail(CE_EINVAL, std::string(who) + ": null grad");
+    const int rc = batch_ok(who, l, n, m, idx, obs0, actions, rewards, obs1, dones, y, stats);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    enqueue_grad(l, n, m, idx, obs0, actions, rewards, obs1, dones, y, grad, stats,
+                 static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_step(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                 const float *actions, const float *rewards, const float *obs1,
+                 const uint8_t *dones, float *y, double actor_lr, double critic_lr, float *stats,
+                 void *hip_stream) {
+    const char *who = "ce_ddpg_step";
+    if (std::isnan(actor_lr) || std::isnan(critic_lr))
+        return fail(CE_EINVAL, std::string(who) + ": a learning rate is not a number");
+    const int rc = batch_ok(who, l, n, m, idx, obs0, actions, rewards, obs1, dones, y, stats);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    enqueue_grad(l, n, m, idx, obs0, actions, rewards, obs1, dones, y, l->grad, stats, stream);
+    enqueue_update(l, actor_lr, critic_lr, stream);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+}  // extern "C"

@@ -170,6 +170,42 @@ class GPUVecEnv:
         self.current_step[:] = np.where(dones, 0, ep_len)
         return result
 
+    def collect_ddpg(self, agent, memory, n_steps, noise=None):
+        """``n_steps`` closed-loop DDPG steps written straight into
+        ``memory`` (a ``custom_envs_amd.ddpg.ReplayMemory`` of ``num_envs``
+        rows per step): ``agent`` (a ``DDPGAgent``) picks every action from
+        the previous observation, starting from the one this env last
+        returned; see ``collect.run_collect_ddpg``.  ``noise``: ``[K][E][A]``
+        device tensor added to the action, or None.  The envs auto-reset: at a
+        done row ``obs1`` is the reset observation, masked by ``(1 - done)`` in
+        the target.  Returns device tensors ``env_actions [K][E][A]``,
+        ``objective``, ``accuracy``, ``episode_len`` ``[K][E]`` and
+        ``last_obs``.  An attached monitor sees the K records in order
+        afterwards."""
+        import torch
+        from custom_envs_amd.vectorize.collect import run_collect_ddpg
+        if self.monitor is not None:
+            self.monitor.check_step()
+        if getattr(self, '_ddpg_stream', None) is None:
+            self._ddpg_stream = torch.cuda.Stream(torch.device('cuda', self.engine.device))
+        keep = ('obs1', 'rewards', 'dones') if self.monitor is not None else ()
+        result, kept = run_collect_ddpg(self.engine, agent, memory, n_steps, self._last_obs, noise,
+                                        self.num_envs, self.engine.obs_dim, self.engine.act_dim,
+                                        self._ddpg_stream, keep)
+        self._last_obs = result['last_obs']
+        k = int(n_steps)
+        host = {n: v.cpu().numpy() for n, v in result.items() if n not in ('env_actions', 'last_obs')}
+        if self.monitor is not None:
+            rewards, dones, obs = (kept[n].cpu().numpy() for n in ('rewards', 'dones', 'obs1'))
+            for t in range(k):
+                infos = LazyInfos(host['objective'][t], host['accuracy'][t], rewards[t],
+                                  host['episode_len'][t])
+                self.monitor.step(rewards[t], dones[t].astype(bool), infos, obs[t])
+        last = (memory.pos - memory.rows) % memory.capacity      # the slot of step K - 1
+        dones = memory.dones[last:last + memory.rows].cpu().numpy().astype(bool)
+        self.current_step[:] = np.where(dones, 0, host['episode_len'][k - 1])
+        return result
+
     def close(self):
         if not self.closed:
             if self.monitor is not None:

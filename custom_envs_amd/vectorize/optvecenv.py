@@ -264,6 +264,43 @@ class OptVecEnv:
                 self.monitor.step(env_rewards, env_dones, infos.per_env())
         return result
 
+    def collect_ddpg(self, agent, memory, n_steps, noise=None):
+        """``n_steps`` closed-loop DDPG steps written straight into ``memory``
+        (a ``custom_envs_amd.ddpg.ReplayMemory`` of one row per (env, agent)
+        row per step); see ``GPUVecEnv.collect_ddpg``.  Returns device tensors
+        ``env_actions [K][rows][1]``, ``info [K][E][14]``, ``episode_len`` and
+        ``last_obs``.  An attached monitor sees the K records in order
+        afterwards; the step callbacks are not called.  The host path raises
+        ``NotImplementedError``; ``problem='nn'`` raises ``NativeEngineError``."""
+        if self._engine is None:
+            raise NotImplementedError('collect_ddpg() needs the engine-backed OptVecEnv (every '
+                                      'factory the same MultiOptLRs-v0 spec)')
+        import torch
+        from custom_envs_amd._native import NativeEngineError
+        from custom_envs_amd.multi_engine import NNMultiEngine
+        from custom_envs_amd.vectorize.collect import run_collect_ddpg
+        eng = self._engine
+        if isinstance(eng, NNMultiEngine):
+            raise NativeEngineError('the network problem has no K-step closed-loop form '
+                                    '(DDPGAgent.act + step_device per step)')
+        if self.monitor is not None:
+            self.monitor.check_step()
+        if getattr(self, '_ddpg_stream', None) is None:
+            self._ddpg_stream = torch.cuda.Stream(torch.device('cuda', getattr(eng, 'device', 0)))
+        keep = ('rewards', 'dones') if self.monitor is not None else ()
+        result, kept = run_collect_ddpg(eng, agent, memory, n_steps, self._last_obs, noise,
+                                        eng.rows, 3 * eng.max_history, 1, self._ddpg_stream, keep)
+        self._last_obs = result['last_obs']
+        if self.monitor is not None:
+            P = eng.n_params
+            info, lengths = result['info'].cpu().numpy(), result['episode_len'].cpu().numpy()
+            rewards, dones = kept['rewards'].cpu().numpy(), kept['dones'].cpu().numpy()
+            for t in range(int(n_steps)):
+                env_rewards, env_dones = rewards[t][::P], dones[t][::P].astype(bool)
+                infos = _RowInfos(info[t], env_rewards, env_dones, lengths[t], P, {})
+                self.monitor.step(env_rewards, env_dones, infos.per_env())
+        return result
+
     def get_attr(self, attr_name, indices=None):
         if self._engine is None:
             return self._host.get_attr(attr_name, indices)

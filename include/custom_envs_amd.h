@@ -660,6 +660,85 @@ int ce_a2c_combine(ce_a2c *l, int32_t world, const double *records, int64_t n_to
 int ce_a2c_apply(ce_a2c *l, int32_t world, const double *records, int64_t n_total, float lr,
                  float *stats, void *hip_stream);
 
+/* ------------------------------------------------------------------------
+ * The DDPG learner on the device (custom_envs_amd/ddpg.py states the
+ * semantics in NumPy): stable-baselines 2.x DDPG over ddpg.MlpPolicy at its
+ * defaults.  With o = min(max(obs, obs_lo), obs_hi):
+ *   actor   a = tanh(relu-MLP(o) . W_out + b_out)              in [-1, 1]^A
+ *   critic  h = relu(o W_0 + b_0); h = concat(h, action); further relu layers;
+ *           Q = h . W_out + b_out
+ *   y       = reward + gamma (1 - done1) critic'(obs1, actor'(obs1))   (targets)
+ *   critic_loss = mean((critic(obs0, action) - y)^2)    -> d / d critic
+ *   actor_loss  = -mean(critic(obs0, actor(obs0)))      -> d / d actor only
+ *   Adam (eps outside the root, no clip) on each block with its own lr and a
+ *   shared step count, then target = (1 - tau) target + tau params.
+ * The flat float32 vector is [actor | critic]:
+ *   actor  [W0[D][h0], b0, ..., W_out[h_last][A], b_out],
+ *   critic [W0[D][h0], b0, W1[h0 + A][h1], b1, ..., W_out[.][1], b_out]
+ * (row-major [in][out]; the + A rows sit on the layer after the first hidden
+ * one, W_out with a single hidden layer).  The targets use the same layout.
+ * Limits: 1..2 hidden layers, each 32 or 64 wide, obs_dim <= 128, act_dim <=
+ * 64; anything else is CE_EUNSUPPORTED.  Every argument check precedes the
+ * first HIP call; calls are stream-ordered on hip_stream, no synchronisation
+ * (host-pointer parameter copies aside) and no allocation.
+ */
+typedef struct ce_ddpg ce_ddpg;
+
+typedef struct ce_ddpg_config {
+    int32_t abi_version; /* CE_ABI_VERSION                                   */
+    int32_t device;      /* HIP device ordinal                               */
+    int32_t obs_dim;     /* D <= 128                                         */
+    int32_t act_dim;     /* A <= 64                                          */
+    int32_t n_hidden;    /* hidden layers per network, 1..2                  */
+    int32_t hidden[4];   /* their widths (32 or 64)                          */
+    int32_t grid_limit;  /* workgroups per branch of the gradient; 0: CUs    */
+    double gamma;        /* discount                                         */
+    double tau;          /* soft-update rate                                 */
+    double actor_lr;     /* Adam step size of the actor's block              */
+    double critic_lr;    /* Adam step size of the critic's block             */
+    double beta1;
+    double beta2;
+    double eps;
+    double obs_lo;       /* observation_range                                */
+    double obs_hi;
+    float scale[64];     /* env_action = action * scale, [A]                 */
+} ce_ddpg_config;
+
+#define CE_DDPG_TARGET 2u /* ce_ddpg_{set,get}_params: the target networks  */
+
+/* Host-only: the length of the flat parameter vector, or a negative
+ * ce_status.  No GPU. */
+int ce_ddpg_n_params(const ce_ddpg_config *cfg);
+int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out);
+void ce_ddpg_destroy(ce_ddpg *l);
+/* The online parameters, copied into the targets too (SB's initialisation);
+ * Adam's moments and step count are kept.  Flags as ce_policy_set_params;
+ * with CE_DDPG_TARGET the targets alone (a saved model's, after the online
+ * ones). */
+int ce_ddpg_set_params(ce_ddpg *l, const float *flat, int64_t n, uint32_t flags, void *hip_stream);
+/* flags: CE_PTR_DEVICE | CE_DDPG_TARGET. */
+int ce_ddpg_get_params(ce_ddpg *l, float *flat, int64_t n, uint32_t flags, void *hip_stream);
+/* One launch over obs [rows][D] (noise [rows][A] or NULL): action = a, or
+ * min(max(a + noise, -1), 1); env_action = action * scale.  Device pointers. */
+int ce_ddpg_act(const ce_ddpg *l, const float *obs, const float *noise, int64_t rows,
+                float *action, float *env_action, void *hip_stream);
+/* y [n] of the rows idx[0..n) (NULL: the first n) of an m-row batch. */
+int ce_ddpg_target(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,
+                   const float *rewards, const uint8_t *dones, float *y, void *hip_stream);
+/* grad [n_params] and stats [8] = critic_loss, actor_loss, mean Q, mean y, 0, 0,
+ * |critic grad|^2, |actor grad|^2; no update.  Four launches.  y [n]: the
+ * caller's device buffer the targets of these rows are left in. */
+int ce_ddpg_grad(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                 const float *actions, const float *rewards, const float *obs1,
+                 const uint8_t *dones, float *y, float *grad, float *stats, void *hip_stream);
+/* ce_ddpg_grad, then Adam on both blocks, the soft update and the images'
+ * repack as one more launch: five.  actor_lr / critic_lr below zero: the
+ * config's; zero: that block's parameters stay where they are. */
+int ce_ddpg_step(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                 const float *actions, const float *rewards, const float *obs1,
+                 const uint8_t *dones, float *y, double actor_lr, double critic_lr,
+                 float *stats, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,456 @@
+"""The DDPG learner on the device (ce_ddpg_*, csrc/ddpg_kernels.h) against the
+NumPy statements of custom_envs_amd/ddpg.py in float64.
+
+1. ``act`` parity at every case's shape, with and without noise: ``action``
+   within 1e-5 (max|d| / max|ref|) of ``actor_numpy``; ``env_action`` bit-equal
+   to the float32 product ``action * scale``; rows past the last tile's live
+   rows are never written (a guard row).
+2. ``target`` parity: ``y`` within 1e-5 of ``target_numpy``, with and without
+   ``idx``.
+3. Gradient parity at every case: each parameter block within 1e-5 of
+   ``loss_grad_numpy`` (max|d| / max|ref over that network's gradient|), the
+   four statistics and both gradient norms within 1e-5 relative.
+4. ``idx``: a shuffled subset of a larger batch equals the contiguous call on
+   the gathered copy bit for bit; a permutation of all rows stays in the bound.
+5. Determinism (the same call twice, bit-identical) and grid independence
+   (grid_limit 1, 2, 0 agree to the bound).
+6. Three ``step`` calls against ``train_step_numpy`` in float64 (cases 3 and
+   6, actor_lr != critic_lr): online and target parameters within 1e-5, the
+   targets bit-equal to the float32 ``soft_update_numpy`` of the device's own
+   new parameters, ``act`` follows the new image.
+7. ``collect_ddpg`` over a ring that wraps, against a second engine stepped
+   with the recorded env actions, bit for bit; an attached monitor writes the
+   rows it writes when a second env is stepped with those actions.
+8. collect -> sample -> step -> collect on 65 envs, and its bit-identical
+   replay.
+"""
+import numpy as np
+import pytest
+
+import ddpg_cases as cases
+import policy_cases as pc
+from custom_envs_amd import ddpg
+from custom_envs_amd.ddpg import STAT_NAMES, DDPGAgent, ReplayMemory
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 1e-5
+FIELDS = cases.FIELDS
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _need_gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a ROCm device')
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _cuda(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _dev(inputs):
+    return {n: _cuda(inputs[n]) for n in FIELDS}
+
+
+def _scale(A):
+    return (0.5 + np.arange(A) / 7.0).astype(np.float32)
+
+
+def _agent(case, grid_limit=None, **over):
+    """An agent at the case's parameters, its targets the perturbed copy."""
+    inputs = cases.draw_case(case)
+    _, D, hidden, A, limit = case
+    agent = DDPGAgent(D, A, hidden, scale=_scale(A),
+                      grid_limit=limit if grid_limit is None else grid_limit, **over)
+    agent.set_params(inputs['params'])
+    agent.set_params(inputs['target_params'], target_only=True)
+    return agent, inputs
+
+
+# ------------------------------------------------------------------ 1. act
+@pytest.mark.parametrize('case', cases.CASES, ids=str)
+def test_act_parity(case):
+    import torch
+    agent, inputs = _agent(case)
+    N, D, hidden, A, _ = case
+    assert np.array_equal(agent.get_params(), inputs['params'])
+    assert np.array_equal(agent.get_params(target=True), inputs['target_params'])
+    obs = _cuda(inputs['obs0'])
+    noise = np.random.RandomState(7).normal(0, 0.4, (N, A)).astype(np.float32)
+    scale = _scale(A)
+    for nz in (None, noise):
+        # one guard row behind the outputs: the kernel's tile is 32 rows
+        buf = {n: torch.full((N + 1, A), 777.0, dtype=torch.float32, device='cuda')
+               for n in ('action', 'env_action')}
+        out = agent.act(obs, None if nz is None else _cuda(nz), out={n: v[:N] for n, v in buf.items()})
+        ref = ddpg.actor_numpy(inputs['params'], inputs['obs0'], nz, hidden)
+        got = _np(out['action'])
+        err = cases.rel_err(got, ref)
+        print('act', case, 'noise' if nz is not None else 'plain', 'err %.3g' % err)
+        assert err <= BOUND
+        assert np.abs(got).max() <= 1.0
+        assert np.array_equal(_np(out['env_action']), got * scale[None, :])
+        for v in buf.values():
+            assert np.all(_np(v[N]) == 777.0)
+    alloc = agent.act(obs)
+    assert np.array_equal(_np(alloc['action']), _np(agent.act(obs)['action']))
+
+
+# --------------------------------------------------------------- 2. target
+@pytest.mark.parametrize('case', cases.CASES, ids=str)
+def test_target_parity(case):
+    agent, inputs = _agent(case)
+    N, hidden = case[0], case[2]
+    batch = _dev(inputs)
+    ref = ddpg.target_numpy(inputs['target_params'], inputs['rewards'], inputs['obs1'],
+                            inputs['dones'], cases.HP.gamma, hidden)
+    y = _np(agent.target(batch))
+    err = cases.rel_err(y, ref)
+    rs = np.random.RandomState(3)
+    idx = rs.randint(0, N, 2 * N + 3).astype(np.int32)
+    yi = _np(agent.target(batch, _cuda(idx)))
+    erri = cases.rel_err(yi, ref[idx])
+    print('target', case, 'err %.3g idx %.3g' % (err, erri))
+    assert err <= BOUND and erri <= BOUND
+    done = inputs['dones'] != 0
+    assert np.array_equal(y[done], inputs['rewards'][done])
+
+
+# ------------------------------------------------------------- 3. gradient
+def _stat_errs(got, ref_stats):
+    return {n: abs(got[n] - float(ref_stats[n])) / abs(float(ref_stats[n])) for n in STAT_NAMES}
+
+
+def _check(case, grad, stats, ref, what):
+    ref_stats, ref_grad = ref
+    errs = cases.block_errs(case, grad, ref_grad)
+    got = stats.stats()
+    serr = _stat_errs(got, ref_stats)
+    serr['critic_grad_norm'] = abs(got['critic_grad_norm'] / np.sqrt(ref_stats['critic_sq']) - 1.0)
+    serr['actor_grad_norm'] = abs(got['actor_grad_norm'] / np.sqrt(ref_stats['actor_sq']) - 1.0)
+    print(what, case, 'worst block %.3g' % max(errs.values()), errs, serr)
+    for name, err in errs.items():
+        assert err <= BOUND, (what, name, err)
+    for name, err in serr.items():
+        assert err <= BOUND, (what, name, err)
+    host = _np(stats.tensor)
+    assert host[4] == 0.0 and host[5] == 0.0
+
+
+@pytest.mark.parametrize('case', cases.CASES, ids=str)
+def test_gradient_parity(case):
+    agent, inputs = _agent(case)
+    grad, stats = agent.grad(_dev(inputs))
+    _check(case, _np(grad), stats, cases.reference(case), 'grad')
+    n_actor = agent.n_actor
+    assert np.abs(_np(grad)[:n_actor]).max() > 0 and np.abs(_np(grad)[n_actor:]).max() > 0
+
+
+# ------------------------------------------------------------------ 4. idx
+def test_idx_subset_is_bit_equal_to_the_gathered_copy():
+    case = cases.CASES[4]
+    agent, inputs = _agent(case)
+    N = case[0]
+    rs = np.random.RandomState(5)
+    idx = rs.permutation(N)[:77].astype(np.int32)
+    batch = _dev(inputs)
+    g_idx, s_idx = agent.grad(batch, _cuda(idx))
+    y_idx = agent.target(batch, _cuda(idx))
+    gathered = {n: _cuda(inputs[n][idx]) for n in FIELDS}
+    g_cp, s_cp = agent.grad(gathered)
+    assert np.array_equal(_np(g_idx), _np(g_cp))
+    assert np.array_equal(_np(s_idx.tensor), _np(s_cp.tensor))
+    assert np.array_equal(_np(y_idx), _np(agent.target(gathered)))
+    # out-of-range indices are clamped, never read out of bounds
+    wild = idx.copy()
+    wild[0], wild[1] = -5, N + 100
+    clamped = idx.copy()
+    clamped[0], clamped[1] = 0, N - 1
+    g_w, _ = agent.grad(batch, _cuda(wild))
+    g_c, _ = agent.grad(batch, _cuda(clamped))
+    assert np.array_equal(_np(g_w), _np(g_c))
+
+
+def test_idx_permutation_stays_in_the_bound():
+    case = cases.CASES[2]
+    agent, inputs = _agent(case)
+    perm = np.random.RandomState(6).permutation(case[0]).astype(np.int32)
+    grad, stats = agent.grad(_dev(inputs), _cuda(perm))
+    _check(case, _np(grad), stats, cases.reference(case), 'perm')
+
+
+# ------------------------------------------- 5. determinism, grid independence
+def test_same_call_twice_is_bit_identical():
+    case = cases.CASES[5]
+    agent, inputs = _agent(case)
+    batch = _dev(inputs)
+    g0, s0 = agent.grad(batch)
+    g1, s1 = agent.grad(batch)
+    assert np.array_equal(_np(g0), _np(g1))
+    assert np.array_equal(_np(s0.tensor), _np(s1.tensor))
+
+
+@pytest.mark.parametrize('grid_limit', [1, 2, 0])
+def test_grid_independence(grid_limit):
+    case = cases.CASES[5]
+    agent, inputs = _agent(case, grid_limit=grid_limit)
+    grad, stats = agent.grad(_dev(inputs))
+    _check(case, _np(grad), stats, cases.reference(case), 'grid %d' % grid_limit)
+
+
+# ----------------------------------------------------------------- 6. step
+@pytest.mark.parametrize('case', [cases.CASES[2], cases.CASES[5]], ids=str)
+def test_three_steps_against_the_statement(case):
+    """At the agent's default learning rates (stable-baselines': 1e-4, 1e-3).
+    The bound on the parameters is not a bound on the gradient alone: the
+    first Adam steps move an entry by lr g / (|g| + 3.2e-7), so an entry whose
+    gradient is at float32's resolution of the largest one (case 6 has one:
+    critic/w1, |g| = 1.2e-7 of max|g| = 1.17) turns a 2e-9 error of its
+    gradient into 8e-3 lr of the parameter.  Measured at case 6: 8e-6 of
+    max|param| at critic_lr = 1e-3 (the float32 NumPy statement: 3.6e-6), and
+    1.59e-5 at critic_lr = 2e-3, which is why the rates are not raised here."""
+    hyper = dict(tau=0.01, actor_lr=1e-4, critic_lr=1e-3)
+    override = dict(actor_lr=2e-4, critic_lr=5e-4)
+    agent, inputs = _agent(case, **hyper)
+    N, D, hidden, A, _ = case
+    batch = _dev(inputs)
+    p = inputs['params'].astype(np.float64)
+    tp = inputs['target_params'].astype(np.float64)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    host = cases.batch_of(inputs)
+    for t in (1, 2, 3):
+        lrs = dict(hyper)
+        if t == 3:          # the per-call override
+            lrs.update(override)
+        before_t = agent.get_params(target=True)
+        stats = agent.step(batch, **({} if t < 3 else override))
+        p, tp, m, v, ref_stats = ddpg.train_step_numpy(p, tp, m, v, t, host, agent.n_actor,
+                                                       hp=cases.HP, hidden=hidden, **lrs)
+        got_p, got_t = agent.get_params(), agent.get_params(target=True)
+        ep, et = cases.rel_err(got_p, p), cases.rel_err(got_t, tp)
+        serr = _stat_errs(stats.stats(), ref_stats)
+        print('step', t, case, 'params %.3g targets %.3g' % (ep, et), serr)
+        assert ep <= BOUND and et <= BOUND
+        assert max(serr.values()) <= BOUND
+        assert np.array_equal(got_t, ddpg.soft_update_numpy(before_t, got_p, hyper['tau']))
+    # the images follow: act and target use the new parameters
+    obs = _cuda(inputs['obs0'])
+    act = _np(agent.act(obs)['action'])
+    assert cases.rel_err(act, ddpg.actor_numpy(got_p, inputs['obs0'], hidden=hidden)) <= BOUND
+    assert cases.rel_err(act, ddpg.actor_numpy(inputs['params'], inputs['obs0'], hidden=hidden)) > BOUND
+    y = _np(agent.target(batch))
+    assert cases.rel_err(y, ddpg.target_numpy(got_t, inputs['rewards'], inputs['obs1'],
+                                              inputs['dones'], cases.HP.gamma, hidden)) <= BOUND
+    # set_params keeps Adam's state and makes the targets equal to the parameters
+    agent.set_params(_cuda(inputs['params']))
+    assert np.array_equal(agent.get_params(target=True), inputs['params'])
+    out = torch_empty(agent.n_params)
+    assert np.array_equal(_np(agent.get_params(out=out)), inputs['params'])
+
+
+def test_zero_rate_freezes_a_network_and_stats_carry_y():
+    """``actor_lr=0`` for a call leaves the actor's block bit for bit where it
+    was while the critic trains, and the other way round; the call's targets
+    are in ``Stats.y``, and batches of different sizes alternate freely."""
+    case = cases.CASES[3]
+    agent, inputs = _agent(case)
+    batch = _dev(inputs)
+    na = agent.n_actor
+    p0 = agent.get_params()
+    y = _np(agent.target(batch))
+    stats = agent.step(batch, actor_lr=0.0)
+    assert np.array_equal(_np(stats.y), y)
+    p1 = agent.get_params()
+    assert np.array_equal(p1[:na], p0[:na]) and not np.array_equal(p1[na:], p0[na:])
+    idx = _cuda(np.arange(7, dtype=np.int32))
+    small = agent.step(batch, idx, critic_lr=0.0)          # a smaller call, then the full one again
+    assert small.y.shape == (7,)
+    p2 = agent.get_params()
+    assert np.array_equal(p2[na:], p1[na:]) and not np.array_equal(p2[:na], p1[:na])
+    grad, gstats = agent.grad(batch)
+    assert np.array_equal(_np(gstats.y), _np(agent.target(batch)))
+    assert np.all(np.isfinite(_np(grad)))
+
+
+def torch_empty(n):
+    import torch
+    return torch.empty(n, dtype=torch.float32, device='cuda')
+
+
+# -------------------------------------------------------------- 7. collect
+COLLECT_HIDDEN = (64, 64)
+
+
+def _collect_env(name, num_envs):
+    """(env, a second engine with the same seeds, D, A, rows, scale)."""
+    import functools
+    rows, D, A = pc.rollout_dims(name)
+    kind, kw = pc.ROLLOUT_SHAPES[name]
+    if kind == 'optimize':
+        from custom_envs_amd.engine import OptimizeEngine
+        from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
+        features, targets = pc.rollout_dataset(name)
+        seeds = [21 + i for i in range(num_envs)]
+        env = GPUVecEnv(num_envs, data_set=(features, targets), max_steps=4, seed=seeds)
+        twin = OptimizeEngine(features, targets, num_envs=num_envs, batch_size=kw['batch_size'],
+                              max_steps=4)
+        twin.seed(seeds)
+        return env, twin, D, A, num_envs, 0.01
+    from custom_envs_amd.envs.multioptlrs import MultiOptLRs
+    from custom_envs_amd.multi_engine import MultiOptEngine
+    from custom_envs_amd.vectorize.optvecenv import OptVecEnv
+    env = OptVecEnv([functools.partial(MultiOptLRs, problem=kw['problem'], max_batches=4)
+                     for _ in range(num_envs)])
+    assert env.engine_backed
+    twin = MultiOptEngine(num_envs, kw['problem'], max_batches=4, max_history=5)
+    return env, twin, D, A, num_envs * (rows // kw['num_envs']), 0.5
+
+
+def _collect_agent(D, A, scale, seed=0):
+    rs = np.random.RandomState(900 + seed)
+    agent = DDPGAgent(D, A, COLLECT_HIDDEN, scale=scale, tau=0.01)
+    agent.set_params(ddpg.dict_to_flat(cases.draw_params(rs, D, A, COLLECT_HIDDEN),
+                                       agent.params_layout()))
+    return agent
+
+
+@pytest.mark.parametrize('name, num_envs', [('lr_two_class_f64', 3), ('multi_func4', 2)])
+def test_collect_ddpg_fills_the_ring(name, num_envs):
+    import torch
+    env, twin, D, A, rows, scale = _collect_env(name, num_envs)
+    agent = _collect_agent(D, A, scale)
+    K, cap_steps = 6, 4
+    memory = ReplayMemory(cap_steps * rows, rows, D, A)
+    noise = _cuda(np.random.RandomState(12).normal(0, 0.3, (K, rows, A)).astype(np.float32))
+    first = np.asarray(env.reset(), np.float32)
+    out = twin.alloc_device_outputs()
+    twin.reset_device(out)
+    twin.wait()
+    assert np.array_equal(_np(out['obs']), first)
+    prev_obs, t, any_done = first, 0, False
+    for k_call in (3, 3):                 # the second call continues the first and wraps
+        result = env.collect_ddpg(agent, memory, k_call, noise[t:t + k_call])
+        assert result['env_actions'].shape == (k_call, rows, A)
+        for j in range(k_call):
+            slot = slice(((t + j) % cap_steps) * rows, ((t + j) % cap_steps + 1) * rows)
+            obs0 = memory.obs0[slot]
+            assert np.array_equal(_np(obs0), prev_obs), (t + j, 'obs0')
+            again = agent.act(obs0, noise[t + j])
+            assert np.array_equal(_np(memory.actions[slot]), _np(again['action']))
+            assert np.array_equal(_np(result['env_actions'][j]), _np(again['env_action']))
+            twin.step_device(result['env_actions'][j].contiguous(), out)
+            twin.wait()
+            assert np.array_equal(_np(memory.obs1[slot]), _np(out['obs'])), (t + j, 'obs1')
+            assert np.array_equal(_np(memory.rewards[slot]), _np(out['reward']))
+            assert np.array_equal(_np(memory.dones[slot]), _np(out['done']))
+            assert np.all(np.isfinite(_np(out['obs']))) and np.all(np.isfinite(_np(out['reward'])))
+            for extra in result:
+                if extra not in ('env_actions', 'last_obs'):      # func4's info holds a NaN: bytes
+                    assert _np(result[extra][j]).tobytes() == _np(out[extra]).tobytes(), extra
+            any_done = any_done or bool(_np(out['done']).any())
+            prev_obs = _np(out['obs'])
+        t += k_call
+        assert np.array_equal(_np(result['last_obs']), prev_obs)
+        assert memory.size == min(t, cap_steps) * rows
+        assert memory.pos == (t % cap_steps) * rows
+    assert any_done                        # the rollout crossed a reset
+    assert (memory.size, memory.pos) == (cap_steps * rows, 2 * rows)
+    idx = memory.sample(32, generator=torch.Generator(device='cuda').manual_seed(1))
+    assert idx.dtype == torch.int32 and idx.is_cuda and int(idx.max()) < memory.size
+    stats = agent.step(memory.as_batch(), idx).stats()
+    assert all(np.isfinite(v) for v in stats.values())
+    env.close()
+    twin.close()
+
+
+def _mon_rows(path):
+    """The .mon.csv rows without the wall-clock column t."""
+    import csv
+    with open(path) as f:
+        lines = [line for line in f if not line.startswith('#')]
+    rows = list(csv.DictReader(lines))
+    assert rows, path
+    return [{k: v for k, v in row.items() if k != 't'} for row in rows]
+
+
+@pytest.mark.parametrize('kind', ['optimize', 'multi'])
+def test_collect_ddpg_feeds_the_monitor(kind, tmp_path):
+    """An attached monitor sees collect_ddpg's K records in order: the same
+    .mon.csv rows as stepping a second env with the recorded env actions."""
+    import functools
+    E, K = 3, 6
+    if kind == 'optimize':
+        from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
+        features, targets = pc.rollout_dataset('lr_two_class_f64')
+        rows, D, A = pc.rollout_dims('lr_two_class_f64')
+        scale = 0.01
+
+        def make_env(prefix):
+            paths = ['%s_%d' % (prefix, i) for i in range(E)]
+            return GPUVecEnv(E, data_set=(features, targets), max_steps=4, seed=[21, 22, 23],
+                             monitor=(paths, dict(info_keywords=('objective', 'accuracy'))))
+    else:
+        from custom_envs_amd.envs.multioptlrs import MultiOptLRs
+        from custom_envs_amd.utils.utils_logging import Monitor
+        from custom_envs_amd.vectorize.optvecenv import OptVecEnv
+        rows, D, A = pc.rollout_dims('multi_func')
+        scale = 0.5
+
+        def make_env(prefix):
+            fns = [functools.partial(Monitor, functools.partial(MultiOptLRs, max_batches=4),
+                                     '%s_%d' % (prefix, i)) for i in range(E)]
+            env = OptVecEnv(fns)
+            assert env.engine_backed and env.monitor is not None
+            return env
+    agent = _collect_agent(D, A, scale)
+    memory = ReplayMemory(4 * rows, rows, D, A)
+    env = make_env(str(tmp_path / 'a'))
+    env.reset()
+    result = env.collect_ddpg(agent, memory, K)
+    actions = _np(result['env_actions'])
+    env.close()
+    replay = make_env(str(tmp_path / 'b'))
+    replay.reset()
+    for t in range(K):
+        obs, _, _, _ = replay.step(actions[t])
+    assert np.array_equal(np.asarray(obs, np.float32), _np(result['last_obs']))
+    replay.close()
+    for i in range(E):
+        a, b = (_mon_rows('%s_%d.mon.csv' % (tmp_path / p, i)) for p in 'ab')
+        assert len(a) >= 1 and a == b, i
+
+
+# ------------------------------------------- 8. collect, sample, step, collect
+def _training_run():
+    import torch
+    env, twin, D, A, rows, scale = _collect_env('lr_two_class_f64', 65)
+    twin.close()
+    agent = _collect_agent(D, A, scale, seed=1)
+    memory = ReplayMemory(8 * rows, rows, D, A)
+    gen = torch.Generator(device='cuda').manual_seed(17)
+    noise = _cuda(np.random.RandomState(13).normal(0, 0.3, (8, rows, A)).astype(np.float32))
+    env.reset()
+    stats = []
+    env.collect_ddpg(agent, memory, 4, noise[:4])
+    stats.append(_np(agent.step(memory.as_batch(), memory.sample(128, generator=gen)).tensor))
+    env.collect_ddpg(agent, memory, 4, noise[4:])
+    stats.append(_np(agent.step(memory.as_batch(), memory.sample(128, generator=gen)).tensor))
+    out = [agent.get_params(), agent.get_params(target=True)] + stats
+    out += [_np(getattr(memory, n)) for n in FIELDS]
+    env.close()
+    return out
+
+
+def test_collect_sample_step_collect_replays_bit_identically():
+    first, second = _training_run(), _training_run()
+    for a, b in zip(first, second):
+        assert np.all(np.isfinite(a.astype(np.float64)))
+        assert np.array_equal(a, b)
+    assert not np.array_equal(first[0], first[1])          # the targets trail the parameters
+    assert first[2][6] > 0 and first[2][7] > 0
