@@ -576,18 +576,32 @@ __device__ __forceinline__ float log_pos(float q) { return __logf(q); }
 // on the table's last entry, not one past it.  20 instructions with a
 // dependent depth of 13 against log_pos's 55 in one chain; within 1.5 ulp
 // for |log x| >= 0.5 and 1.3e-16 absolute below (tests/test_log_table.py).
-__device__ __forceinline__ double log_pos_tab(double x, const double *tab) {
-    constexpr double kH = kLn2Hi / kLrExpTab, kL = kLn2Lo / kLrExpTab;
+// In two stages, so a caller can issue the head (the frexp pair, v_log_f32,
+// the index, the table read and 2048 ex - j) ahead of other work and take the
+// tail (z, the polynomial, the split ln 2) once the LDS read has landed: the
+// same operations in the same order, log_pos_tab(x) = tail(head(x)).
+struct LogTabHead {
+    double m, t;            // the mantissa and its reduction factor T[j]
+    int n;                  // 2048 ex - j
+};
+__device__ __forceinline__ LogTabHead log_pos_tab_head(double x, const double *tab) {
     const int ex = __builtin_amdgcn_frexp_exp(x);
     const double m = __builtin_amdgcn_frexp_mant(x);
     const float lf = __builtin_amdgcn_logf(static_cast<float>(m));      // log2(m) in [-1, 0]
     const float sh = fmaf(lf, -static_cast<float>(kLrExpTab - 1), 0x1.8p23f);
     const int j = __float_as_int(sh) & (kLrExpTab - 1);
-    const double z = fma(m, tab[j], -1.0);
+    return LogTabHead{m, tab[j], (ex << kLrExpBits) - j};
+}
+__device__ __forceinline__ double log_pos_tab_tail(const LogTabHead &hd) {
+    constexpr double kH = kLn2Hi / kLrExpTab, kL = kLn2Lo / kLrExpTab;
+    const double z = fma(hd.m, hd.t, -1.0);
     const double q = fma(fma(z, -0.25, 1.0 / 3.0), z, -0.5);
     const double lp = fma(z * z, q, z);
-    const double n = static_cast<double>((ex << kLrExpBits) - j);
+    const double n = static_cast<double>(hd.n);
     return fma(n, kH, fma(n, kL, lp));
+}
+__device__ __forceinline__ double log_pos_tab(double x, const double *tab) {
+    return log_pos_tab_tail(log_pos_tab_head(x, tab));
 }
 
 // Two-class rows are stored pre-multiplied by s_y = +1 (y = 0) or -1 (y = 1)

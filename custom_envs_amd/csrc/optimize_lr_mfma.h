@@ -107,6 +107,21 @@ typedef double lr_d4 __attribute__((ext_vector_type(4)));
 #define CE_LR_RCPB 1
 #endif
 
+//  CE_LR_MISS_SHR the argmax miss count as a shift register: the sign bit of
+//                 u's high word is shifted into a 32-bit accumulator
+//                 (v_alignbit_b32, one instruction per value) and counted
+//                 with one popcount where the hits are formed, instead of a
+//                 shift and an add per value
+#ifndef CE_LR_MISS_SHR
+#define CE_LR_MISS_SHR 1
+#endif
+//  CE_LR_TIE_HI   the tie prefilter min |u| on the high words: in the batched
+//                 and the clamp-free body one v_min3_f32 with abs modifiers
+//                 covers two values, instead of one v_min_f64 per value
+#ifndef CE_LR_TIE_HI
+#define CE_LR_TIE_HI 1
+#endif
+
 constexpr int kLrEnvs = 16;                    // envs per workgroup (MFMA N)
 
 // plain or write-through (CE_LR_WT) stores of 4- and 8-byte values
@@ -228,14 +243,33 @@ __device__ __forceinline__ void lr_exp_neg(double (&a)[Q], const double *tab) {
 #endif
 }
 
-// The argmax hit of a row by the sign bit of u (two integer operations per
-// row instead of an f64 compare and a carry add): u > 0 and "sign clear"
-// differ only at u = +0, a tie (|u| < 2^-52) that the exact re-walk after the
-// row loop settles with lr_hit, the same test.  lr_miss is 1 for a row that
-// is not a hit or not a real row (a padding row); hits = rows - misses.
-__device__ __forceinline__ unsigned lr_miss(double u, bool valid) {
-    const unsigned hi = static_cast<unsigned>(static_cast<unsigned long long>(__double_as_longlong(u)) >> 32);
-    return valid ? hi >> 31 : 1u;
+// The argmax hit of a row by the sign bit of u (integer operations on the
+// high word instead of an f64 compare and a carry add): u > 0 and "sign
+// clear" differ only at u = +0, a tie (|u| < 2^-52) that the exact re-walk
+// after the row loop settles with lr_hit, the same test.  A row that is not a
+// hit, or not a real row (a padding row), is a miss; hits = rows - misses.
+// The misses of a lane are a shift register of sign bits (CE_LR_MISS_SHR):
+// lr_miss_add shifts one value's in, lr_miss_count is the popcount.  The
+// register holds kLrMissBits values: the K-step kernels see at most 32 per
+// lane and step (8 tiles), the one-step kernel counts and restarts it.
+constexpr int kLrMissBits = 32;
+__device__ __forceinline__ unsigned lr_hi32(double u) {
+    return static_cast<unsigned>(static_cast<unsigned long long>(__double_as_longlong(u)) >> 32);
+}
+__device__ __forceinline__ void lr_miss_add(unsigned &miss, double u, bool valid) {
+    const unsigned hi = lr_hi32(u);
+#if CE_LR_MISS_SHR
+    miss = __builtin_amdgcn_alignbit(miss, valid ? hi : 0x80000000u, 31);
+#else
+    miss += valid ? hi >> 31 : 1u;
+#endif
+}
+__device__ __forceinline__ int lr_miss_count(unsigned miss) {
+#if CE_LR_MISS_SHR
+    return __popc(miss);
+#else
+    return static_cast<int>(miss);
+#endif
 }
 __device__ __forceinline__ int lr_hit(double u) { return __double_as_longlong(u) >= 0 ? 1 : 0; }
 
@@ -247,6 +281,32 @@ __device__ __forceinline__ double lr_log(double x, const double *tab) {
 #else
     (void)tab;
     return log_pos(x);
+#endif
+}
+
+// The same logarithm in two stages (log_pos_tab_head / _tail): the head holds
+// the table read, the tail the arithmetic.  Without the table the head only
+// keeps x.
+struct LrLogHead {
+#if CE_LR_TLOG && CE_LR_TEXP
+    LogTabHead h;
+#else
+    double x;
+#endif
+};
+__device__ __forceinline__ LrLogHead lr_log_head(double x, const double *tab) {
+#if CE_LR_TLOG && CE_LR_TEXP
+    return LrLogHead{log_pos_tab_head(x, tab)};
+#else
+    (void)tab;
+    return LrLogHead{x};
+#endif
+}
+__device__ __forceinline__ double lr_log_tail(const LrLogHead &hd) {
+#if CE_LR_TLOG && CE_LR_TEXP
+    return log_pos_tab_tail(hd.h);
+#else
+    return log_pos(hd.x);
 #endif
 }
 
@@ -283,29 +343,55 @@ __device__ __forceinline__ void lr_run_tier(int tier, Rows &&rows) {
 
 // Per (row, env) after the exp, from t = e^-u and p_y = inv = 1/(1 + t): the
 // gradient weight q = t p_y, the loss factor p_y + 1e-16 into the running
-// product, min |u| (the tie flag) and the argmax miss.  A padding row
-// (valid == false) leaves every statistic alone.
+// product and the argmax miss.  A padding row (valid == false) leaves every
+// statistic alone.
 __device__ __forceinline__ void lr_post_tail(double uq, double t, double inv, bool valid, double &qo,
-                                             double &prod, double &umin, unsigned &miss) {
+                                             double &prod, unsigned &miss) {
     qo = valid ? t * inv : 0.0;
     prod *= valid ? inv + 1e-16 : 1.0;
-    // min(umin, |u|) as one v_min_f64 with the abs modifier (fmin of an MFMA
-    // result gets a canonicalising v_max_f64 first)
-    {
-        const double au = valid ? uq : 1.0;
+    lr_miss_add(miss, uq, valid);
+}
+// min |u| (the tie flag) over the four values of one tile in a lane; padding
+// rows stay out.  The flag is only ever read as umin < 2^-52, and for a
+// positive double that is hi(|u|) < 0x3CB00000 on the upper 32 bits.  In the
+// batched and the clamp-free body |u| < 650, so every high word is the bit
+// pattern of an ordinary (or denormal) float32 number and bit order is
+// float32 order: one v_min3_f32 with abs modifiers covers two values
+// (CE_LR_TIE_HI), and umin is kept as that high word over a zero low word (a
+// float32 denormal flush only moves it towards zero, which still flags).
+// The clamped body (NaN, infinite and huge weights: a high word can be a
+// float32 NaN pattern, and a signalling one would poison the minimum) keeps
+// one v_min_f64 with the abs modifier per value (fmin of an MFMA result gets
+// a canonicalising v_max_f64 first).
+template <int TIER>
+__device__ __forceinline__ void lr_tie4(const lr_d4 &u, const bool (&valid)[4], double &umin) {
+#if CE_LR_TIE_HI
+    if constexpr (TIER != kLrClamped) {
+        unsigned hw[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hw[i] = valid[i] ? lr_hi32(u[i]) : 0x3ff00000u;
+        unsigned hm = lr_hi32(umin);
+        asm("v_min3_f32 %0, %1, |%2|, |%3|" : "=v"(hm) : "v"(hm), "v"(hw[0]), "v"(hw[1]));
+        asm("v_min3_f32 %0, %1, |%2|, |%3|" : "=v"(hm) : "v"(hm), "v"(hw[2]), "v"(hw[3]));
+        umin = __hiloint2double(static_cast<int>(hm), 0);
+        return;
+    }
+#endif
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double au = valid[i] ? u[i] : 1.0;
         asm("v_min_f64 %0, %1, |%2|" : "=v"(umin) : "v"(umin), "v"(au));
     }
-    miss += lr_miss(uq, valid);
 }
 // one value: its own reciprocal (the free and the clamped body)
 __device__ __forceinline__ void lr_post(double uq, double t, bool valid, double &qo, double &prod,
-                                        double &umin, unsigned &miss) {
+                                        unsigned &miss) {
 #if CE_LR_RCP1
     const double inv = rcp_newton1(1.0 + t);
 #else
     const double inv = rcp_unit(1.0 + t);
 #endif
-    lr_post_tail(uq, t, inv, valid, qo, prod, umin, miss);
+    lr_post_tail(uq, t, inv, valid, qo, prod, miss);
 }
 // the four values of one tile in a lane (the forward's four C registers),
 // one reciprocal between them (the batched body): with d_i = 1 + t_i and
@@ -328,7 +414,7 @@ __device__ __forceinline__ void lr_post(double uq, double t, bool valid, double 
 #define CE_LR_RCPB_NEWTON 2
 #endif
 __device__ __forceinline__ void lr_post4(const lr_d4 &u, const double (&t)[4], const bool (&valid)[4],
-                                         double (&qo)[4], double &prod, double &umin, unsigned &miss) {
+                                         double (&qo)[4], double &prod, unsigned &miss) {
     const double d0 = 1.0 + t[0], d1 = 1.0 + t[1], d2 = 1.0 + t[2], d3 = 1.0 + t[3];
     const double ab = d0 * d1, cd = d2 * d3;
     const double p = ab * cd;
@@ -344,7 +430,7 @@ __device__ __forceinline__ void lr_post4(const lr_d4 &u, const double (&t)[4], c
 #endif
     const double inv[4] = {rab * d1, rab * d0, rcd * d3, rcd * d2};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) lr_post_tail(u[i], t[i], inv[i], valid[i], qo[i], prod, umin, miss);
+    for (int i = 0; i < 4; ++i) lr_post_tail(u[i], t[i], inv[i], valid[i], qo[i], prod, miss);
 }
 
 // sum of an int over lanes l, l^16, l^32, l^48 (permlane swaps)
@@ -572,6 +658,7 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     unsigned miss = 0;
     int rows_seen = 0;
     int since = 0;
+    [[maybe_unused]] int mbits = 0, missed = 0;         // values in the miss register, misses counted out of it
     // two-class softmax of TwoClassModel per (row, env) in its signed form:
     // u = s_y z, t = e^-u, p_y = 1/(1+t), q = 1 - p_y = t p_y (the gradient
     // weight) -- no per-row selects.  Argmax hit = u > 0 except on a tie
@@ -599,14 +686,13 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
 #pragma unroll
             for (int i = 0; i < QC; ++i) {
                 if constexpr (TIER == kLrBatched) t4[q0 + i] = tx[i];
-                else lr_post(u[q0 + i], tx[i], !PAD || ys[q0 + i] >= 0, qv[q0 + i], prod, umin, miss);
+                else lr_post(u[q0 + i], tx[i], !PAD || ys[q0 + i] >= 0, qv[q0 + i], prod, miss);
             }
         }
-        if constexpr (TIER == kLrBatched) {
-            const bool valid[4] = {!PAD || ys[0] >= 0, !PAD || ys[1] >= 0, !PAD || ys[2] >= 0,
-                                   !PAD || ys[3] >= 0};
-            lr_post4(u, t4, valid, qv, prod, umin, miss);
-        }
+        const bool valid[4] = {!PAD || ys[0] >= 0, !PAD || ys[1] >= 0, !PAD || ys[2] >= 0,
+                               !PAD || ys[3] >= 0};
+        if constexpr (TIER == kLrBatched) lr_post4(u, t4, valid, qv, prod, miss);
+        lr_tie4<TIER>(u, valid, umin);
     };
     auto forward = [&](const double (&xv)[NKF]) {
         lr_d4 u = {0.0, 0.0, 0.0, 0.0};
@@ -650,6 +736,16 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     for (int t = t_first; t < ntiles; t += NT * kLrWaves) {
         since += NT;
         rows_seen += 4 * NT;
+#if CE_LR_MISS_SHR
+        // the miss register holds 32 values: counted and restarted before a
+        // group that would not fit (uniform: every second group of 4 tiles)
+        mbits += 4 * NT;
+        if (mbits > kLrMissBits) {
+            missed += lr_miss_count(miss);
+            miss = 0;
+            mbits = 4 * NT;
+        }
+#endif
         if (since > 4) {                                // 16 factors in (1e-16, 1]: fold
             nlog -= lr_log(prod, tab);
             prod = 1.0;
@@ -688,7 +784,7 @@ __global__ __launch_bounds__(LrShape<W>::kBlock) void optimize_lr_mfma_kernel(
     // a tie (p0 == p1) is np.argmax's class 0: hit iff y == 0.  Only a wave
     // that saw |u| < 2^-52 re-walks its tiles with the exact test e^-|u| == 1
     // (practically never).
-    int hits = rows_seen - static_cast<int>(miss);
+    int hits = rows_seen - missed - lr_miss_count(miss);
     if (__any(umin < 0x1p-52)) {
         for (int t = wave; t < ntiles; t += kLrWaves) {
             double fv[NKF];

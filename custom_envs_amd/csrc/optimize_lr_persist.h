@@ -62,6 +62,15 @@ constexpr int kLpMaxTpw = 8;                  // row tiles a wave keeps in regis
 #ifndef CE_LP_ROW_PRIO
 #define CE_LP_ROW_PRIO 3
 #endif
+// the wave-specialised kernel issues the head of the step's loss logarithm
+// (lr_log_head: frexp, v_log_f32, the table read) right after the last
+// tile's softmax, ahead of that tile's gradient MFMAs, and takes the tail
+// after them: the one LDS latency the row wave waited out with nothing else
+// to issue (the epilogue waves are parked at the barrier then) moves under
+// ~190 cycles of MFMAs.  Same operations, same order: no bit changes.
+#ifndef CE_LP_LOG_HEAD
+#define CE_LP_LOG_HEAD 1
+#endif
 __host__ __device__ constexpr bool lp_g4(int nkf) { return CE_LP_G4 && nkf <= 3; }
 
 // Row tiles per wave for N rows over W waves: the smallest of 1, 2, 4, 8
@@ -299,11 +308,12 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
                     }
                     lr_exp_neg<QC>(tx, tab_s);                      // t = e^-u
                     if constexpr (TIER == kLrBatched) {
-                        lr_post4(u[i], tx, valid, qv, prod, umin, miss);
+                        lr_post4(u[i], tx, valid, qv, prod, miss);
                     } else {
 #pragma unroll
-                        for (int j = 0; j < QC; ++j) lr_post(u[i][j], tx[j], valid[j], qv[j], prod, umin, miss);
+                        for (int j = 0; j < QC; ++j) lr_post(u[i][j], tx[j], valid[j], qv[j], prod, miss);
                     }
+                    lr_tie4<TIER>(u[i], valid, umin);
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         sacc = __builtin_amdgcn_mfma_f64_16x16x4f64(xg[g0 + i][q], qv[q], sacc, 0, 0, 0);
@@ -313,7 +323,7 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
         lr_run_tier(tier, rows);
         // a tie (p0 == p1, |u| < 2^-52) is np.argmax's class 0: hit iff y == 0;
         // only a wave that saw one re-walks its tiles exactly (practically never)
-        int hits = 4 * TPW - static_cast<int>(miss);
+        int hits = 4 * TPW - lr_miss_count(miss);
         if (__any(umin < 0x1p-52)) {
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
@@ -630,6 +640,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             for (int g = 0; g < NKF; ++g) gacc[g] = 0.0;
             double prod = 1.0, nlog = 0.0, umin = 1.0;
             unsigned miss = 0;
+            [[maybe_unused]] LrLogHead lhead = {};          // CE_LP_LOG_HEAD: the loss log, head issued in the last tile
             auto rows = [&](auto tier_c) {
                 constexpr int TIER = decltype(tier_c)::value;
 #pragma unroll
@@ -670,12 +681,23 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                         }
                         lr_exp_neg<QC>(tx, tab_s);
                         if constexpr (TIER == kLrBatched) {
-                            lr_post4(u[i], tx, valid, qv, prod, umin, miss);
+                            lr_post4(u[i], tx, valid, qv, prod, miss);
                         } else {
 #pragma unroll
                             for (int j = 0; j < QC; ++j)
-                                lr_post(u[i][j], tx[j], valid[j], qv[j], prod, umin, miss);
+                                lr_post(u[i][j], tx[j], valid[j], qv[j], prod, miss);
                         }
+                        lr_tie4<TIER>(u[i], valid, umin);
+#if CE_LP_LOG_HEAD
+                        // the last tile: prod is final, so the loss log's head
+                        // (its table read) goes ahead of this tile's gradient
+                        // MFMAs, which cover the LDS latency; the tail follows
+                        // the row loop
+                        if (g0 + NG >= TPW && i == NG - 1) {
+                            lhead = lr_log_head(prod, tab_s);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+#endif
                         if constexpr (G4) {
                             // S[4g + m][4b + n] += X~[4q + k][4g + m] q[4q + k][4b + n]:
                             // the forward's C register q is the B operand as it stands
@@ -693,7 +715,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 }
             };
             lr_run_tier(tier, rows);
-            int hits = 4 * TPW - static_cast<int>(miss);
+            int hits = 4 * TPW - lr_miss_count(miss);
             if (__any(umin < 0x1p-52)) {
 #pragma unroll
                 for (int i = 0; i < TPW; ++i) {
@@ -713,7 +735,11 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                         if (yv[q] >= 0 && tx[q] == 1.0) hits += (yv[q] == 0 ? 1 : 0) - lr_hit(uu[q]);
                 }
             }
+#if CE_LP_LOG_HEAD
+            double lsum = nlog - lr_log_tail(lhead);
+#else
             double lsum = nlog - lr_log(prod, tab_s);
+#endif
             lsum = fold_pair<16>(lsum, lsum);
             lsum = fold_pair<32>(lsum, lsum);
             const double hsum = static_cast<double>(fold_env_lanes(hits));

@@ -81,6 +81,10 @@ COST_NS = {'mfma16': 27.6, 'mfma4': 27.6 * 0.26, 'valu64': 2.35, 'valu32': 2.0, 
 # round 6's tree (CE_LR_TLOG=0, CE_LR_RCPB=0) by the same classes: its 325
 # f64 VALU held 16 v_rcp_f64, its 138 32-bit VALU one v_log_f32
 ROUND6 = {'mfma16': 12, 'mfma4': 48, 'valu64': 309, 'valu32': 137, 'trans': 17}
+# round 9's tree (the table log, one reciprocal per four values), before the
+# miss shift register and the high-word tie prefilter
+# (profiles/r09_issue_budget.json)
+ROUND9 = {'mfma16': 12, 'mfma4': 48, 'valu64': 312, 'valu32': 123, 'trans': 5}
 
 
 def budget(counts, ops):
@@ -189,8 +193,10 @@ def main():
         if 'budget' in lp:
             keys = ('mfma16', 'mfma4', 'valu64', 'valu32', 'trans')
             r6 = {k: ROUND6[k] * COST_NS[k] * 1e-3 for k in keys}
+            r9 = {k: ROUND9[k] * COST_NS[k] * 1e-3 for k in keys}
             print('   budget, us      : ' + ' '.join('%8s' % k for k in keys) + '    total')
-            for name, n, us in (('round 6', ROUND6, r6), ('this tree', lp['budget']['counts'], lp['budget']['us'])):
+            for name, n, us in (('round 6', ROUND6, r6), ('round 9', ROUND9, r9),
+                                ('this tree', lp['budget']['counts'], lp['budget']['us'])):
                 print('   %-10s count: ' % name + ' '.join('%8d' % n[k] for k in keys))
                 print('   %-10s    us: ' % name + ' '.join('%8.3f' % us[k] for k in keys)
                       + ' %8.3f' % sum(us[k] for k in keys))
