@@ -53,6 +53,10 @@ EXPORTS = (
     'ce_ppo2_apply', 'ce_a2c_partial', 'ce_a2c_update_partial', 'ce_a2c_combine', 'ce_a2c_apply',
     'ce_ddpg_n_params', 'ce_ddpg_create', 'ce_ddpg_destroy', 'ce_ddpg_set_params',
     'ce_ddpg_get_params', 'ce_ddpg_act', 'ce_ddpg_target', 'ce_ddpg_grad', 'ce_ddpg_step',
+    'ce_rng_normal', 'ce_rng_u32', 'ce_policy_forward_rng', 'ce_rollout_policy_rng',
+    'ce_multi_rollout_policy_rng',
+    'ce_ppo2_get_opt_state', 'ce_ppo2_set_opt_state', 'ce_a2c_get_opt_state',
+    'ce_a2c_set_opt_state',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -147,6 +151,7 @@ _lib = None
 
 def _declare(lib):
     vp, i32, u32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64
+    u64 = ctypes.c_uint64
     f32, f64 = ctypes.c_float, ctypes.c_double
     sig = {
         'ce_abi_version': ([], ctypes.c_int),
@@ -254,6 +259,19 @@ def _declare(lib):
         'ce_ddpg_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_ddpg_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp],
                          ctypes.c_int),
+        'ce_rng_normal': ([vp, i32, i64, i32, i64, u64, u32, u32, vp], ctypes.c_int),
+        'ce_rng_u32': ([vp, i64, u64, u32, u32, vp], ctypes.c_int),
+        'ce_policy_forward_rng': ([vp, vp, u64, u32, u32, i64, ctypes.POINTER(CePolicyOutputs), vp],
+                                  ctypes.c_int),
+        'ce_rollout_policy_rng': ([vp, vp, i32, vp, u64, u32, u32, ctypes.POINTER(CeOutputs), i64,
+                                   ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
+        'ce_multi_rollout_policy_rng': ([vp, vp, i32, vp, u64, u32, u32,
+                                         ctypes.POINTER(CeMultiOutputs), i64,
+                                         ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
+        'ce_ppo2_get_opt_state': ([vp, vp, vp, i64, ctypes.POINTER(i64), u32, vp], ctypes.c_int),
+        'ce_ppo2_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
+        'ce_a2c_get_opt_state': ([vp, vp, vp, i64, ctypes.POINTER(i64), u32, vp], ctypes.c_int),
+        'ce_a2c_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -149,6 +149,7 @@ class A2CLearner(Learner):
     CONFIG = CeA2cConfig
     BATCH_FIELDS = BATCH_FIELDS
     STATS = Stats
+    OPT_BLOCKS = ('ms', 'mom')   # RMSProp's mean square and momentum; no counter
     _loss_grad = staticmethod(loss_grad_numpy)
 
     def __init__(self, policy, gamma=0.99, ent_coef=0.01, vf_coef=0.25, max_grad_norm=0.5,

@@ -1,0 +1,440 @@
+"""The training loop on the device: ``PPO2`` and ``A2C`` with stable-baselines
+2.x's constructor names, ``learn``, ``predict``, ``save`` and ``load``.
+
+A training script of the reference (run_multiagent_exp_single.py:30-54,
+search_optimize_hyperparam.py:33-66) changes one import line:
+
+    from custom_envs_amd.agents import PPO2, A2C, MlpPolicy
+
+``learn`` is the loop the pieces of this package were written for: per update
+one ``env.collect`` (the closed-loop rollout, ``vectorize/collect.py``) and one
+learner ``update`` (``ppo2.PPO2Learner`` / ``a2c.A2CLearner``), with every
+random number taken from the counter-based generator (``rng.DeviceRng``): the
+policy's noise is formed inside the policy kernel, the minibatch permutations
+come from the same seed, and ``predict`` has a counter of its own, so
+evaluation does not disturb training's stream.  A run is a function of
+``seed``, the env's own seeding and the hyper-parameters; ``save`` / ``load``
+carry the parameters, the optimiser's state, ``num_timesteps`` and the
+generator's position, so a resumed run continues bit for bit.
+
+What differs from stable-baselines, on purpose:
+
+* ``env`` is a ``GPUVecEnv`` or an engine-backed ``OptVecEnv``; rows are envs x
+  agents.  ``seed`` seeds the agent (initial parameters, noise,
+  permutations), not the env, which is seeded where it is built.
+* ``learn`` resets the env only when it has no observation to start from, so
+  a second ``learn`` (``reset_num_timesteps=False``) continues the episodes.
+* ``policy_kwargs`` takes ``net_arch=[dict(pi=[...], vf=[...])]`` with equal
+  widths (the device policy is two separate tanh networks of one shape).
+* ``save`` writes one ``.npz`` through ``np.savez`` (no pickle); ``load`` reads
+  that file only, not stable-baselines' own pickles.  A callable
+  ``learning_rate`` / ``cliprange`` is not stored: pass it to ``load`` again.
+* A2C's ``lr_schedule`` is ``'constant'`` or ``'linear'``.  ``'linear'``
+  follows stable-baselines' ``Scheduler`` as remembered (stable-baselines is
+  not installed where this was written, so it was not compared against it):
+  the scheduler is evaluated once per batch row, so update ``u`` (1-based)
+  uses ``lr * (1 - (u * n_batch - 1) / total_timesteps)``.
+* DDPG, ``MlpLstmPolicy``, ``explained_variance`` and ``learn`` under a
+  gradient exchange are not here.
+"""
+import json
+import os
+
+import numpy as np
+
+from custom_envs_amd import policy as _policy
+from custom_envs_amd.rng import DeviceRng
+
+
+class MlpPolicy:
+    """The marker stable-baselines scripts pass as ``policy``: the device-side
+    actor-critic MLP (``custom_envs_amd.policy.MlpPolicy``)."""
+
+
+class EnvSpec:
+    """The shape of an env without the env: what ``load`` builds a model on
+    when no env is given, and what argument checks need.  Such a model can
+    ``predict`` (with a ``device``) but not ``learn``."""
+
+    def __init__(self, rows, obs_dim, act_dim, low=None, high=None, device=None):
+        self.rows, self.obs_dim, self.act_dim = int(rows), int(obs_dim), int(act_dim)
+        self.low = None if low is None else np.broadcast_to(
+            np.asarray(low, np.float32), (self.act_dim,)).copy()
+        self.high = None if high is None else np.broadcast_to(
+            np.asarray(high, np.float32), (self.act_dim,)).copy()
+        self.device = None if device is None else int(device)
+
+
+def env_spec(env):
+    """``EnvSpec`` of a ``GPUVecEnv`` or an engine-backed ``OptVecEnv`` (rows
+    are envs x agents; widths from the env's engine, bounds from its action
+    space); an ``EnvSpec`` passes through.  Anything else: ``TypeError``."""
+    if isinstance(env, EnvSpec):
+        return env
+    from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
+    from custom_envs_amd.vectorize.optvecenv import OptVecEnv
+    if isinstance(env, GPUVecEnv):
+        eng = env.engine
+        space = env.single_action_space
+        return EnvSpec(env.num_envs, eng.obs_dim, eng.act_dim, space.low.reshape(-1),
+                       space.high.reshape(-1), eng.device)
+    if isinstance(env, OptVecEnv) and env.engine_backed:
+        eng = env._engine
+        return EnvSpec(eng.rows, 3 * eng.max_history, 1, env.action_space.low.reshape(-1),
+                       env.action_space.high.reshape(-1), getattr(eng, 'device', 0))
+    raise TypeError('env must be a GPUVecEnv or an engine-backed OptVecEnv (every factory the '
+                    'same MultiOptLRs-v0 spec), got %s' % type(env).__name__)
+
+
+def hidden_from_policy_kwargs(policy_kwargs):
+    """``net_arch=[dict(pi=[...], vf=[...])]`` -> the hidden widths (default
+    (64, 64)).  Unequal pi / vf widths, shared layers and other keys raise."""
+    if not policy_kwargs:
+        return (64, 64)
+    unknown = set(policy_kwargs) - {'net_arch'}
+    if unknown:
+        raise ValueError('policy_kwargs takes net_arch only, got %s' % sorted(unknown))
+    arch = policy_kwargs['net_arch']
+    if (not isinstance(arch, (list, tuple)) or len(arch) != 1 or not isinstance(arch[0], dict)
+            or set(arch[0]) != {'pi', 'vf'}):
+        raise ValueError('net_arch must be [dict(pi=[...], vf=[...])] (no shared layers), got %r'
+                         % (arch,))
+    pi, vf = tuple(int(h) for h in arch[0]['pi']), tuple(int(h) for h in arch[0]['vf'])
+    if pi != vf:
+        raise ValueError('the pi and vf networks must have equal widths, got pi=%s vf=%s'
+                         % (list(pi), list(vf)))
+    if not pi:
+        raise ValueError('net_arch needs at least one hidden layer')
+    return pi
+
+
+def init_params_numpy(layout, seed):
+    """The initial flat float32 parameters, a function of ``seed``:
+    orthogonal kernels as stable-baselines' ``ortho_init`` (gain sqrt 2 for
+    hidden layers, 0.01 for the mean head, 1 for the value head), zero biases,
+    ``logstd`` 0.  (The draws are NumPy's ``RandomState(seed mod 2^32)``.)"""
+    rs = np.random.RandomState(int(seed) & 0xffffffff)
+    flat = np.zeros(_policy.layout_size(layout), np.float32)
+    for name, (off, shape) in layout.items():
+        if len(shape) != 2:
+            continue
+        gain = {'pi/w_out': 0.01, 'vf/w_out': 1.0}.get(name, np.sqrt(2.0))
+        a = rs.normal(0.0, 1.0, shape)
+        u, _, vt = np.linalg.svd(a, full_matrices=False)
+        q = u if u.shape == shape else vt
+        flat[off:off + q.size] = (gain * q).astype(np.float32).reshape(-1)
+    return flat
+
+
+def linear_schedule_lr(lr, update, n_batch, total_timesteps):
+    """A2C's ``lr_schedule='linear'`` at update ``update`` (1-based); see the
+    module docstring."""
+    return float(lr) * (1.0 - (int(update) * int(n_batch) - 1) / float(total_timesteps))
+
+
+def ppo2_frac(update, n_updates):
+    """PPO2's ``frac`` at update ``update`` (1-based): 1 at the first update,
+    ``1 / n_updates`` at the last."""
+    return 1.0 - (int(update) - 1.0) / int(n_updates)
+
+
+def _constfn(value):
+    return value if callable(value) else (lambda _frac, v=float(value): v)
+
+
+class BaseAgent:
+    """What ``PPO2`` and ``A2C`` share: the env's shape, the device policy and
+    its learner, the generator, ``learn``'s loop, ``predict``, ``save`` and
+    ``load``.  A subclass gives ``LEARNER``, ``OPT_INIT``, its constructor and
+    ``_update``."""
+    LEARNER = None
+    OPT_INIT = {}                # shape-only models: block name -> fill value
+    LOG_INTERVAL = 1
+
+    def _setup(self, policy, env, kwargs, seed, verbose, policy_kwargs, learner_kwargs):
+        if policy is not MlpPolicy and policy != 'MlpPolicy':
+            raise ValueError('policy must be agents.MlpPolicy, got %r' % (policy,))
+        self.hidden = hidden_from_policy_kwargs(policy_kwargs)
+        self.spec = env_spec(env)
+        self.env = None if isinstance(env, EnvSpec) else env
+        self.kwargs = dict(kwargs, policy_kwargs=policy_kwargs, verbose=int(verbose))
+        self.verbose = int(verbose)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), 'little')
+        self.seed = int(seed)
+        self.kwargs['seed'] = self.seed
+        self.n_batch = self.spec.rows * self.n_steps
+        self.num_timesteps = 0
+        s = self.spec
+        self.policy = _policy.MlpPolicy(s.obs_dim, s.act_dim, self.hidden, low=s.low, high=s.high,
+                                        device=s.device)
+        self.learner = self.LEARNER(self.policy, **learner_kwargs)
+        self.rng = DeviceRng(self.seed, s.device)
+        self._host = None
+        flat = init_params_numpy(self.policy.params_layout(), self.seed)
+        if s.device is None:     # shape only: the state lives here
+            self._host = {'params': flat, 'opt': dict(
+                {n: np.full(flat.size, v, np.float32) for n, v in self.OPT_INIT.items()}, step=0)}
+        else:
+            self.learner.set_params(flat)
+
+    # ------------------------------------------------------------- the state
+    def get_parameters(self):
+        """The flat float32 parameters (``policy.params_layout``), numpy."""
+        if self._host is not None:
+            return self._host['params'].copy()
+        return self.learner.get_params()
+
+    def set_parameters(self, flat):
+        flat = np.ascontiguousarray(flat, np.float32).reshape(-1)
+        if flat.size != self.policy.n_params:
+            raise ValueError('got %d parameters, the policy has %d'
+                             % (flat.size, self.policy.n_params))
+        if self._host is not None:
+            self._host['params'] = flat.copy()
+        else:
+            self.learner.set_params(flat)
+
+    def get_opt_state(self):
+        if self._host is not None:
+            return {k: (v.copy() if hasattr(v, 'copy') else v)
+                    for k, v in self._host['opt'].items()}
+        return self.learner.get_opt_state()
+
+    def set_opt_state(self, state):
+        if self._host is not None:
+            a, b, step = self.learner.check_opt_state(state)
+            names = self.learner.OPT_BLOCKS
+            self._host['opt'] = {names[0]: a.copy(), names[1]: b.copy(), 'step': step}
+        else:
+            self.learner.set_opt_state(state)
+
+    # ------------------------------------------------------------------ learn
+    def check_learn(self, total_timesteps):
+        """``n_updates`` of a ``learn(total_timesteps)`` call (no GPU)."""
+        total = int(total_timesteps)
+        if total < self.n_batch:
+            raise ValueError('total_timesteps = %d is less than one batch (rows * n_steps = %d)'
+                             % (total, self.n_batch))
+        return total // self.n_batch
+
+    def learn(self, total_timesteps, callback=None, log_interval=None, reset_num_timesteps=True):
+        """``total_timesteps // (rows * n_steps)`` updates; see the module
+        docstring.  ``callback(locals_, globals_)`` runs after each update
+        (``locals_`` holds at least ``self`` and ``update``); a return value
+        of exactly ``False`` ends the loop, and an exception propagates with
+        the env and the model consistent (the update is complete).  Statistics
+        are read back only on logging updates with ``verbose >= 1``.  Returns
+        ``self``."""
+        n_updates = self.check_learn(total_timesteps)
+        total_timesteps = int(total_timesteps)
+        if self.env is None:
+            raise RuntimeError('learn() needs an env: this model was loaded without one '
+                               '(load(path, env=...))')
+        log_interval = self.LOG_INTERVAL if log_interval is None else int(log_interval)
+        if reset_num_timesteps:
+            self.num_timesteps = 0
+        env = self.env
+        if getattr(env, '_last_obs', None) is None:
+            env.reset()
+        for update in range(1, n_updates + 1):
+            stats = self._update(env, update, n_updates, total_timesteps)
+            self.num_timesteps += self.n_batch
+            if self.verbose >= 1 and log_interval > 0 and (update % log_interval == 0
+                                                           or update == 1):
+                self._log(update, stats)
+            if callback is not None:
+                if callback(locals(), globals()) is False:
+                    break
+        return self
+
+    def _log(self, update, stats):
+        last = stats[-1] if isinstance(stats, (list, tuple)) else stats
+        print('| update %d | timesteps %d |' % (update, self.num_timesteps))
+        for key, value in last.stats().items():
+            print('| %-12s | %-12.5g |' % (key, value))
+
+    # ---------------------------------------------------------------- predict
+    def predict(self, observation, state=None, mask=None, deterministic=False):
+        """``(actions, None)``: the policy's action for ``observation``
+        (numpy or a device tensor, ``[rows][D]`` or ``[D]``), clipped to the
+        action space; numpy in, numpy out.  Stochastic draws use the
+        generator's ``PREDICT`` stream and its own counter."""
+        import torch
+        if self.policy._h is None:
+            raise RuntimeError('predict() needs a device: this model holds the shape only')
+        dev = torch.device('cuda', self.policy.device)
+        as_numpy = not torch.is_tensor(observation)
+        if as_numpy:
+            obs = torch.from_numpy(np.ascontiguousarray(observation, dtype=np.float32)).to(dev)
+        else:
+            obs = observation.to(dev, torch.float32).contiguous()
+        single = obs.dim() == 1
+        if single:
+            obs = obs[None]
+        if obs.dim() != 2 or obs.shape[1] != self.spec.obs_dim:
+            raise ValueError('observation must have shape [rows][%d] or [%d], got %s'
+                             % (self.spec.obs_dim, self.spec.obs_dim, tuple(observation.shape)))
+        noise = None if deterministic else self.rng.predict_normal(obs.shape[0], self.spec.act_dim)
+        actions = self.policy.forward_device(obs, noise)['env_action']
+        if single:
+            actions = actions[0]
+        if as_numpy:
+            actions = actions.cpu().numpy()
+        return actions, None
+
+    # ------------------------------------------------------------ save / load
+    def _meta(self):
+        kwargs = {}
+        for key, value in self.kwargs.items():
+            kwargs[key] = {'callable': True} if callable(value) else value
+        s = self.spec
+        return {'format': 1, 'algorithm': type(self).__name__, 'kwargs': kwargs,
+                'rows': s.rows, 'obs_dim': s.obs_dim, 'act_dim': s.act_dim,
+                'low': None if s.low is None else [float(v) for v in s.low],
+                'high': None if s.high is None else [float(v) for v in s.high],
+                'hidden': list(self.hidden), 'n_params': int(self.policy.n_params),
+                'opt_blocks': list(self.learner.OPT_BLOCKS)}
+
+    def save(self, save_path):
+        """One ``.npz`` (``np.savez``; a path without the suffix gets it): a
+        JSON string of the constructor arguments and shapes, the flat
+        parameters, the optimiser's state, ``num_timesteps`` and the
+        generator's state."""
+        opt = self.get_opt_state()
+        g = self.rng.state()
+        arrays = {'meta': np.array(json.dumps(self._meta())), 'params': self.get_parameters(),
+                  'opt_step': np.array(opt['step'], np.int64),
+                  'num_timesteps': np.array(self.num_timesteps, np.int64),
+                  'rng': np.array([g['seed'], g['row_offset'], g['t'], g['epoch'],
+                                   g['predict_t']], np.uint64)}
+        for name in self.learner.OPT_BLOCKS:
+            arrays['opt_' + name] = opt[name]
+        np.savez(save_path, **arrays)
+
+    @classmethod
+    def load(cls, load_path, env=None, device='auto', **overrides):
+        """The model ``save`` wrote, from a path (with or without ``.npz``) or
+        an open binary file.  ``env``: the env to go on learning with; None
+        builds the model on the saved shapes, which can ``predict`` (on
+        ``device``; ``'auto'``: cuda:0 when there is one, else the shape only)
+        but not ``learn``.  ``overrides`` replace constructor arguments (a
+        callable ``learning_rate`` / ``cliprange`` must be given again)."""
+        if isinstance(load_path, (str, os.PathLike)) and not os.path.exists(load_path) \
+                and os.path.exists(str(load_path) + '.npz'):
+            load_path = str(load_path) + '.npz'
+        with np.load(load_path, allow_pickle=False) as data:
+            data = {k: data[k] for k in data.files}
+        meta = json.loads(str(data['meta']))
+        if meta.get('algorithm') != cls.__name__:
+            raise ValueError('the file holds a %s model, not a %s'
+                             % (meta.get('algorithm'), cls.__name__))
+        kwargs = dict(meta['kwargs'])
+        kwargs.update(overrides)
+        for key, value in kwargs.items():
+            if isinstance(value, dict) and value.get('callable'):
+                raise ValueError('%s was a callable and is not stored: pass it to load()' % key)
+        if env is None:
+            if device == 'auto':
+                import torch
+                device = 0 if torch.cuda.is_available() else None
+            env = EnvSpec(meta['rows'], meta['obs_dim'], meta['act_dim'], meta['low'],
+                          meta['high'], device)
+        model = cls(MlpPolicy, env, **kwargs)
+        s = model.spec
+        if (s.obs_dim, s.act_dim, list(model.hidden)) != (meta['obs_dim'], meta['act_dim'],
+                                                          meta['hidden']):
+            raise ValueError('the env maps %d -> %d, the saved model %d -> %d (hidden %s)'
+                             % (s.obs_dim, s.act_dim, meta['obs_dim'], meta['act_dim'],
+                                meta['hidden']))
+        model.set_parameters(data['params'])
+        opt = {name: data['opt_' + name] for name in meta['opt_blocks']}
+        opt['step'] = int(data['opt_step'])
+        model.set_opt_state(opt)
+        model.num_timesteps = int(data['num_timesteps'])
+        g = [int(v) for v in data['rng']]
+        model.rng.set_state({'seed': g[0], 'row_offset': g[1], 't': g[2], 'epoch': g[3],
+                             'predict_t': g[4]})
+        model.seed = g[0]
+        return model
+
+
+class PPO2(BaseAgent):
+    """stable-baselines 2.x ``PPO2`` on the device (see the module
+    docstring).  ``learning_rate`` and ``cliprange`` are floats or callables
+    of ``frac`` (1 at the first update, falling to ``1 / n_updates``); with a
+    callable ``cliprange`` give ``cliprange_vf`` explicitly (the value clip
+    is fixed per learner)."""
+    OPT_INIT = {'m': 0.0, 'v': 0.0}
+    LOG_INTERVAL = 1
+
+    def __init__(self, policy, env, gamma=0.99, n_steps=128, ent_coef=0.01, learning_rate=2.5e-4,
+                 vf_coef=0.5, max_grad_norm=0.5, lam=0.95, nminibatches=4, noptepochs=4,
+                 cliprange=0.2, cliprange_vf=None, verbose=0, seed=None, policy_kwargs=None):
+        from custom_envs_amd.ppo2 import PPO2Learner
+        self.LEARNER = PPO2Learner
+        self.n_steps, self.nminibatches = int(n_steps), int(nminibatches)
+        self.noptepochs = int(noptepochs)
+        if self.n_steps < 1 or self.nminibatches < 1 or self.noptepochs < 1:
+            raise ValueError('n_steps, nminibatches and noptepochs must be >= 1')
+        if callable(cliprange) and cliprange_vf is None:
+            raise ValueError('a callable cliprange needs an explicit cliprange_vf (the value '
+                             'clip is fixed per learner; negative: none)')
+        self.learning_rate, self.cliprange = _constfn(learning_rate), _constfn(cliprange)
+        kwargs = dict(gamma=gamma, n_steps=self.n_steps, ent_coef=ent_coef,
+                      learning_rate=learning_rate, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+                      lam=lam, nminibatches=self.nminibatches, noptepochs=self.noptepochs,
+                      cliprange=cliprange, cliprange_vf=cliprange_vf)
+        self._setup(policy, env, kwargs, seed, verbose, policy_kwargs, dict(
+            gamma=gamma, lam=lam, cliprange=float(self.cliprange(1.0)), cliprange_vf=cliprange_vf,
+            ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+            lr=float(self.learning_rate(1.0))))
+        if self.n_batch % self.nminibatches:
+            raise ValueError('rows * n_steps = %d rows do not split into %d minibatches'
+                             % (self.n_batch, self.nminibatches))
+
+    def _update(self, env, update, n_updates, total_timesteps):
+        frac = ppo2_frac(update, n_updates)
+        result = env.collect(self.policy, self.n_steps, noise=self.rng)
+        perms = [self.rng.permutation(self.n_batch) for _ in range(self.noptepochs)]
+        return self.learner.update(result, noptepochs=self.noptepochs,
+                                   nminibatches=self.nminibatches,
+                                   lr=float(self.learning_rate(frac)),
+                                   cliprange=float(self.cliprange(frac)), perms=perms)
+
+
+class A2C(BaseAgent):
+    """stable-baselines 2.x ``A2C`` on the device (see the module docstring):
+    ``lr_schedule`` is ``'constant'`` or ``'linear'``; other schedules
+    raise."""
+    OPT_INIT = {'ms': 1.0, 'mom': 0.0}
+    LOG_INTERVAL = 100
+
+    def __init__(self, policy, env, gamma=0.99, n_steps=5, vf_coef=0.25, ent_coef=0.01,
+                 max_grad_norm=0.5, learning_rate=7e-4, alpha=0.99, epsilon=1e-5,
+                 lr_schedule='constant', verbose=0, seed=None, policy_kwargs=None):
+        from custom_envs_amd.a2c import A2CLearner
+        self.LEARNER = A2CLearner
+        self.n_steps = int(n_steps)
+        if self.n_steps < 1:
+            raise ValueError('n_steps must be >= 1')
+        if lr_schedule not in ('constant', 'linear'):
+            raise ValueError("lr_schedule must be 'constant' or 'linear', got %r" % (lr_schedule,))
+        if callable(learning_rate):
+            raise ValueError('A2C takes a float learning_rate and an lr_schedule')
+        self.lr_schedule, self.learning_rate = lr_schedule, float(learning_rate)
+        kwargs = dict(gamma=gamma, n_steps=self.n_steps, vf_coef=vf_coef, ent_coef=ent_coef,
+                      max_grad_norm=max_grad_norm, learning_rate=self.learning_rate, alpha=alpha,
+                      epsilon=epsilon, lr_schedule=lr_schedule)
+        self._setup(policy, env, kwargs, seed, verbose, policy_kwargs, dict(
+            gamma=gamma, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+            lr=self.learning_rate, alpha=alpha, eps=epsilon))
+
+    def lr_at(self, update, total_timesteps):
+        if self.lr_schedule == 'constant':
+            return self.learning_rate
+        return linear_schedule_lr(self.learning_rate, update, self.n_batch, total_timesteps)
+
+    def _update(self, env, update, n_updates, total_timesteps):
+        result = env.collect(self.policy, self.n_steps, noise=self.rng)
+        return self.learner.update(result, lr=self.lr_at(update, total_timesteps))

@@ -204,6 +204,26 @@ int ce_a2c_get_params(ce_a2c *l, float *flat, int64_t n, uint32_t flags, void *h
                                   hip_stream);
 }
 
+int ce_a2c_get_opt_state(ce_a2c *l, float *ms, float *mom, int64_t n, int64_t *step,
+                         uint32_t flags, void *hip_stream) {
+    if (!step) return fail(CE_EINVAL, "ce_a2c_get_opt_state: null step");
+    const int rc = ce::learner_opt_state("ce_a2c_get_opt_state", l ? &l->core : nullptr,
+                                         l ? l->ms : nullptr, l ? l->mom : nullptr, "ms", "mom", ms,
+                                         mom, n, false, flags, hip_stream);
+    if (rc == CE_OK) *step = 0;      // RMSProp keeps no counter
+    return rc;
+}
+
+int ce_a2c_set_opt_state(ce_a2c *l, const float *ms, const float *mom, int64_t n, int64_t step,
+                         uint32_t flags, void *hip_stream) {
+    if (step != 0)
+        return fail(CE_EINVAL, "ce_a2c_set_opt_state: RMSProp keeps no counter, step must be 0");
+    return ce::learner_opt_state("ce_a2c_set_opt_state", l ? &l->core : nullptr,
+                                 l ? l->ms : nullptr, l ? l->mom : nullptr, "ms", "mom",
+                                 const_cast<float *>(ms), const_cast<float *>(mom), n, true, flags,
+                                 hip_stream);
+}
+
 int ce_a2c_returns(const ce_a2c *l, int32_t k, int64_t rows, const float *rewards,
                    int64_t reward_stride_bytes, const uint8_t *dones, int64_t done_stride_bytes,
                    const float *last_values, float *ret, void *hip_stream) {

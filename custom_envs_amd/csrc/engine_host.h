@@ -370,13 +370,18 @@ int host_step_many_strided(E *e, int32_t k, const float *actions, int64_t stride
 }
 
 // [policy, env step] x k: step s reads the observation step s - 1 wrote
-// (obs0 first) and writes record s of `out` and `pout`.  The arguments are
-// checked before was_reset.
+// (obs0 first) and writes record s of `out` and `pout`; its noise is
+// `noise.at(s)`: the caller's block s, or draw t0 + s of the generator.  The
+// arguments are checked before was_reset.
 template <class Ops, class E, class O>
 int host_rollout_policy(const char *who, E *e, const ce_policy *p, int32_t k, const float *obs0,
-                        const float *noise, int64_t noise_stride, const O *out, int64_t out_step,
+                        const PolicyNoise &noise, const O *out, int64_t out_step,
                         const ce_policy_outputs *pout, int64_t pout_step) {
     const auto bad = [who](int code, const char *what) { return fail(code, std::string(who) + what); };
+    if (noise.generated) {      // needs no engine: checked first
+        const int rc = policy_rng_args_ok(who, k, 0, noise.t0, noise.row0);
+        if (rc != CE_OK) return rc;
+    }
     if (!e) return bad(CE_EINVAL, ": null engine");
     if (!complete(out)) return bad(CE_EINVAL, ": device outputs must all be set");
     Host<O> &h = e->host;
@@ -385,16 +390,18 @@ int host_rollout_policy(const char *who, E *e, const ce_policy *p, int32_t k, co
     int obs_dim, act_dim;
     int64_t rows;
     Ops::policy_shape(e, &obs_dim, &act_dim, &rows);
-    int rc = policy_rollout_args_ok(who, p, obs_dim, act_dim, k, obs0, noise, noise_stride, rows,
-                                    out->obs, out_step, pout, pout_step);
+    int rc = policy_rollout_args_ok(who, p, obs_dim, act_dim, k, obs0, noise.ptr, noise.stride,
+                                    rows, out->obs, out_step, pout, pout_step);
     if (rc != CE_OK) return rc;
+    if (noise.generated && (rc = policy_rng_args_ok(who, k, rows, noise.t0, noise.row0)) != CE_OK)
+        return rc;
     if (!h.was_reset) return bad(CE_ESTATE, " before the first reset()");
     CE_CLEAR_STALE_ERROR();
     const float *obs = obs0;
     for (int s = 0; s < k; ++s) {
         const ce_policy_outputs po = policy_advance(*pout, s * pout_step);
         const O eo = advance(*out, s * out_step);
-        policy_launch(p, obs, noise ? noise + s * noise_stride : nullptr, rows, po, h.stream);
+        policy_launch(p, obs, noise.at(s), rows, po, h.stream);
         if ((rc = Ops::step(e, po.env_action, eo, true)) != CE_OK) return rc;
         obs = eo.obs;
     }

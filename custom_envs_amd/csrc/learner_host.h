@@ -133,6 +133,39 @@ inline int learner_get_params(const char *who, LearnerCore *core, float *flat, i
     return CE_OK;
 }
 
+// ---- the optimiser's state in and out ----------------------------------------
+// A learner names its two [n_params] float32 blocks once (PPO2: Adam's m and
+// v; A2C: RMSProp's ms and mom) and its step counter; these copy them to
+// (`set` false) or from (`set` true) the caller's `a` and `b`: host pointers
+// (synchronises) or, under CE_PTR_DEVICE, device pointers (stream-ordered).
+// `core` null: a null learner.
+inline int learner_opt_state(const char *who, const LearnerCore *core, float *dev_a, float *dev_b,
+                             const char *name_a, const char *name_b, void *a, void *b, int64_t n,
+                             bool set, uint32_t flags, void *hip_stream) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (!a) return bad(std::string(": null ") + name_a);
+    if (!b) return bad(std::string(": null ") + name_b);
+    if (!core) return bad(": null learner");
+    if (n != core->plan.n_params)
+        return bad(": got " + std::to_string(n) + " entries per block, the policy has " +
+                   std::to_string(core->plan.n_params) + " parameters");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    const size_t bytes = static_cast<size_t>(n) * sizeof(float);
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice
+                                   : (set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    if (set) {
+        CE_HIP(hipMemcpyAsync(dev_a, a, bytes, kind, stream));
+        CE_HIP(hipMemcpyAsync(dev_b, b, bytes, kind, stream));
+    } else {
+        CE_HIP(hipMemcpyAsync(a, dev_a, bytes, kind, stream));
+        CE_HIP(hipMemcpyAsync(b, dev_b, bytes, kind, stream));
+    }
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));   // the host blocks may be pageable
+    return CE_OK;
+}
+
 // ---- argument checks --------------------------------------------------------
 
 // n rows gathered by idx (null: the first n) out of an m-row batch

@@ -250,8 +250,18 @@ int ce_multi_step_many_strided(ce_multi_engine *e, int32_t k, const float *actio
 int ce_multi_rollout_policy(ce_multi_engine *e, const ce_policy *p, int32_t k, const float *obs0,
                             const float *noise, int64_t noise_stride, const ce_multi_outputs *out,
                             int64_t out_step, const ce_policy_outputs *pout, int64_t pout_step) {
-    return ce::host_rollout_policy<MultiOps>("ce_multi_rollout_policy", e, p, k, obs0, noise,
-                                             noise_stride, out, out_step, pout, pout_step);
+    return ce::host_rollout_policy<MultiOps>("ce_multi_rollout_policy", e, p, k, obs0,
+                                             ce::PolicyNoise::block(noise, noise_stride), out,
+                                             out_step, pout, pout_step);
+}
+
+int ce_multi_rollout_policy_rng(ce_multi_engine *e, const ce_policy *p, int32_t k,
+                                const float *obs0, uint64_t seed, uint32_t t0, uint32_t row0,
+                                const ce_multi_outputs *out, int64_t out_step,
+                                const ce_policy_outputs *pout, int64_t pout_step) {
+    return ce::host_rollout_policy<MultiOps>("ce_multi_rollout_policy_rng", e, p, k, obs0,
+                                             ce::PolicyNoise::rng(seed, t0, row0), out, out_step,
+                                             pout, pout_step);
 }
 
 int ce_multi_set_persistent(ce_multi_engine *e, int32_t on) { return ce::host_set_persistent(e, on); }

@@ -12,10 +12,49 @@ namespace ce {
 // obs_dim / act_dim of a policy (no HIP call)
 void policy_dims(const ce_policy *p, int *obs_dim, int *act_dim);
 
-// Enqueue one policy_mlp_kernel launch: every pointer a device pointer, all
-// four outputs set, rows >= 1.  Arguments are NOT validated here.
-void policy_launch(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+// Where a forward's N(0,1) noise comes from: the caller's block (`ptr`
+// [rows][A], null for the deterministic policy; step s of a rollout reads
+// ptr + s * stride), or, with `generated`, rng.h's stream under `seed` at
+// draw t0 (+ s) for the global rows row0 .. row0 + rows - 1.
+struct PolicyNoise {
+    const float *ptr = nullptr;
+    int64_t stride = 0;
+    bool generated = false;
+    uint64_t seed = 0;
+    uint32_t t0 = 0, row0 = 0;
+
+    static PolicyNoise block(const float *ptr, int64_t stride) {
+        PolicyNoise n;
+        n.ptr = ptr;
+        n.stride = stride;
+        return n;
+    }
+    static PolicyNoise rng(uint64_t seed, uint32_t t0, uint32_t row0) {
+        PolicyNoise n;
+        n.generated = true;
+        n.seed = seed;
+        n.t0 = t0;
+        n.row0 = row0;
+        return n;
+    }
+    // the source of step s of a rollout
+    PolicyNoise at(int s) const {
+        PolicyNoise n = *this;
+        if (ptr) n.ptr = ptr + s * stride;
+        n.t0 = t0 + static_cast<uint32_t>(s);
+        return n;
+    }
+};
+
+// Enqueue one policy_mlp_kernel launch (the instance `noise` selects): every
+// pointer a device pointer, all four outputs set, rows >= 1.  Arguments are
+// NOT validated here.
+void policy_launch(const ce_policy *p, const float *obs, const PolicyNoise &noise, int64_t rows,
                    const ce_policy_outputs &out, hipStream_t stream);
+
+// The draws and rows of a generated-noise call (before any HIP call): draws
+// t0 .. t0 + k - 1 and rows row0 .. row0 + rows - 1 must fit 32 bits.
+int policy_rng_args_ok(const char *who, int64_t k, int64_t rows, uint32_t t0, uint32_t row0);
 
 // The argument checks the two rollout entry points share (before any HIP
 // call): null pointers, k, strides, alignment, the policy's shape against the

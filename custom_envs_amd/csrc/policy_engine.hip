@@ -119,6 +119,11 @@ void plan(ce_policy *p) {
     p->lds_bytes = static_cast<size_t>(wmax + 2 * a.act_floats) * sizeof(float);
 }
 
+// the generated instance's noise tile: 32 rows x round4(A) floats
+size_t gen_lds_bytes(int act_dim) {
+    return static_cast<size_t>(ce::kPolTile) * round_up(act_dim, 4) * sizeof(float);
+}
+
 bool complete(const ce_policy_outputs *o) {
     return o && o->action && o->env_action && o->neglogp && o->value;
 }
@@ -167,18 +172,35 @@ void policy_repack(const ce_policy *p, const float *flat, hipStream_t stream) {
                        p->img);
 }
 
-void policy_launch(const ce_policy *p, const float *obs, const float *noise, int64_t rows,
+void policy_launch(const ce_policy *p, const float *obs, const PolicyNoise &noise, int64_t rows,
                    const ce_policy_outputs &out, hipStream_t stream) {
     PolicyArgs a = p->args;
     a.rows = static_cast<int>(rows);
     a.obs = obs;
-    a.noise = noise;
+    a.noise = noise.generated ? nullptr : noise.ptr;
+    a.seed_lo = static_cast<uint32_t>(noise.seed);
+    a.seed_hi = static_cast<uint32_t>(noise.seed >> 32);
+    a.t = noise.t0;
+    a.row0 = noise.row0;
     a.action = out.action;
     a.env_action = out.env_action;
     a.neglogp = out.neglogp;
     a.value = out.value;
     const dim3 grid(static_cast<unsigned>((rows + kPolTile - 1) / kPolTile), 2);
-    hipLaunchKernelGGL(policy_mlp_kernel, grid, dim3(kPolBlock), p->lds_bytes, stream, a);
+    if (noise.generated)
+        hipLaunchKernelGGL(policy_mlp_kernel<true>, grid, dim3(kPolBlock),
+                           p->lds_bytes + gen_lds_bytes(a.A), stream, a);
+    else
+        hipLaunchKernelGGL(policy_mlp_kernel<false>, grid, dim3(kPolBlock), p->lds_bytes, stream, a);
+}
+
+int policy_rng_args_ok(const char *who, int64_t k, int64_t rows, uint32_t t0, uint32_t row0) {
+    const std::string w(who);
+    if (k > 0 && static_cast<uint64_t>(t0) + static_cast<uint64_t>(k) > (uint64_t(1) << 32))
+        return fail(CE_EINVAL, w + ": draws t0 .. t0 + k - 1 must stay below 2^32");
+    if (rows > 0 && static_cast<uint64_t>(row0) + static_cast<uint64_t>(rows) > (uint64_t(1) << 32))
+        return fail(CE_EINVAL, w + ": rows row0 .. row0 + rows - 1 must stay below 2^32");
+    return CE_OK;
 }
 
 ce_policy_outputs policy_advance(const ce_policy_outputs &o, int64_t bytes) {
@@ -235,10 +257,14 @@ int ce_policy_create(const ce_policy_config *cfg, ce_policy **out) {
         return code;
     };
     CE_TRY(hipSetDevice(cfg->device));
-    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel),
+    const size_t max_lds = (ce::kPolMaxWidth * ce::kPolMaxWidth +
+                            2 * ce::kPolMaxWidth * ce::kPolLd) * sizeof(float);
+    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<false>),
                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>((ce::kPolMaxWidth * ce::kPolMaxWidth +
-                                                 2 * ce::kPolMaxWidth * ce::kPolLd) * sizeof(float))));
+                               static_cast<int>(max_lds)));
+    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(max_lds + gen_lds_bytes(ce::kPolMaxA))));
     CE_TRY(hipMalloc(&p->img, p->img_floats * sizeof(float)));
     CE_TRY(hipMalloc(&p->d_flat, p->n_params * sizeof(float)));
     // zero parameters, unbounded actions
@@ -302,7 +328,71 @@ int ce_policy_forward(const ce_policy *p, const float *obs, const float *noise, 
     if (rows < 1 || rows > (int64_t(1) << 24))
         return fail(CE_EINVAL, "ce_policy_forward: rows must be in [1, 2^24]");
     CE_CLEAR_STALE_ERROR();
-    ce::policy_launch(p, obs, noise, rows, *out, static_cast<hipStream_t>(hip_stream));
+    ce::policy_launch(p, obs, ce::PolicyNoise::block(noise, 0), rows, *out,
+                      static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_policy_forward_rng(const ce_policy *p, const float *obs, uint64_t seed, uint32_t t,
+                          uint32_t row0, int64_t rows, const ce_policy_outputs *out,
+                          void *hip_stream) {
+    if (!p || !obs) return fail(CE_EINVAL, "ce_policy_forward_rng: null argument");
+    if (!complete(out))
+        return fail(CE_EINVAL, "ce_policy_forward_rng: policy outputs must all be set");
+    if (rows < 1 || rows > (int64_t(1) << 24))
+        return fail(CE_EINVAL, "ce_policy_forward_rng: rows must be in [1, 2^24]");
+    const int rc = ce::policy_rng_args_ok("ce_policy_forward_rng", 1, rows, t, row0);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR();
+    ce::policy_launch(p, obs, ce::PolicyNoise::rng(seed, t, row0), rows, *out,
+                      static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                  int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                  void *hip_stream) {
+    const char *who = "ce_rng_normal";
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (!out) return bad(": null output");
+    if (k < 1) return bad(": k must be at least 1, got " + std::to_string(k));
+    if (rows < 1 || rows > (int64_t(1) << 24))
+        return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
+    if (act_dim < 1 || act_dim > ce::kPolMaxA)
+        return bad(": act_dim must be in [1, 64], got " + std::to_string(act_dim));
+    if (record_stride_bytes % 4 != 0 || record_stride_bytes < rows * act_dim * 4)
+        return bad(": record_stride_bytes must be a multiple of 4 of at least rows * act_dim * 4");
+    if (reinterpret_cast<uintptr_t>(out) & 3) return bad(": the output must be 4-byte aligned");
+    const int rc = ce::policy_rng_args_ok(who, k, rows, t0, row0);
+    if (rc != CE_OK) return rc;
+    const int64_t total = int64_t(k) * rows * ((act_dim + 3) / 4);
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffff) return bad(": k * rows * act_dim is too large for one launch");
+    CE_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ce::rng_normal_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                       static_cast<hipStream_t>(hip_stream), out, static_cast<long long>(total),
+                       static_cast<int>(rows), act_dim,
+                       static_cast<long long>(record_stride_bytes / 4),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), t0, row0);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_rng_u32(uint32_t *out, int64_t n, uint64_t seed, uint32_t purpose, uint32_t t,
+               void *hip_stream) {
+    const char *who = "ce_rng_u32";
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (!out) return bad(": null output");
+    if (n < 1 || n > (int64_t(1) << 31))
+        return bad(": n must be in [1, 2^31], got " + std::to_string(n));
+    if (reinterpret_cast<uintptr_t>(out) & 3) return bad(": the output must be 4-byte aligned");
+    CE_CLEAR_STALE_ERROR();
+    const int64_t blocks = ((n + 3) / 4 + 255) / 256;
+    hipLaunchKernelGGL(ce::rng_u32_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                       static_cast<hipStream_t>(hip_stream), out, static_cast<long long>(n),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), purpose, t);
     CE_HIP(hipGetLastError());
     return CE_OK;
 }

@@ -4,7 +4,8 @@
 // separate tanh networks of the same hidden widths over the observation row,
 // a linear mean head (A values) on the first and a linear value head (1) on
 // the second, a state-independent logstd[A], and a diagonal Gaussian sample
-//   action     = mean + exp(logstd) * noise          (noise supplied, or null)
+//   action     = mean + exp(logstd) * noise          (noise supplied, or null; or
+//                                                    formed here: kGen below)
 //   env_action = min(max(action, low), high)
 //   neglogp    = 0.5 sum noise^2 + sum logstd + 0.5 A log(2 pi)
 // (neglogp from the noise itself, not from (action - mean) / std).
@@ -30,6 +31,8 @@
 
 #include <cstdint>
 
+#include "rng.h"
+
 namespace ce {
 
 constexpr int kPolBlock = 256;       // 4 waves: up to 128 output units per layer
@@ -54,18 +57,26 @@ struct PolicyArgs {
     int act_floats;                  // LDS floats of one activation buffer
     const float *img;
     const float *obs;                // [rows][D]
-    const float *noise;              // [rows][A] or null
+    const float *noise;              // [rows][A] or null (the explicit instance)
+    uint32_t seed_lo, seed_hi, t, row0;   // the generated instance: rng.h's key, draw, first row
     float *action, *env_action;      // [rows][A]
     float *neglogp, *value;          // [rows]
 };
 
 __device__ __forceinline__ int pol_acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// kGen false: the noise is a.noise (or null).  kGen true: the pi workgroup
+// (blockIdx.y == 0) forms its tile's noise once from rng.h -- every thread
+// whole Philox blocks of a row -- into an LDS block of 32 x round4(A) floats
+// behind the activation buffers, and both consumers read it there.
+template <bool kGen>
 __global__ __launch_bounds__(kPolBlock) void policy_mlp_kernel(const PolicyArgs a) {
     extern __shared__ float pol_lds[];
     float *wbuf = pol_lds;
     float *cur = wbuf + a.w_floats;
     float *nxt = cur + a.act_floats;
+    float *gen = nxt + a.act_floats;         // kGen: [32][round4(A)]
+    const int a4 = (a.A + 3) & ~3;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int li = lane & 31, h = lane >> 5;
     const int net = blockIdx.y;
@@ -84,9 +95,24 @@ __global__ __launch_bounds__(kPolBlock) void policy_mlp_kernel(const PolicyArgs 
 
     // neglogp needs no network: 8 threads per row over the noise row
     if (net == 0) {
+        if (kGen) {
+            const int nb = a4 >> 2;
+            for (int i = tid; i < live * nb; i += kPolBlock) {
+                const int r = i / nb, b = i - r * nb;
+                reinterpret_cast<float4 *>(gen)[i] =
+                    rng_normal4(a.seed_lo, a.seed_hi, a.row0 + static_cast<uint32_t>(row0 + r), a.t,
+                                static_cast<uint32_t>(b), kRngPolicy);
+            }
+            __syncthreads();                 // net is uniform over the workgroup
+        }
         const int r = tid >> 3, part = tid & 7;
         float s = 0.0f;
-        if (a.noise && r < live) {
+        if (kGen) {
+            if (r < live) {
+                const float *nz = gen + r * a4;
+                for (int c = part; c < a.A; c += 8) s += nz[c] * nz[c];
+            }
+        } else if (a.noise && r < live) {
             const float *nz = a.noise + (row0 + r) * a.A;
             for (int c = part; c < a.A; c += 8) s += nz[c] * nz[c];
         }
@@ -132,7 +158,8 @@ __global__ __launch_bounds__(kPolBlock) void policy_mlp_kernel(const PolicyArgs 
                         if (row < live) {
                             const long long o = (row0 + row) * a.A + col;
                             float act = acc[r] + bias;
-                            if (a.noise) act += sd * a.noise[o];
+                            if (kGen) act += sd * gen[row * a4 + col];
+                            else if (a.noise) act += sd * a.noise[o];
                             a.action[o] = act;
                             a.env_action[o] = act < lo ? lo : (act > hi ? hi : act);
                         }

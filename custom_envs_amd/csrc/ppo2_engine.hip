@@ -183,6 +183,27 @@ int ce_ppo2_get_params(ce_ppo2 *l, float *flat, int64_t n, uint32_t flags, void 
                                   hip_stream);
 }
 
+int ce_ppo2_get_opt_state(ce_ppo2 *l, float *m, float *v, int64_t n, int64_t *step,
+                          uint32_t flags, void *hip_stream) {
+    if (!step) return fail(CE_EINVAL, "ce_ppo2_get_opt_state: null step");
+    const int rc = ce::learner_opt_state("ce_ppo2_get_opt_state", l ? &l->core : nullptr,
+                                         l ? l->m : nullptr, l ? l->v : nullptr, "m", "v", m, v, n,
+                                         false, flags, hip_stream);
+    if (rc == CE_OK) *step = l->t;
+    return rc;
+}
+
+int ce_ppo2_set_opt_state(ce_ppo2 *l, const float *m, const float *v, int64_t n, int64_t step,
+                          uint32_t flags, void *hip_stream) {
+    if (step < 0) return fail(CE_EINVAL, "ce_ppo2_set_opt_state: step must not be negative");
+    const int rc = ce::learner_opt_state("ce_ppo2_set_opt_state", l ? &l->core : nullptr,
+                                         l ? l->m : nullptr, l ? l->v : nullptr, "m", "v",
+                                         const_cast<float *>(m), const_cast<float *>(v), n, true,
+                                         flags, hip_stream);
+    if (rc == CE_OK) l->t = step;
+    return rc;
+}
+
 int ce_ppo2_gae(const ce_ppo2 *l, int32_t k, int64_t rows, const float *rewards,
                 int64_t reward_stride_bytes, const uint8_t *dones, int64_t done_stride_bytes,
                 const float *values, int64_t value_stride_bytes, const float *last_values,

@@ -405,7 +405,9 @@ class OptimizeEngine:
         ``fields['obs'][t - 1]`` and writes ``policy_fields[...][t]``, then the
         env steps with ``policy_fields['env_action'][t]`` -- the kernel
         ``step_device`` launches -- and writes ``fields[...][t]``.  ``noise``:
-        ``[>= k][E][A]`` N(0,1) draws, or None for the deterministic policy.
+        ``[>= k][E][A]`` N(0,1) draws, None for the deterministic policy, or a
+        ``rng.DeviceRng``: step t's noise is its draw ``t + step`` formed in the
+        policy kernel (``ce_rollout_policy_rng``; the caller advances it).
         Needs the full output form.  Every tensor is validated first
         (``policy.validate_rollout``)."""
         from custom_envs_amd.policy import validate_rollout
@@ -418,6 +420,12 @@ class OptimizeEngine:
         o = self._outputs(first)
         po = policy.outputs_struct({n: policy_fields[n][0] for n in
                                     ('action', 'env_action', 'neglogp', 'value')})
+        if hasattr(noise, 'row_offset'):       # a DeviceRng (validated above)
+            check(self._lib.ce_rollout_policy_rng(
+                self._h, policy._h, int(k), obs0.data_ptr(), noise.seed, int(noise.t),
+                noise.row_offset, ctypes.byref(o), int(record_bytes), ctypes.byref(po), prec),
+                'ce_rollout_policy_rng')
+            return
         check(self._lib.ce_rollout_policy(
             self._h, policy._h, int(k), obs0.data_ptr(),
             None if noise is None else noise.data_ptr(), self.num_envs * self.act_dim,

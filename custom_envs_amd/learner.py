@@ -218,6 +218,50 @@ class Learner:
         self._call('get_params', self._h, flat.ctypes.data, flat.size, 0, self._stream(stream))
         return flat
 
+    # --------------------------------------------------------- optimiser state
+    OPT_BLOCKS = ()      # the names of the optimiser's two [n_params] blocks
+
+    def get_opt_state(self, stream=None):
+        """The optimiser's state as a dict: the two ``OPT_BLOCKS`` as new
+        float32 numpy vectors and ``step`` (an int; 0 where the optimiser
+        keeps no counter).  Synchronises.  With ``get_params`` this is all a
+        learner carries from one step to the next."""
+        a, b = (np.empty(self.n_params, np.float32) for _ in self.OPT_BLOCKS)
+        step = ctypes.c_int64(0)
+        self._call('get_opt_state', self._h, a.ctypes.data, b.ctypes.data, self.n_params,
+                   ctypes.byref(step), 0, self._stream(stream))
+        return {self.OPT_BLOCKS[0]: a, self.OPT_BLOCKS[1]: b, 'step': int(step.value)}
+
+    def check_opt_state(self, state):
+        """The form of a ``get_opt_state`` dict for this learner (no GPU):
+        returns (block, block, step)."""
+        blocks = []
+        for name in self.OPT_BLOCKS:
+            v = state.get(name) if hasattr(state, 'get') else None
+            if v is None:
+                raise ValueError('optimiser state lacks %r' % name)
+            v = np.asarray(v)
+            if v.dtype != np.float32:
+                raise ValueError('optimiser state %s must have dtype float32, got %s'
+                                 % (name, v.dtype))
+            if v.shape != (self.n_params,):
+                raise ValueError('optimiser state %s must have shape (%d,), got %s'
+                                 % (name, self.n_params, v.shape))
+            blocks.append(np.ascontiguousarray(v))
+        if state.get('step') is None:
+            raise ValueError("optimiser state lacks 'step'")
+        step = int(state['step'])
+        if step < 0:
+            raise ValueError('optimiser state step must not be negative, got %d' % step)
+        return blocks[0], blocks[1], step
+
+    def set_opt_state(self, state, stream=None):
+        """Install a ``get_opt_state`` dict (validated first).  The
+        parameters are kept."""
+        a, b, step = self.check_opt_state(state)
+        self._call('set_opt_state', self._h, a.ctypes.data, b.ctypes.data, self.n_params, step, 0,
+                   self._stream(stream))
+
     # ----------------------------------------------------------------- records
     @staticmethod
     def rollout_shape(rewards):

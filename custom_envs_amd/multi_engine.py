@@ -135,6 +135,11 @@ class MultiOptEngine:
         o = self._outputs(first)
         po = policy.outputs_struct({n: policy_fields[n][0] for n in
                                     ('action', 'env_action', 'neglogp', 'value')})
+        if hasattr(noise, 'row_offset'):       # a DeviceRng (validated above)
+            self._call('rollout_policy_rng', policy._h, int(k), obs0.data_ptr(), noise.seed,
+                       int(noise.t), noise.row_offset, ctypes.byref(o), int(record_bytes),
+                       ctypes.byref(po), prec)
+            return
         self._call('rollout_policy', policy._h, int(k), obs0.data_ptr(),
                    None if noise is None else noise.data_ptr(), self.rows, ctypes.byref(o),
                    int(record_bytes), ctypes.byref(po), prec)

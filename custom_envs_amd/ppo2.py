@@ -196,6 +196,7 @@ class PPO2Learner(Learner):
     CONFIG = CePpo2Config
     BATCH_FIELDS = BATCH_FIELDS
     STATS = Stats
+    OPT_BLOCKS = ('m', 'v')      # Adam's moments; ``step`` counts its steps
     _loss_grad = staticmethod(loss_grad_numpy)
 
     def __init__(self, policy, gamma=0.99, lam=0.95, cliprange=0.2, cliprange_vf=None,
@@ -335,11 +336,31 @@ class PPO2Learner(Learner):
                 'neglogps': result['neglogps'].reshape(-1).contiguous(),
                 'values': result['values'].reshape(-1).contiguous()}
 
+    def check_perms(self, perms, noptepochs, total):
+        """``perms``: ``noptepochs`` int32 contiguous ``[total]`` tensors (the
+        device is checked with the batch, by ``step``)."""
+        import torch
+        perms = list(perms)
+        if len(perms) != noptepochs:
+            raise ValueError('perms holds %d permutations, noptepochs is %d'
+                             % (len(perms), noptepochs))
+        for i, perm in enumerate(perms):
+            if not hasattr(perm, 'data_ptr') or perm.dtype != torch.int32:
+                raise ValueError('perms[%d] must be an int32 tensor, got %s'
+                                 % (i, getattr(perm, 'dtype', type(perm).__name__)))
+            if tuple(perm.shape) != (total,) or not perm.is_contiguous():
+                raise ValueError('perms[%d] must be contiguous with shape (%d,), got %s'
+                                 % (i, total, tuple(perm.shape)))
+        return perms
+
     def update(self, result, noptepochs=4, nminibatches=4, generator=None, lr=None,
-               cliprange=None, stream=None):
+               cliprange=None, stream=None, perms=None):
         """The whole PPO2 update of one rollout: GAE, then ``noptepochs``
         passes of ``nminibatches`` ``step`` calls over slices of one
-        ``torch.randperm`` per epoch (drawn on the device from ``generator``).
+        ``torch.randperm`` per epoch (drawn on the device from ``generator``),
+        or of ``perms[epoch]`` when ``perms`` is given: ``noptepochs`` int32
+        device permutations of the ``K * R`` rows (``rng.DeviceRng.
+        permutation``), so the split does not depend on torch's generator.
         Nothing is read back; returns the ``Stats`` of every step, in order.
         With a gradient exchange attached every rank splits its own ``K * R_r``
         rows with its own ``generator``, and ``K * R_r`` must divide by
@@ -357,6 +378,8 @@ class PPO2Learner(Learner):
         if total % nminibatches:
             raise ValueError('K * R = %d rows do not split into %d minibatches'
                              % (total, nminibatches))
+        if perms is not None:
+            perms = self.check_perms(perms, noptepochs, total)
         if self.exchange is not None:
             # decided for every rank on every rank, so none enters a
             # collective alone
@@ -378,8 +401,12 @@ class PPO2Learner(Learner):
         self.check_batch(batch)
         size = total // nminibatches
         all_stats = []
-        for _ in range(noptepochs):
-            perm = torch.randperm(total, dtype=torch.int32, device=adv.device, generator=generator)
+        for epoch in range(noptepochs):
+            if perms is not None:
+                perm = perms[epoch]
+            else:
+                perm = torch.randperm(total, dtype=torch.int32, device=adv.device,
+                                      generator=generator)
             for b in range(nminibatches):
                 all_stats.append(self.step(batch, perm[b * size:(b + 1) * size], stream=stream,
                                            lr=lr, cliprange=cliprange))

@@ -1,0 +1,230 @@
+"""The project's counter-based random numbers: Philox4x32-10 (Salmon et al.,
+Random123), stated in NumPy and bound to the device (csrc/rng.h).
+
+A run's sample stream is a pure function of ``(seed, counter)``; it does not
+belong to torch's generator, and a test can say which actions a seed must give.
+
+    key      (seed & 0xffffffff, seed >> 32) of a 64-bit seed
+    counter  (row, t, block, purpose)
+               row      the global row: the caller's ``row_offset`` + local row
+               t        the draw index (one per env step, or per epoch), < 2^32
+               block    the group of four values inside the row
+               purpose  ``POLICY`` 0, ``PERMUTATION`` 1, ``PREDICT`` 2
+    uniform  u(x) = ((x >> 8) + 0.5) * 2^-24, strictly inside (0, 1)
+    normals  r = sqrt(-2 ln u(x0)); z0 = r cospi(2 u(x1)), z1 = r sinpi(2 u(x1));
+             the same from (x2, x3) gives z2, z3, so |z| <= 5.89
+
+Column ``a`` of a row's noise is element ``a % 4`` of block ``a // 4``, so it
+does not depend on ``act_dim``.  The unsigned 32-bit stream ``u32_numpy(seed,
+purpose, t, n)`` is word ``i % 4`` of the block at counter ``(0, t, i // 4,
+purpose)``; a permutation of ``n`` is the stable argsort of that stream under
+``PERMUTATION``.
+
+The statement is evaluated in float64.  ``(n + 0.5) * 2^-24`` does not fit
+float32 once ``n = x >> 8`` reaches 2^23, so the device (float32) takes both
+``ln u`` and the angle from the distance to the far end there (``log1pf(-(1 -
+u))``, ``cospi(2 u - 2)``), whose argument is exact; it stays within a few
+float32 ulp of this statement at every ``x``.
+"""
+import ctypes
+
+import numpy as np
+
+from custom_envs_amd import _native
+from custom_envs_amd._native import check
+
+POLICY, PERMUTATION, PREDICT = 0, 1, 2
+M0, M1 = 0xD2511F53, 0xCD9E8D57
+W0, W1 = 0x9E3779B9, 0xBB67AE85
+MAX_ABS_NORMAL = 5.89
+_MASK = np.uint64(0xffffffff)
+
+
+def philox_numpy(counter, key):
+    """Philox4x32-10, vectorised: ``counter`` is four and ``key`` two uint32
+    arrays (or scalars) that broadcast together.  Returns the four result
+    words as uint32 arrays of the broadcast shape."""
+    c = [np.asarray(x, np.uint64) & _MASK for x in counter]
+    k = [np.asarray(x, np.uint64) & _MASK for x in key]
+    shape = np.broadcast(*c, *k).shape
+    c = [np.broadcast_to(x, shape).copy() for x in c]
+    k = [np.broadcast_to(x, shape).copy() for x in k]
+    for _ in range(10):
+        p0 = np.uint64(M0) * c[0]
+        p1 = np.uint64(M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _MASK,
+             (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _MASK]
+        k = [(k[0] + np.uint64(W0)) & _MASK, (k[1] + np.uint64(W1)) & _MASK]
+    return tuple(x.astype(np.uint32) for x in c)
+
+
+def seed_key(seed):
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('seed must be in [0, 2^64), got %d' % seed)
+    return seed & 0xffffffff, seed >> 32
+
+
+def uniform_numpy(x):
+    """``u(x)`` in float64: exact, and strictly inside (0, 1)."""
+    return ((np.asarray(x, np.uint32) >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+
+
+def box_muller_numpy(xa, xb):
+    r = np.sqrt(-2.0 * np.log(uniform_numpy(xa)))
+    angle = 2.0 * np.pi * uniform_numpy(xb)
+    return r * np.cos(angle), r * np.sin(angle)
+
+
+def _check_draws(t, k):
+    if t < 0 or k < 0 or t + k > 2 ** 32:
+        raise ValueError('draws t .. t + k - 1 must stay inside [0, 2^32): t = %d, k = %d' % (t, k))
+
+
+def normal_numpy(seed, t, rows, act_dim, row_offset=0, dtype=np.float64, purpose=POLICY):
+    """The ``[rows][act_dim]`` N(0,1) block of draw ``t`` for the global rows
+    ``row_offset .. row_offset + rows - 1`` (computed in float64, returned as
+    ``dtype``)."""
+    t, rows, act_dim, row_offset = int(t), int(rows), int(act_dim), int(row_offset)
+    _check_draws(t, 1)
+    if rows < 1 or act_dim < 1 or row_offset < 0 or row_offset + rows > 2 ** 32:
+        raise ValueError('rows and act_dim must be >= 1 and the rows stay below 2^32')
+    nb = (act_dim + 3) // 4
+    row = (np.arange(rows, dtype=np.uint64) + np.uint64(row_offset))[:, None]
+    block = np.arange(nb, dtype=np.uint64)[None, :]
+    x0, x1, x2, x3 = philox_numpy((row, t, block, purpose), seed_key(seed))
+    z0, z1 = box_muller_numpy(x0, x1)
+    z2, z3 = box_muller_numpy(x2, x3)
+    z = np.stack([z0, z1, z2, z3], axis=-1).reshape(rows, 4 * nb)
+    return np.ascontiguousarray(z[:, :act_dim]).astype(dtype)
+
+
+def u32_numpy(seed, purpose, t, n):
+    """``n`` unsigned 32-bit values: word ``i % 4`` of the block at counter
+    ``(0, t, i // 4, purpose)``."""
+    t, n = int(t), int(n)
+    _check_draws(t, 1)
+    if not 1 <= n <= 2 ** 31:
+        raise ValueError('n must be in [1, 2^31], got %d' % n)
+    block = np.arange((n + 3) // 4, dtype=np.uint64)
+    words = philox_numpy((0, t, block, int(purpose)), seed_key(seed))
+    return np.ascontiguousarray(np.stack(words, axis=-1).reshape(-1)[:n])
+
+
+def permutation_numpy(seed, t, n):
+    """The permutation of ``range(n)`` of epoch ``t``: the stable argsort of
+    ``u32_numpy(seed, PERMUTATION, t, n)``, int32."""
+    return np.argsort(u32_numpy(seed, PERMUTATION, t, n), kind='stable').astype(np.int32)
+
+
+class DeviceRng:
+    """The generator's position for one consumer on one GPU: ``seed``, the
+    policy-noise draw counter ``t`` (a Python int the caller may read and
+    set), an epoch counter for permutations and a counter for ``predict``.
+    Passed as ``noise=`` to ``MlpPolicy.forward_device``, ``rollout_policy``
+    and ``collect`` it makes the policy kernel form its own noise.
+    ``device=None`` gives the bookkeeping only (no GPU)."""
+
+    def __init__(self, seed, device=0, row_offset=0):
+        self.seed = int(seed)
+        seed_key(self.seed)
+        self.row_offset = int(row_offset)
+        if not 0 <= self.row_offset < 2 ** 32:
+            raise ValueError('row_offset must be in [0, 2^32), got %d' % self.row_offset)
+        self.device = None if device is None else int(device)
+        self.t = 0
+        self.epoch = 0
+        self.predict_t = 0
+
+    # ------------------------------------------------------------------ state
+    def advance(self, k):
+        k = int(k)
+        _check_draws(self.t, k)
+        self.t += k
+
+    def check_draws(self, k):
+        """``t + k <= 2^32``: the call's draws exist."""
+        _check_draws(int(self.t), int(k))
+
+    def state(self):
+        return {'seed': self.seed, 'row_offset': self.row_offset, 't': int(self.t),
+                'epoch': int(self.epoch), 'predict_t': int(self.predict_t)}
+
+    def set_state(self, state):
+        missing = [k for k in ('seed', 't', 'epoch') if k not in state]
+        if missing:
+            raise ValueError('generator state lacks %s' % missing)
+        seed, t, epoch = int(state['seed']), int(state['t']), int(state['epoch'])
+        seed_key(seed)
+        _check_draws(t, 0)
+        _check_draws(epoch, 0)
+        self.seed, self.t, self.epoch = seed, t, epoch
+        self.row_offset = int(state.get('row_offset', self.row_offset))
+        self.predict_t = int(state.get('predict_t', 0))
+
+    # ----------------------------------------------------------------- device
+    def _torch_device(self):
+        import torch
+        if self.device is None:
+            raise RuntimeError('this DeviceRng was built without a device')
+        return torch.device('cuda', self.device)
+
+    @staticmethod
+    def _stream(stream):
+        if stream is not None:
+            return ctypes.c_void_p(stream or 0)
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream or 0)
+
+    def normal(self, k, rows, act_dim, stream=None):
+        """``[k][rows][act_dim]`` float32 on the device: the policy noise of
+        draws ``t .. t + k - 1``.  Does not advance."""
+        import torch
+        k, rows, act_dim = int(k), int(rows), int(act_dim)
+        if k < 1 or rows < 1 or not 1 <= act_dim <= 64:
+            raise ValueError('k and rows must be >= 1 and act_dim in [1, 64]')
+        self.check_draws(k)
+        dev = self._torch_device()
+        out = torch.empty((k, rows, act_dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(_native.load().ce_rng_normal(out.data_ptr(), k, rows, act_dim, rows * act_dim * 4,
+                                               self.seed, int(self.t), self.row_offset,
+                                               self._stream(stream)), 'ce_rng_normal')
+        return out
+
+    def u32(self, purpose, t, n, stream=None):
+        """``u32_numpy(seed, purpose, t, n)`` on the device, as an int64 tensor
+        of the values (torch has no unsigned 32-bit sort)."""
+        import torch
+        t, n = int(t), int(n)
+        _check_draws(t, 1)
+        if not 1 <= n <= 2 ** 31:
+            raise ValueError('n must be in [1, 2^31], got %d' % n)
+        dev = self._torch_device()
+        raw = torch.empty(n, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(_native.load().ce_rng_u32(raw.data_ptr(), n, self.seed, int(purpose), t,
+                                            self._stream(stream)), 'ce_rng_u32')
+        return raw.to(torch.int64) & 0xffffffff
+
+    def permutation(self, n):
+        """The permutation of epoch ``epoch`` (``permutation_numpy``) as an
+        int32 device tensor; advances the epoch counter."""
+        import torch
+        keys = self.u32(PERMUTATION, self.epoch, n)
+        perm = torch.argsort(keys, stable=True).to(torch.int32)
+        self.epoch += 1
+        return perm
+
+    def predict_normal(self, rows, act_dim):
+        """``[rows][act_dim]`` float32 N(0,1) for a stochastic ``predict``:
+        ``normal_numpy(..., purpose=PREDICT)`` at a counter of its own,
+        evaluated on the host and uploaded (evaluation is not the hot path).
+        Advances that counter only; ``t`` and ``epoch`` are untouched."""
+        import torch
+        dev = self._torch_device()
+        _check_draws(self.predict_t, 1)
+        z = normal_numpy(self.seed, self.predict_t, rows, act_dim, self.row_offset, np.float32,
+                         PREDICT)
+        self.predict_t += 1
+        return torch.from_numpy(z).to(dev)

@@ -142,7 +142,8 @@ class GPUVecEnv:
         previous observation, starting from the one this env last returned
         (reset, step or a previous collect).  ``noise``: ``[K][E][A]`` N(0,1)
         device tensor; None draws it (one ``torch.randn``); False runs the
-        deterministic policy.  Returns device tensors: ``obs [K][E][D]`` (the
+        deterministic policy; a ``rng.DeviceRng`` has the policy kernel form
+        draws ``t .. t + K - 1`` itself and is advanced by K.  Returns device tensors: ``obs [K][E][D]`` (the
         observation each action was chosen from), ``actions``,
         ``env_actions`` (clipped, what the env read), ``values``,
         ``neglogps``, ``rewards``, ``dones``, ``last_obs``, ``last_values``

@@ -240,7 +240,8 @@ class OptVecEnv:
         """``n_steps`` closed-loop steps on the device as one engine call
         (``MultiOptEngine.rollout_policy``), one policy row per (env, agent)
         row, starting from the observation last returned; see
-        ``GPUVecEnv.collect``.  Returns device tensors ``obs [K][rows][3H]``,
+        ``GPUVecEnv.collect`` (``noise`` likewise: a tensor, None, False or a
+        ``rng.DeviceRng``).  Returns device tensors ``obs [K][rows][3H]``,
         ``actions``, ``env_actions``, ``values``, ``neglogps``, ``rewards``,
         ``dones``, ``last_obs``, ``last_values``, ``info [K][E][14]`` and
         ``episode_len``.  An attached monitor sees the K records in order

@@ -395,7 +395,8 @@ int ce_nn_get_state(ce_nn_engine *eng, float *theta, float *gprev, int32_t *step
  *   value   = tanh-MLP_vf(obs) . Wv + bv              (a separate network of
  *                                                      the same hidden widths)
  *   action  = mean + exp(logstd) * noise              (noise: caller-supplied
- *             N(0,1) block, or NULL: action = mean; there is no device RNG)
+ *             N(0,1) block, or NULL: action = mean; the *_rng entries form
+ *             it in the kernel from the counter-based generator below)
  *   env_action = min(max(action, low), high)          (what the env step reads;
  *             action stays unclipped, as SB's runner stores it)
  *   neglogp = 0.5 sum noise^2 + sum logstd + 0.5 A log(2 pi)   (from the noise
@@ -466,6 +467,43 @@ int ce_multi_rollout_policy(ce_multi_engine *eng, const ce_policy *p, int32_t k,
                             const ce_multi_outputs *out, int64_t out_step_bytes,
                             const ce_policy_outputs *pout, int64_t pout_step_bytes);
 
+/* The counter-based generator (csrc/rng.h; custom_envs_amd/rng.py states it in
+ * NumPy): Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) at the
+ * counter (row, t, block, purpose) -- the global row, the draw index, the
+ * group of four values inside the row, and a tag (0 policy noise, 1
+ * permutation keys, 2 predict).  Column a of a row's N(0,1) noise is element
+ * a % 4 of block a / 4 (Box-Muller on u(x) = ((x >> 8) + 0.5) 2^-24, so
+ * |z| <= 5.89).  Each entry below is one plain launch on hip_stream, and every
+ * argument is checked before any HIP call.
+ *
+ * ce_rng_normal: out[s][r][a], s < k, r < rows, a < act_dim (record s at
+ * out + s * record_stride_bytes; device pointer) = the policy noise (purpose
+ * 0) of global row row0 + r at draw t0 + s.  rows in [1, 2^24], act_dim in
+ * [1, 64], t0 + k <= 2^32, row0 + rows <= 2^32.
+ * ce_rng_u32: out[i], i < n <= 2^31, = word i % 4 of the block at the counter
+ * (0, t, i / 4, purpose). */
+int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                  int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                  void *hip_stream);
+int ce_rng_u32(uint32_t *out, int64_t n, uint64_t seed, uint32_t purpose, uint32_t t,
+               void *hip_stream);
+/* ce_policy_forward / ce_rollout_policy / ce_multi_rollout_policy with the
+ * noise formed inside the policy kernel instead of read from a block: row r
+ * of the call uses global row row0 + r, and step s of a rollout uses draw
+ * t0 + s.  Bit-equal to the block forms fed the output of ce_rng_normal.
+ * CE_EINVAL when t0 + k > 2^32 or row0 + rows > 2^32. */
+int ce_policy_forward_rng(const ce_policy *p, const float *obs, uint64_t seed, uint32_t t,
+                          uint32_t row0, int64_t rows, const ce_policy_outputs *out,
+                          void *hip_stream);
+int ce_rollout_policy_rng(ce_engine *eng, const ce_policy *p, int32_t k, const float *obs0,
+                          uint64_t seed, uint32_t t0, uint32_t row0, const ce_outputs *out,
+                          int64_t out_step_bytes, const ce_policy_outputs *pout,
+                          int64_t pout_step_bytes);
+int ce_multi_rollout_policy_rng(ce_multi_engine *eng, const ce_policy *p, int32_t k,
+                                const float *obs0, uint64_t seed, uint32_t t0, uint32_t row0,
+                                const ce_multi_outputs *out, int64_t out_step_bytes,
+                                const ce_policy_outputs *pout, int64_t pout_step_bytes);
+
 /* ------------------------------------------------------------------------
  * The PPO2 learner on the device (stable-baselines 2.x PPO2 over the policy
  * above; custom_envs_amd/ppo2.py states the semantics in NumPy): GAE, the
@@ -506,6 +544,15 @@ void ce_ppo2_destroy(ce_ppo2 *l);
 int ce_ppo2_set_params(ce_ppo2 *l, const float *flat, int64_t n, uint32_t flags,
                        void *hip_stream);
 int ce_ppo2_get_params(ce_ppo2 *l, float *flat, int64_t n, uint32_t flags, void *hip_stream);
+/* The optimiser's state, so that training can be resumed elsewhere: Adam's m
+ * and v ([n] float32 each, n = ce_policy_n_params; host pointers: synchronises;
+ * CE_PTR_DEVICE: device pointers, stream-ordered) and the count of Adam steps
+ * taken (`step` is always a host value).  With the parameters this is all a
+ * learner carries from one step to the next. */
+int ce_ppo2_get_opt_state(ce_ppo2 *l, float *m, float *v, int64_t n, int64_t *step,
+                          uint32_t flags, void *hip_stream);
+int ce_ppo2_set_opt_state(ce_ppo2 *l, const float *m, const float *v, int64_t n, int64_t step,
+                          uint32_t flags, void *hip_stream);
 /* adv, ret [k][rows] contiguous float32 from rewards (float32), dones (uint8)
  * and values (float32) read in place in rollout records: record t of each at
  * base + t * stride bytes (reward / value strides multiples of 4), last_values
@@ -572,6 +619,13 @@ void ce_a2c_destroy(ce_a2c *l);
  * mom are kept. */
 int ce_a2c_set_params(ce_a2c *l, const float *flat, int64_t n, uint32_t flags, void *hip_stream);
 int ce_a2c_get_params(ce_a2c *l, float *flat, int64_t n, uint32_t flags, void *hip_stream);
+/* The optimiser's state, as ce_ppo2_get_opt_state: RMSProp's mean square ms
+ * and its momentum buffer mom ([n] float32 each).  RMSProp keeps no counter:
+ * `step` comes back 0 and must be 0 when set. */
+int ce_a2c_get_opt_state(ce_a2c *l, float *ms, float *mom, int64_t n, int64_t *step,
+                         uint32_t flags, void *hip_stream);
+int ce_a2c_set_opt_state(ce_a2c *l, const float *ms, const float *mom, int64_t n, int64_t step,
+                         uint32_t flags, void *hip_stream);
 /* ret [k][rows] contiguous float32 from rewards (float32) and dones (uint8)
  * read in place in rollout records (record t at base + t * stride bytes; the
  * reward stride a multiple of 4) and last_values [rows]:
