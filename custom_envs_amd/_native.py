@@ -57,6 +57,8 @@ EXPORTS = (
     'ce_multi_rollout_policy_rng',
     'ce_ppo2_get_opt_state', 'ce_ppo2_set_opt_state', 'ce_a2c_get_opt_state',
     'ce_a2c_set_opt_state',
+    'ce_rng_normal_purpose', 'ce_rng_replay', 'ce_ddpg_act_rng', 'ce_ddpg_train',
+    'ce_ddpg_get_opt_state', 'ce_ddpg_set_opt_state',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -138,6 +140,15 @@ class CeDdpgConfig(ctypes.Structure):
         [(name, ctypes.c_double) for name in (
             'gamma', 'tau', 'actor_lr', 'critic_lr', 'beta1', 'beta2', 'eps', 'obs_lo', 'obs_hi')] +
         [('scale', ctypes.c_float * CE_DDPG_MAX_ACT)])
+
+
+CE_DDPG_NOISE_NORMAL, CE_DDPG_NOISE_OU = 0, 1
+
+
+class CeDdpgNoise(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('theta', ctypes.c_double), ('dt', ctypes.c_double),
+                ('mean', ctypes.c_float * CE_DDPG_MAX_ACT),
+                ('sigma', ctypes.c_float * CE_DDPG_MAX_ACT)]
 
 
 class CeState(ctypes.Structure):
@@ -272,6 +283,14 @@ def _declare(lib):
         'ce_ppo2_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
         'ce_a2c_get_opt_state': ([vp, vp, vp, i64, ctypes.POINTER(i64), u32, vp], ctypes.c_int),
         'ce_a2c_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
+        'ce_rng_normal_purpose': ([vp, i32, i64, i32, i64, u64, u32, u32, u32, vp], ctypes.c_int),
+        'ce_rng_replay': ([vp, i64, i64, i64, u64, u32, vp], ctypes.c_int),
+        'ce_ddpg_act_rng': ([vp, vp, i64, u64, u32, u32, ctypes.POINTER(CeDdpgNoise), vp, vp, vp,
+                             vp, vp], ctypes.c_int),
+        'ce_ddpg_train': ([vp, i32, i64, i64, u64, u32, vp, vp, vp, vp, vp, vp, vp, f64, f64, vp,
+                           vp], ctypes.c_int),
+        'ce_ddpg_get_opt_state': ([vp, vp, vp, i64, ctypes.POINTER(i64), u32, vp], ctypes.c_int),
+        'ce_ddpg_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -1,10 +1,11 @@
-"""The training loop on the device: ``PPO2`` and ``A2C`` with stable-baselines
-2.x's constructor names, ``learn``, ``predict``, ``save`` and ``load``.
+"""The training loop on the device: ``PPO2``, ``A2C`` and ``DDPG`` with
+stable-baselines 2.x's constructor names, ``learn``, ``predict``, ``save`` and
+``load``.
 
 A training script of the reference (run_multiagent_exp_single.py:30-54,
 search_optimize_hyperparam.py:33-66) changes one import line:
 
-    from custom_envs_amd.agents import PPO2, A2C, MlpPolicy
+    from custom_envs_amd.agents import PPO2, A2C, DDPG, MlpPolicy, ddpg
 
 ``learn`` is the loop the pieces of this package were written for: per update
 one ``env.collect`` (the closed-loop rollout, ``vectorize/collect.py``) and one
@@ -34,14 +35,34 @@ What differs from stable-baselines, on purpose:
   not installed where this was written, so it was not compared against it):
   the scheduler is evaluated once per batch row, so update ``u`` (1-based)
   uses ``lr * (1 - (u * n_batch - 1) / total_timesteps)``.
-* DDPG, ``MlpLstmPolicy``, ``explained_variance`` and ``learn`` under a
-  gradient exchange are not here.
+* ``MlpLstmPolicy``, ``explained_variance`` and ``learn`` under a gradient
+  exchange are not here.
+
+``DDPG(ddpg.MlpPolicy, env, ...)`` is stable-baselines' cycle: per cycle one
+``env.collect_ddpg`` of ``nb_rollout_steps`` steps into the replay memory, the
+action noise (``ddpg.NormalActionNoise`` / ``ddpg.OrnsteinUhlenbeckActionNoise``)
+formed inside the act kernel, then one ``DDPGAgent.train`` call of
+``nb_train_steps`` steps whose replay indices come from the same seed; the
+train phase is skipped while the memory holds fewer than ``batch_size``
+records.  What differs from stable-baselines there:
+
+* every env row steps every rollout step, so a cycle is ``rows *
+  nb_rollout_steps`` timesteps and ``learn`` runs ``total_timesteps //`` that
+  many cycles (SB's ``nb_epoch_cycles`` grouping is only its logging);
+* ``buffer_size`` is rounded down to a multiple of ``rows`` (a step's records
+  are one slice of the ring);
+* ``save(path, memory=True)`` also stores the replay memory; without it a
+  loaded model starts from an empty memory, as SB's does;
+* parameter noise, layer norm, observation / return normalisation, pop-art,
+  ``critic_l2_reg``, ``clip_norm``, ``reward_scale != 1``,
+  ``random_exploration``, ``eval_env`` and ``render`` raise ``ValueError``.
 """
 import json
 import os
 
 import numpy as np
 
+from custom_envs_amd import ddpg
 from custom_envs_amd import policy as _policy
 from custom_envs_amd.rng import DeviceRng
 
@@ -313,13 +334,9 @@ class BaseAgent:
         np.savez(save_path, **arrays)
 
     @classmethod
-    def load(cls, load_path, env=None, device='auto', **overrides):
-        """The model ``save`` wrote, from a path (with or without ``.npz``) or
-        an open binary file.  ``env``: the env to go on learning with; None
-        builds the model on the saved shapes, which can ``predict`` (on
-        ``device``; ``'auto'``: cuda:0 when there is one, else the shape only)
-        but not ``learn``.  ``overrides`` replace constructor arguments (a
-        callable ``learning_rate`` / ``cliprange`` must be given again)."""
+    def _read(cls, load_path, env, device, overrides):
+        """(arrays, meta, constructor kwargs, env or the saved shapes'
+        ``EnvSpec``) of a saved file of this algorithm."""
         if isinstance(load_path, (str, os.PathLike)) and not os.path.exists(load_path) \
                 and os.path.exists(str(load_path) + '.npz'):
             load_path = str(load_path) + '.npz'
@@ -340,6 +357,17 @@ class BaseAgent:
                 device = 0 if torch.cuda.is_available() else None
             env = EnvSpec(meta['rows'], meta['obs_dim'], meta['act_dim'], meta['low'],
                           meta['high'], device)
+        return data, meta, kwargs, env
+
+    @classmethod
+    def load(cls, load_path, env=None, device='auto', **overrides):
+        """The model ``save`` wrote, from a path (with or without ``.npz``) or
+        an open binary file.  ``env``: the env to go on learning with; None
+        builds the model on the saved shapes, which can ``predict`` (on
+        ``device``; ``'auto'``: cuda:0 when there is one, else the shape only)
+        but not ``learn``.  ``overrides`` replace constructor arguments (a
+        callable ``learning_rate`` / ``cliprange`` must be given again)."""
+        data, meta, kwargs, env = cls._read(load_path, env, device, overrides)
         model = cls(MlpPolicy, env, **kwargs)
         s = model.spec
         if (s.obs_dim, s.act_dim, list(model.hidden)) != (meta['obs_dim'], meta['act_dim'],
@@ -438,3 +466,265 @@ class A2C(BaseAgent):
     def _update(self, env, update, n_updates, total_timesteps):
         result = env.collect(self.policy, self.n_steps, noise=self.rng)
         return self.learner.update(result, lr=self.lr_at(update, total_timesteps))
+
+
+def ddpg_hidden_from_policy_kwargs(policy_kwargs):
+    """``dict(layers=[...])`` -> the hidden widths (default (64, 64));
+    ``layer_norm`` and other keys raise."""
+    if not policy_kwargs:
+        return (64, 64)
+    if policy_kwargs.get('layer_norm'):
+        raise ValueError('layer_norm is not supported (ddpg.py: out of scope)')
+    unknown = set(policy_kwargs) - {'layers', 'layer_norm'}
+    if unknown:
+        raise ValueError('policy_kwargs takes layers only, got %s' % sorted(unknown))
+    layers = policy_kwargs.get('layers')
+    if layers is None:
+        return (64, 64)
+    hidden = tuple(int(h) for h in layers)
+    if not hidden:
+        raise ValueError('layers needs at least one hidden layer')
+    return hidden
+
+
+class DDPG(BaseAgent):
+    """stable-baselines 2.x ``DDPG`` on the device (see the module docstring
+    and ``custom_envs_amd.ddpg``).  ``nb_eval_steps``, ``memory_limit``,
+    ``memory_policy``, ``param_noise_adaption_interval``, ``return_range`` and
+    ``render_eval`` are accepted and ignored."""
+    LOG_INTERVAL = 1
+    # what ddpg.py lists as out of scope: keyword -> its stable-baselines default
+    REFUSED = {'param_noise': None, 'normalize_observations': False, 'normalize_returns': False,
+               'enable_popart': False, 'critic_l2_reg': 0.0, 'clip_norm': None,
+               'reward_scale': 1.0, 'random_exploration': 0.0, 'eval_env': None, 'render': False}
+
+    def __init__(self, policy, env, gamma=0.99, memory_policy=None, eval_env=None,
+                 nb_train_steps=50, nb_rollout_steps=100, nb_eval_steps=100, param_noise=None,
+                 action_noise=None, normalize_observations=False, tau=0.001, batch_size=128,
+                 param_noise_adaption_interval=50, normalize_returns=False, enable_popart=False,
+                 observation_range=(-5.0, 5.0), critic_l2_reg=0.0,
+                 return_range=(-np.inf, np.inf), actor_lr=1e-4, critic_lr=1e-3, clip_norm=None,
+                 reward_scale=1.0, render=False, render_eval=False, memory_limit=None,
+                 buffer_size=50000, random_exploration=0.0, verbose=0, seed=None,
+                 policy_kwargs=None):
+        if policy is not ddpg.MlpPolicy and policy != 'MlpPolicy':
+            if getattr(policy, '__name__', policy) == 'LnMlpPolicy':
+                raise ValueError('layer_norm (LnMlpPolicy) is not supported')
+            raise ValueError('policy must be ddpg.MlpPolicy, got %r' % (policy,))
+        given = dict(param_noise=param_noise, normalize_observations=normalize_observations,
+                     normalize_returns=normalize_returns, enable_popart=enable_popart,
+                     critic_l2_reg=critic_l2_reg, clip_norm=clip_norm, reward_scale=reward_scale,
+                     random_exploration=random_exploration, eval_env=eval_env, render=render)
+        for key, default in self.REFUSED.items():
+            value = given[key]
+            same = (value is None) if default is None else \
+                (value is not None and not callable(value) and value == default)
+            if not same:
+                raise ValueError('%s=%r is not supported: only stable-baselines\' default %r '
+                                 '(ddpg.py: out of scope)' % (key, value, default))
+        if action_noise is not None and not isinstance(action_noise, ddpg.ActionNoise):
+            raise ValueError('action_noise must be a ddpg.NormalActionNoise, a '
+                             'ddpg.OrnsteinUhlenbeckActionNoise or None, got %r' % (action_noise,))
+        self.hidden = ddpg_hidden_from_policy_kwargs(policy_kwargs)
+        self.spec = s = env_spec(env)
+        self.env = None if isinstance(env, EnvSpec) else env
+        self.verbose = int(verbose)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), 'little')
+        self.seed = int(seed)
+        self.nb_train_steps, self.nb_rollout_steps = int(nb_train_steps), int(nb_rollout_steps)
+        self.batch_size = int(batch_size)
+        if self.nb_train_steps < 1 or self.nb_rollout_steps < 1 or self.batch_size < 1:
+            raise ValueError('nb_train_steps, nb_rollout_steps and batch_size must be >= 1')
+        self.buffer_size = int(buffer_size) // s.rows * s.rows
+        if self.buffer_size < max(s.rows, self.batch_size):
+            raise ValueError('buffer_size = %d rounds down to %d records (a multiple of the %d '
+                             'rows a step writes), which must be at least max(rows, batch_size) '
+                             '= %d' % (int(buffer_size), self.buffer_size, s.rows,
+                                       max(s.rows, self.batch_size)))
+        self.action_noise = action_noise
+        if action_noise is not None:
+            action_noise.params(s.act_dim)
+        self.kwargs = dict(
+            gamma=float(gamma), nb_train_steps=self.nb_train_steps,
+            nb_rollout_steps=self.nb_rollout_steps, tau=float(tau), batch_size=self.batch_size,
+            observation_range=[float(observation_range[0]), float(observation_range[1])],
+            actor_lr=float(actor_lr), critic_lr=float(critic_lr), buffer_size=int(buffer_size),
+            verbose=self.verbose, seed=self.seed, policy_kwargs=policy_kwargs)
+        self.n_batch = s.rows * self.nb_rollout_steps        # timesteps per cycle
+        self.num_timesteps = 0
+        scale = 1.0 if s.low is None else np.abs(s.low)
+        self.agent = ddpg.DDPGAgent(s.obs_dim, s.act_dim, self.hidden, scale=scale, gamma=gamma,
+                                    tau=tau, actor_lr=actor_lr, critic_lr=critic_lr,
+                                    obs_range=observation_range, device=s.device)
+        self.memory = ddpg.ReplayMemory(self.buffer_size, s.rows, s.obs_dim, s.act_dim,
+                                        device=s.device)
+        self.rng = DeviceRng(self.seed, s.device)
+        self.agent.set_params(ddpg.init_params_numpy(s.obs_dim, s.act_dim, self.hidden,
+                                                     self.seed & 0xffffffff))
+
+    # ------------------------------------------------------------- the state
+    def get_parameters(self, target=False):
+        """The flat float32 online (``target``: target) parameters
+        (``ddpg.params_layout``), numpy."""
+        return self.agent.get_params(target=target)
+
+    def set_parameters(self, flat, target=None):
+        """The online parameters, copied into the targets too unless
+        ``target`` (a flat vector) gives those."""
+        self.agent.set_params(flat)
+        if target is not None:
+            self.agent.set_params(target, target_only=True)
+
+    def get_opt_state(self):
+        return self.agent.get_opt_state()
+
+    def set_opt_state(self, state):
+        self.agent.set_opt_state(state)
+
+    # ------------------------------------------------------------------ learn
+    def check_learn(self, total_timesteps):
+        """The cycles of a ``learn(total_timesteps)`` call (no GPU)."""
+        total = int(total_timesteps)
+        if total < self.n_batch:
+            raise ValueError('total_timesteps = %d is less than one cycle (rows * '
+                             'nb_rollout_steps = %d)' % (total, self.n_batch))
+        return total // self.n_batch
+
+    def _noise(self):
+        return None if self.action_noise is None else (self.action_noise, self.rng)
+
+    def _update(self, env, update, n_updates, total_timesteps):
+        """One cycle: the rollout into the memory, then the train phase
+        (skipped while the memory cannot fill a batch: SB's ``can_sample``).
+        Returns the last train step's ``ddpg.Stats`` or None."""
+        env.collect_ddpg(self.agent, self.memory, self.nb_rollout_steps, noise=self._noise())
+        if self.memory.size < self.batch_size:
+            return None
+        stats = self.agent.train(self.memory, self.nb_train_steps, self.batch_size, self.rng)
+        return ddpg.Stats(stats[-1])
+
+    def _log(self, update, stats):
+        if stats is None:
+            print('| cycle %d | timesteps %d | memory %d < batch_size |'
+                  % (update, self.num_timesteps, self.memory.size))
+            return
+        super()._log(update, stats)
+
+    # ---------------------------------------------------------------- predict
+    def predict(self, observation, state=None, mask=None, deterministic=True):
+        """``(env_action, None)`` for ``observation`` (numpy or a device
+        tensor, ``[rows][D]`` or ``[D]``); numpy in, numpy out.  With
+        ``deterministic=False`` a ``NormalActionNoise`` is drawn on the
+        generator's ``PREDICT`` stream and its own counter (training's
+        streams are untouched); without a noise object the action is the
+        deterministic one; Ornstein-Uhlenbeck noise raises (its state belongs
+        to training)."""
+        import torch
+        if self.agent._h is None:
+            raise RuntimeError('predict() needs a device: this model holds the shape only')
+        noisy = not deterministic and self.action_noise is not None
+        if noisy and not isinstance(self.action_noise, ddpg.NormalActionNoise):
+            raise ValueError('a stochastic predict() with Ornstein-Uhlenbeck noise is not '
+                             'supported: the process state belongs to training')
+        dev = torch.device('cuda', self.agent.device)
+        as_numpy = not torch.is_tensor(observation)
+        if as_numpy:
+            obs = torch.from_numpy(np.ascontiguousarray(observation, dtype=np.float32)).to(dev)
+        else:
+            obs = observation.to(dev, torch.float32).contiguous()
+        single = obs.dim() == 1
+        if single:
+            obs = obs[None]
+        if obs.dim() != 2 or obs.shape[1] != self.spec.obs_dim:
+            raise ValueError('observation must have shape [rows][%d] or [%d], got %s'
+                             % (self.spec.obs_dim, self.spec.obs_dim, tuple(observation.shape)))
+        noise = None
+        if noisy:
+            mean, sigma = (torch.from_numpy(v).to(dev)
+                           for v in self.action_noise.params(self.spec.act_dim))
+            noise = mean + sigma * self.rng.predict_normal(obs.shape[0], self.spec.act_dim)
+        actions = self.agent.act(obs, noise)['env_action']
+        if single:
+            actions = actions[0]
+        if as_numpy:
+            actions = actions.cpu().numpy()
+        return actions, None
+
+    # ------------------------------------------------------------ save / load
+    def _meta(self):
+        s = self.spec
+        return {'format': 1, 'algorithm': type(self).__name__, 'kwargs': self.kwargs,
+                'action_noise': None if self.action_noise is None
+                else self.action_noise.describe(),
+                'rows': s.rows, 'obs_dim': s.obs_dim, 'act_dim': s.act_dim,
+                'low': None if s.low is None else [float(v) for v in s.low],
+                'high': None if s.high is None else [float(v) for v in s.high],
+                'hidden': list(self.hidden), 'n_params': int(self.agent.n_params),
+                'opt_blocks': list(self.agent.OPT_BLOCKS)}
+
+    def save(self, save_path, memory=False):
+        """One ``.npz`` (``np.savez``, no pickle): a JSON string of the
+        constructor arguments, shapes and the noise description, the online
+        and target parameters, Adam's ``m``, ``v`` and step count,
+        ``num_timesteps``, the generator's state (``replay_t`` included) and
+        an Ornstein-Uhlenbeck process's state.  ``memory=True`` adds the valid
+        records of the replay memory with ``size`` and ``pos``."""
+        opt = self.get_opt_state()
+        g = self.rng.state()
+        arrays = {'meta': np.array(json.dumps(self._meta())),
+                  'params': self.get_parameters(), 'target': self.get_parameters(target=True),
+                  'opt_m': opt['m'], 'opt_v': opt['v'], 'opt_step': np.array(opt['step'], np.int64),
+                  'num_timesteps': np.array(self.num_timesteps, np.int64),
+                  'rng': np.array([g['seed'], g['row_offset'], g['t'], g['epoch'],
+                                   g['predict_t'], g['replay_t']], np.uint64)}
+        ou = getattr(self.action_noise, 'get_state', lambda: None)()
+        if ou is not None:
+            arrays['ou_state'], arrays['ou_dones'] = ou
+        if memory:
+            mem = self.memory
+            arrays['mem_size_pos'] = np.array([mem.size, mem.pos], np.int64)
+            for name in mem.FIELDS:
+                arrays['mem_' + name] = getattr(mem, name)[:mem.size].cpu().numpy()
+        np.savez(save_path, **arrays)
+
+    @classmethod
+    def load(cls, load_path, env=None, device='auto', **overrides):
+        """The model ``save`` wrote (see ``BaseAgent.load`` for ``env`` and
+        ``device``).  ``overrides`` replace constructor arguments
+        (``action_noise`` among them).  A file saved with ``memory=True``
+        restores the replay memory; otherwise the memory starts empty."""
+        data, meta, kwargs, env = cls._read(load_path, env, device, overrides)
+        if 'action_noise' not in kwargs:
+            kwargs['action_noise'] = ddpg.ActionNoise.from_description(meta.get('action_noise'))
+        model = cls(ddpg.MlpPolicy, env, **kwargs)
+        s = model.spec
+        if (s.obs_dim, s.act_dim, list(model.hidden)) != (meta['obs_dim'], meta['act_dim'],
+                                                          meta['hidden']):
+            raise ValueError('the env maps %d -> %d, the saved model %d -> %d (hidden %s)'
+                             % (s.obs_dim, s.act_dim, meta['obs_dim'], meta['act_dim'],
+                                meta['hidden']))
+        model.set_parameters(data['params'], target=data['target'])
+        model.set_opt_state({'m': data['opt_m'], 'v': data['opt_v'],
+                             'step': int(data['opt_step'])})
+        model.num_timesteps = int(data['num_timesteps'])
+        g = [int(v) for v in data['rng']]
+        model.rng.set_state({'seed': g[0], 'row_offset': g[1], 't': g[2], 'epoch': g[3],
+                             'predict_t': g[4], 'replay_t': g[5]})
+        model.seed = g[0]
+        if 'ou_state' in data and hasattr(model.action_noise, 'set_state') \
+                and 'action_noise' not in overrides:
+            model.action_noise.set_state(data['ou_state'], data['ou_dones'])
+        if 'mem_size_pos' in data:
+            import torch
+            mem = model.memory
+            size, pos = (int(v) for v in data['mem_size_pos'])
+            if s.rows != meta['rows'] or size > mem.capacity or size % s.rows or pos % s.rows \
+                    or pos >= mem.capacity:
+                raise ValueError('the saved replay memory (%d records of %d-row steps) does not '
+                                 'fit this model\'s (%d records, %d rows)'
+                                 % (size, meta['rows'], mem.capacity, s.rows))
+            for name in mem.FIELDS:
+                getattr(mem, name)[:size].copy_(torch.from_numpy(data['mem_' + name]))
+            mem.size, mem.pos = size, pos
+        return model

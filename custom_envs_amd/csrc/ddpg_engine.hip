@@ -7,6 +7,8 @@
 //   ce_ddpg_target  [target]
 //   ce_ddpg_grad    [target, gradient, reduce, statistics]
 //   ce_ddpg_step    [target, gradient, reduce, statistics, update]    (five)
+//   ce_ddpg_act_rng [act, the noise formed in the kernel]
+//   ce_ddpg_train   [replay indices] + steps x the five of ce_ddpg_step
 // where update is Adam on both blocks, the soft update and both images'
 // repack.  Every argument check precedes the first HIP call, and the checks of
 // the plain arguments precede the check of the handle, so they run without a
@@ -21,6 +23,7 @@
 
 #include "common.h"
 #include "ddpg_kernels.h"
+#include "policy_engine.h"     // rng_replay_args_ok, rng_enqueue_replay
 
 struct ce_ddpg {
     ce_ddpg_config cfg{};
@@ -280,6 +283,7 @@ int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out) {
     l->grid_max = cfg->grid_limit > 0 ? cfg->grid_limit : std::max(1, prop.multiProcessorCount);
     // the dynamic LDS of the three tile kernels, once, from the limits' need
     for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_kernel),
+                          reinterpret_cast<const void *>(ce::ddpg_act_rng_kernel),
                           reinterpret_cast<const void *>(ce::ddpg_target_kernel),
                           reinterpret_cast<const void *>(ce::ddpg_grad_kernel)})
         CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -379,6 +383,65 @@ int ce_ddpg_act(const ce_ddpg *l, const float *obs, const float *noise, int64_t 
     return CE_OK;
 }
 
+int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
+                    uint32_t row0, const ce_ddpg_noise *noise, float *ou_state,
+                    const uint8_t *reset, float *action, float *env_action, void *hip_stream) {
+    const char *who = "ce_ddpg_act_rng";
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (rows < 1 || rows > kMaxRows)
+        return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
+    if (static_cast<uint64_t>(row0) + static_cast<uint64_t>(rows) > (uint64_t(1) << 32))
+        return bad(": rows row0 .. row0 + rows - 1 must stay below 2^32");
+    if (!obs) return bad(": null obs");
+    if (!action) return bad(": null action output");
+    if (!env_action) return bad(": null env_action output");
+    if (!noise) return bad(": null noise description");
+    if (noise->kind != CE_DDPG_NOISE_NORMAL && noise->kind != CE_DDPG_NOISE_OU)
+        return bad(": unknown noise kind " + std::to_string(noise->kind));
+    const bool ou = noise->kind == CE_DDPG_NOISE_OU;
+    if (ou && !ou_state) return bad(": Ornstein-Uhlenbeck noise needs its state buffer");
+    if (ou && (!std::isfinite(noise->theta) || !std::isfinite(noise->dt) || !(noise->dt > 0.0)))
+        return bad(": theta must be finite and dt positive");
+    if (!l) return bad(": null learner");
+    for (int c = 0; c < l->plan.A; ++c)
+        if (!std::isfinite(noise->mean[c]) || !std::isfinite(noise->sigma[c]) ||
+            noise->sigma[c] < 0.0f)
+            return bad(": mean must be finite and sigma finite and not negative");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    ce::DdpgActArgs g{};
+    g.p = l->plan;
+    g.rows = static_cast<int>(rows);
+    g.img = l->img;
+    g.scale = l->scale;
+    g.obs = obs;
+    g.action = action;
+    g.env_action = env_action;
+    ce::DdpgActRng n{};
+    n.seed_lo = static_cast<uint32_t>(seed);
+    n.seed_hi = static_cast<uint32_t>(seed >> 32);
+    n.t = t;
+    n.row0 = row0;
+    n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
+    n.theta = ou ? static_cast<float>(noise->theta) : 0.0f;
+    n.dt = ou ? static_cast<float>(noise->dt) : 0.0f;
+    n.ou = ou ? ou_state : nullptr;
+    n.reset = ou ? reset : nullptr;
+    for (int c = 0; c < l->plan.A; ++c) {
+        n.mean[c] = noise->mean[c];
+        n.sigma[c] = ou ? static_cast<float>(static_cast<double>(noise->sigma[c]) *
+                                             std::sqrt(noise->dt))
+                        : noise->sigma[c];
+    }
+    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
+    // + the tile's N(0,1) block [round4(A)][33] behind the row scalars
+    const size_t lds = l->lds_act + static_cast<size_t>(round_up(l->plan.A, 4)) * ce::kDdpgLd *
+                                        sizeof(float);
+    hipLaunchKernelGGL(ce::ddpg_act_rng_kernel, dim3(tiles), dim3(ce::kDdpgBlock), lds,
+                       static_cast<hipStream_t>(hip_stream), g, n);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
 int ce_ddpg_target(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,
                    const float *rewards, const uint8_t *dones, float *y, void *hip_stream) {
     const char *who = "ce_ddpg_target";
@@ -424,6 +487,78 @@ int ce_ddpg_step(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const flo
     enqueue_grad(l, n, m, idx, obs0, actions, rewards, obs1, dones, y, l->grad, stats, stream);
     enqueue_update(l, actor_lr, critic_lr, stream);
     CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_train(ce_ddpg *l, int32_t steps, int64_t n, int64_t size, uint64_t seed, uint32_t t0,
+                  const float *obs0, const float *actions, const float *rewards,
+                  const float *obs1, const uint8_t *dones, int32_t *idx_scratch, float *y,
+                  double actor_lr, double critic_lr, float *stats, void *hip_stream) {
+    const char *who = "ce_ddpg_train";
+    if (std::isnan(actor_lr) || std::isnan(critic_lr))
+        return fail(CE_EINVAL, std::string(who) + ": a learning rate is not a number");
+    int rc = ce::rng_replay_args_ok(who, steps, n, size, t0);
+    if (rc != CE_OK) return rc;
+    if (!idx_scratch) return fail(CE_EINVAL, std::string(who) + ": null idx_scratch");
+    if (reinterpret_cast<uintptr_t>(idx_scratch) & 3)
+        return fail(CE_EINVAL, std::string(who) + ": idx_scratch must be 4-byte aligned");
+    rc = batch_ok(who, l, n, size, idx_scratch, obs0, actions, rewards, obs1, dones, y, stats);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    ce::rng_enqueue_replay(idx_scratch, steps, n, size, seed, t0, stream);
+    for (int32_t s = 0; s < steps; ++s) {
+        enqueue_grad(l, n, size, idx_scratch + s * n, obs0, actions, rewards, obs1, dones, y,
+                     l->grad, stats + s * 8, stream);
+        enqueue_update(l, actor_lr, critic_lr, stream);
+    }
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+// Adam's two blocks to (`set` false) or from the caller's; every check first
+static int ddpg_opt_state(const char *who, ce_ddpg *l, void *m, void *v, int64_t n, bool set,
+                          uint32_t flags, void *hip_stream) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (!m) return bad(": null m");
+    if (!v) return bad(": null v");
+    if (!l) return bad(": null learner");
+    if (n != l->plan.n_params)
+        return bad(": got " + std::to_string(n) + " entries per block, the agent has " +
+                   std::to_string(l->plan.n_params) + " parameters");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool dev = (flags & CE_PTR_DEVICE) != 0;
+    const size_t bytes = static_cast<size_t>(n) * sizeof(float);
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice
+                                   : (set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    if (set) {
+        CE_HIP(hipMemcpyAsync(l->m, m, bytes, kind, stream));
+        CE_HIP(hipMemcpyAsync(l->v, v, bytes, kind, stream));
+    } else {
+        CE_HIP(hipMemcpyAsync(m, l->m, bytes, kind, stream));
+        CE_HIP(hipMemcpyAsync(v, l->v, bytes, kind, stream));
+    }
+    if (!dev) CE_HIP(hipStreamSynchronize(stream));   // the host blocks may be pageable
+    return CE_OK;
+}
+
+int ce_ddpg_get_opt_state(ce_ddpg *l, float *m, float *v, int64_t n, int64_t *step,
+                          uint32_t flags, void *hip_stream) {
+    if (!step) return fail(CE_EINVAL, "ce_ddpg_get_opt_state: null step");
+    const int rc = ddpg_opt_state("ce_ddpg_get_opt_state", l, m, v, n, false, flags, hip_stream);
+    if (rc != CE_OK) return rc;
+    *step = l->t;
+    return CE_OK;
+}
+
+int ce_ddpg_set_opt_state(ce_ddpg *l, const float *m, const float *v, int64_t n, int64_t step,
+                          uint32_t flags, void *hip_stream) {
+    if (step < 0) return fail(CE_EINVAL, "ce_ddpg_set_opt_state: step must not be negative");
+    const int rc = ddpg_opt_state("ce_ddpg_set_opt_state", l, const_cast<float *>(m),
+                                  const_cast<float *>(v), n, true, flags, hip_stream);
+    if (rc != CE_OK) return rc;
+    l->t = step;
     return CE_OK;
 }
 

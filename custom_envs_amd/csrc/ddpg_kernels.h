@@ -21,6 +21,8 @@
 //
 // ddpg_act_kernel      grid ceil(rows / 32): obs tile -> actor chain -> tanh
 //                      (+ noise, clip to [-1, 1]) -> action, action * scale.
+// ddpg_act_rng_kernel  the same tile with the noise formed in the epilogue from
+//                      rng.h's stream (Normal or Ornstein-Uhlenbeck).
 // ddpg_target_kernel   grid ceil(n / 32), rows gathered by idx: obs1 tile once,
 //                      the target actor's action left in LDS as the concat rows
 //                      of the target critic's second layer, the target critic,
@@ -65,6 +67,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "rng.h"
 
 namespace ce {
 
@@ -352,7 +356,35 @@ struct DdpgActArgs {
     float *action, *env_action;
 };
 
-__global__ __launch_bounds__(kDdpgBlock) void ddpg_act_kernel(const DdpgActArgs g) {
+// The noise the generated instance forms (ce_ddpg_act_rng): tile row r, column
+// c take z = rng_normal4(seed, row0 + r, t, c / 4, kRngActionNoise)[c % 4], then
+//   Normal  n  = mean + sigma * z
+//   OU      x' = (x + (theta * (mean - x)) * dt) + s * z,  n = x'
+// (stable-baselines' NormalActionNoise / OrnsteinUhlenbeckActionNoise; sigma
+// holds s = float32(sigma sqrt(dt)) for OU), every operation float32 and
+// unfused.  x is the caller's [rows][A] state, read as 0 where reset[r] != 0;
+// the thread that owns (r, c) in the epilogue reads and writes its element.
+//
+// The tile's z are drawn by all 256 threads, one (row, block of four) each,
+// into an LDS block [round4(A)][33] behind the row scalars (where the gradient
+// kernel keeps the head's derivative) while the observation tile loads; the
+// forward's barriers lie between that and the epilogue, which reads z[c][r].
+// Drawn inside the epilogue instead, the one wave that owns an A <= 32 head
+// runs 16 Philox + Box-Muller chains per lane with three waves idle: 29.5 us
+// a launch against 14.9 us for the tensor instance at 4096 rows, 41 -> 20.
+constexpr int kDdpgNoiseNormal = 0, kDdpgNoiseOu = 1;
+struct DdpgActRng {
+    uint32_t seed_lo, seed_hi, t, row0;
+    int kind;
+    float theta, dt;
+    float *ou;                 // [rows][A], OU only
+    const uint8_t *reset;      // [rows] or null, OU only
+    float mean[kDdpgMaxA], sigma[kDdpgMaxA];
+};
+
+// `n` is read by the RNG instance only.
+template <bool RNG>
+__device__ __forceinline__ void ddpg_act_tile(const DdpgActArgs &g, const DdpgActRng *n) {
     extern __shared__ __attribute__((aligned(16))) float ddpg_lds_act[];
     const DdpgPlan &a = g.p;
     const DdpgLds s = ddpg_lds(ddpg_lds_act, a, kDdpgActBufs);
@@ -362,10 +394,29 @@ __global__ __launch_bounds__(kDdpgBlock) void ddpg_act_kernel(const DdpgActArgs 
     ddpg_tile_rows(s.rowsrc, nullptr, row0, live, g.rows);
     __syncthreads();
     ddpg_load_obs(s.buf[0], g.obs, s.rowsrc, a.D, a.in_pad[0][0], a.obs_lo, a.obs_hi);
+    if constexpr (RNG) {
+        const int nb = (a.A + 3) >> 2;
+        for (int i = threadIdx.x; i < live * nb; i += kDdpgBlock) {
+            const int r = i / nb, b = i - r * nb;
+            const float4 z = rng_normal4(n->seed_lo, n->seed_hi,
+                                         n->row0 + static_cast<uint32_t>(row0 + r), n->t,
+                                         static_cast<uint32_t>(b), kRngActionNoise);
+            float *dst = s.sech2 + 4 * b * kDdpgLd + r;
+            dst[0] = z.x;
+            dst[kDdpgLd] = z.y;
+            dst[2 * kDdpgLd] = z.z;
+            dst[3 * kDdpgLd] = z.w;
+        }
+    }
     float *const xs[kDdpgLayers] = {s.buf[0], s.buf[1], s.buf[2]};
     ddpg_forward(a, 0, g.img, s.wbuf, xs, [&](const ddpg_f32x16 &acc, int col) {
         if (col >= a.A) return;
         const float sc = g.scale[col];
+        float mean = 0.0f, sigma = 0.0f;
+        if constexpr (RNG) {
+            mean = n->mean[col];
+            sigma = n->sigma[col];
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = ddpg_acc_row(r, h);
@@ -373,12 +424,37 @@ __global__ __launch_bounds__(kDdpgBlock) void ddpg_act_kernel(const DdpgActArgs 
                 const long long o = (row0 + row) * a.A + col;
                 float d;
                 float act = ddpg_tanh(acc[r], &d);
-                if (g.noise) act = fminf(fmaxf(act + g.noise[o], -1.0f), 1.0f);
+                if constexpr (RNG) {
+#pragma clang fp contract(off)
+                    const float z = s.sech2[col * kDdpgLd + row];
+                    float noise;
+                    if (n->kind == kDdpgNoiseOu) {
+                        float x = n->ou[o];
+                        if (n->reset && n->reset[row0 + row]) x = 0.0f;
+                        noise = (x + (n->theta * (mean - x)) * n->dt) + sigma * z;
+                        n->ou[o] = noise;
+                    } else {
+                        noise = mean + sigma * z;
+                    }
+                    act = fminf(fmaxf(act + noise, -1.0f), 1.0f);
+                } else {
+                    if (g.noise) act = fminf(fmaxf(act + g.noise[o], -1.0f), 1.0f);
+                }
                 g.action[o] = act;
                 g.env_action[o] = act * sc;
             }
         }
     });
+}
+
+__global__ __launch_bounds__(kDdpgBlock) void ddpg_act_kernel(const DdpgActArgs g) {
+    ddpg_act_tile<false>(g, nullptr);
+}
+
+// the instance that forms its own noise
+__global__ __launch_bounds__(kDdpgBlock) void ddpg_act_rng_kernel(const DdpgActArgs g,
+                                                                  const DdpgActRng n) {
+    ddpg_act_tile<true>(g, &n);
 }
 
 // The actor's action of network image `img` at the tile in obs_buf into the

@@ -56,6 +56,14 @@ void policy_launch(const ce_policy *p, const float *obs, const PolicyNoise &nois
 // t0 .. t0 + k - 1 and rows row0 .. row0 + rows - 1 must fit 32 bits.
 int policy_rng_args_ok(const char *who, int64_t k, int64_t rows, uint32_t t0, uint32_t row0);
 
+// The replay indices of draws t0 .. t0 + steps - 1 (rng_kernels.h:
+// rng_replay_kernel), for ce_rng_replay and ce_ddpg_train.  rng_replay_args_ok
+// is every check (no HIP call); rng_enqueue_replay is the one launch, its
+// arguments NOT validated.
+int rng_replay_args_ok(const char *who, int64_t steps, int64_t n, int64_t size, uint32_t t0);
+void rng_enqueue_replay(int32_t *out, int64_t steps, int64_t n, int64_t size, uint64_t seed,
+                        uint32_t t0, hipStream_t stream);
+
 // The argument checks the two rollout entry points share (before any HIP
 // call): null pointers, k, strides, alignment, the policy's shape against the
 // engine's.  CE_OK or a failed status with ce_last_error set.

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "policy_engine.h"
 #include "policy_kernels.h"
+#include "rng_kernels.h"
 
 struct ce_policy {
     ce_policy_config cfg{};
@@ -203,6 +204,29 @@ int policy_rng_args_ok(const char *who, int64_t k, int64_t rows, uint32_t t0, ui
     return CE_OK;
 }
 
+int rng_replay_args_ok(const char *who, int64_t steps, int64_t n, int64_t size, uint32_t t0) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (steps < 1) return bad(": steps must be at least 1, got " + std::to_string(steps));
+    if (n < 1 || n > (int64_t(1) << 24))
+        return bad(": n must be in [1, 2^24], got " + std::to_string(n));
+    if (size < 1 || size > (int64_t(1) << 24))
+        return bad(": size must be in [1, 2^24], got " + std::to_string(size));
+    if (static_cast<uint64_t>(t0) + static_cast<uint64_t>(steps) > (uint64_t(1) << 32))
+        return bad(": draws t0 .. t0 + steps - 1 must stay below 2^32");
+    if (steps * ((n + 3) / 4) > (int64_t(1) << 31) || steps * n > (int64_t(1) << 31))
+        return bad(": steps * n is too large for one launch");
+    return CE_OK;
+}
+
+void rng_enqueue_replay(int32_t *out, int64_t steps, int64_t n, int64_t size, uint64_t seed,
+                        uint32_t t0, hipStream_t stream) {
+    const int64_t nb = (n + 3) / 4, total = steps * nb;
+    hipLaunchKernelGGL(rng_replay_kernel, dim3(static_cast<unsigned>((total + 255) / 256)),
+                       dim3(256), 0, stream, out, static_cast<long long>(total),
+                       static_cast<int>(nb), static_cast<int>(n), static_cast<uint32_t>(size),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), t0);
+}
+
 ce_policy_outputs policy_advance(const ce_policy_outputs &o, int64_t bytes) {
     auto adv = [bytes](float *q) { return reinterpret_cast<float *>(reinterpret_cast<char *>(q) + bytes); };
     return ce_policy_outputs{adv(o.action), adv(o.env_action), adv(o.neglogp), adv(o.value)};
@@ -351,10 +375,11 @@ int ce_policy_forward_rng(const ce_policy *p, const float *obs, uint64_t seed, u
     return CE_OK;
 }
 
-int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
-                  int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
-                  void *hip_stream) {
-    const char *who = "ce_rng_normal";
+// ce_rng_normal (purpose < 0: the policy-noise kernel, as before) and
+// ce_rng_normal_purpose
+static int rng_normal_entry(const char *who, float *out, int32_t k, int64_t rows, int32_t act_dim,
+                            int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                            int64_t purpose, void *hip_stream) {
     const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
     if (!out) return bad(": null output");
     if (k < 1) return bad(": k must be at least 1, got " + std::to_string(k));
@@ -370,12 +395,47 @@ int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
     const int64_t total = int64_t(k) * rows * ((act_dim + 3) / 4);
     const int64_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffff) return bad(": k * rows * act_dim is too large for one launch");
+    CE_CLEAR_STALE_ERROR_AT(who);
+    const dim3 grid(static_cast<unsigned>(blocks));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const long long stride = record_stride_bytes / 4;
+    const uint32_t lo = static_cast<uint32_t>(seed), hi = static_cast<uint32_t>(seed >> 32);
+    if (purpose < 0)
+        hipLaunchKernelGGL(ce::rng_normal_kernel, grid, dim3(256), 0, stream, out,
+                           static_cast<long long>(total), static_cast<int>(rows), act_dim, stride,
+                           lo, hi, t0, row0);
+    else
+        hipLaunchKernelGGL(ce::rng_normal_purpose_kernel, grid, dim3(256), 0, stream, out,
+                           static_cast<long long>(total), static_cast<int>(rows), act_dim, stride,
+                           lo, hi, t0, row0, static_cast<uint32_t>(purpose));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                  int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                  void *hip_stream) {
+    return rng_normal_entry("ce_rng_normal", out, k, rows, act_dim, record_stride_bytes, seed, t0,
+                            row0, -1, hip_stream);
+}
+
+int ce_rng_normal_purpose(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                          int64_t record_stride_bytes, uint64_t seed, uint32_t purpose, uint32_t t0,
+                          uint32_t row0, void *hip_stream) {
+    return rng_normal_entry("ce_rng_normal_purpose", out, k, rows, act_dim, record_stride_bytes,
+                            seed, t0, row0, purpose, hip_stream);
+}
+
+int ce_rng_replay(int32_t *out, int64_t steps, int64_t n, int64_t size, uint64_t seed, uint32_t t0,
+                  void *hip_stream) {
+    const char *who = "ce_rng_replay";
+    if (!out) return fail(CE_EINVAL, std::string(who) + ": null output");
+    if (reinterpret_cast<uintptr_t>(out) & 3)
+        return fail(CE_EINVAL, std::string(who) + ": the output must be 4-byte aligned");
+    const int rc = ce::rng_replay_args_ok(who, steps, n, size, t0);
+    if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ce::rng_normal_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       static_cast<hipStream_t>(hip_stream), out, static_cast<long long>(total),
-                       static_cast<int>(rows), act_dim,
-                       static_cast<long long>(record_stride_bytes / 4),
-                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), t0, row0);
+    ce::rng_enqueue_replay(out, steps, n, size, seed, t0, static_cast<hipStream_t>(hip_stream));
     CE_HIP(hipGetLastError());
     return CE_OK;
 }

@@ -5,7 +5,8 @@
 //   key      (seed & 0xffffffff, seed >> 32)
 //   counter  (row, t, block, purpose): the global row, the draw index (one per
 //            env step or per epoch), the group of four values inside the row,
-//            and a tag (kRngPolicy, kRngPermutation, kRngPredict)
+//            and a tag (kRngPolicy, kRngPermutation, kRngPredict,
+//            kRngActionNoise, kRngReplay)
 //   uniform  u(x) = ((x >> 8) + 0.5) * 2^-24, strictly inside (0, 1)
 //   normals  r = sqrt(-2 ln u(x0)), z0 = r cospi(2 u(x1)), z1 = r sinpi(2 u(x1));
 //            the same from (x2, x3) gives z2, z3.  |z| <= 5.89.
@@ -18,6 +19,9 @@
 // so every argument of logf / log1pf / sincospif is the exact real number the
 // statement names, and the float32 result is within a few ulp of the float64
 // one at every x (near u = 1 a rounded u would cost up to 2.4e-4 in z).
+//
+// Device functions only, so every kernel header may include it; the kernels
+// of the ce_rng_* entries are in rng_kernels.h (policy_engine.hip's unit).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,6 +31,7 @@
 namespace ce {
 
 constexpr uint32_t kRngPolicy = 0, kRngPermutation = 1, kRngPredict = 2;
+constexpr uint32_t kRngActionNoise = 3, kRngReplay = 4;     // DDPG: action noise, replay indices
 
 struct RngWords {
     uint32_t x0, x1, x2, x3;
@@ -78,41 +83,6 @@ __device__ __forceinline__ float4 rng_normal4(uint32_t seed_lo, uint32_t seed_hi
     rng_box_muller(w.x0, w.x1, &z.x, &z.y);
     rng_box_muller(w.x2, w.x3, &z.z, &z.w);
     return z;
-}
-
-// ce_rng_normal: out[s][r][a] (record s at out + s * stride floats) for draws
-// t0 + s, rows row0 + r; one thread per (s, r, block)
-__global__ __launch_bounds__(256) void rng_normal_kernel(float *out, long long total, int rows,
-                                                         int A, long long stride, uint32_t seed_lo,
-                                                         uint32_t seed_hi, uint32_t t0,
-                                                         uint32_t row0) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int nb = (A + 3) >> 2;
-    const int b = static_cast<int>(i % nb);
-    const long long sr = i / nb;
-    const int r = static_cast<int>(sr % rows);
-    const long long s = sr / rows;
-    const float4 z = rng_normal4(seed_lo, seed_hi, row0 + static_cast<uint32_t>(r),
-                                 t0 + static_cast<uint32_t>(s), static_cast<uint32_t>(b), kRngPolicy);
-    float *dst = out + s * stride + static_cast<long long>(r) * A + 4 * b;
-    const float v[4] = {z.x, z.y, z.z, z.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (4 * b + j < A) dst[j] = v[j];
-}
-
-// ce_rng_u32: value i is word i % 4 of the block (0, t, i / 4, purpose)
-__global__ __launch_bounds__(256) void rng_u32_kernel(uint32_t *out, long long n, uint32_t seed_lo,
-                                                      uint32_t seed_hi, uint32_t purpose,
-                                                      uint32_t t) {
-    const long long b = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (4 * b >= n) return;
-    const RngWords w = philox4x32_10(0u, t, static_cast<uint32_t>(b), purpose, seed_lo, seed_hi);
-    const uint32_t v[4] = {w.x0, w.x1, w.x2, w.x3};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (4 * b + j < n) out[4 * b + j] = v[j];
 }
 
 }  // namespace ce

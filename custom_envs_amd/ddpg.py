@@ -21,6 +21,15 @@ dtype, no GPU) and the checkers of the kernels:
              h = relu(h W_l + b_l) for hidden l >= 1; Q = h W_out + b_out
     act      action = a (+ noise, then clip to [-1, 1], when noise is given)
              env_action = action * scale
+    noise    a tensor, or formed inside the act kernel from the counter-based
+             generator (``rng.ACTION_NOISE``; ``normal_noise_numpy``,
+             ``ou_noise_numpy``): z = N(0,1) of (global row, draw t, column),
+             Normal  n  = mean + sigma z
+             OU      x' = (x + (theta (mean - x)) dt) + s z,  n = x',
+                     s = float32(sigma sqrt(dt)), x = 0 at the start and at
+                     the rows whose previous step ended an episode
+    sample   the rows of train step t: ``rng.replay_indices_numpy`` (with
+             replacement), one draw per step
     target   y = reward + gamma (1 - done1) critic'(obs1, actor'(obs1))
              (' = the target networks; y is a constant of both losses)
     critic   critic_loss = mean((critic(obs0, action) - y)^2)
@@ -37,7 +46,11 @@ is the normalised one in [-1, 1], as SB stores it; SB steps the env with
 ``action * abs(action_space.low)``, which is ``scale`` here.
 
 ``DDPGAgent`` owns the parameters, the targets and Adam's moments on its
-device.  ``ReplayMemory`` is a device ring of plain torch tensors.  The envs
+device; ``train`` is the train phase of SB's cycle as ONE C call (the indices
+of all its steps from one launch, then the steps' launches, no allocation and
+no host read), and ``get_opt_state`` / ``set_opt_state`` carry Adam across a
+save.  ``agents.DDPG`` is the loop on top (``learn``, ``predict``, ``save``,
+``load``).  ``ReplayMemory`` is a device ring of plain torch tensors.  The envs
 auto-reset: at a done row ``obs1`` is the reset observation, and ``(1 - done)``
 masks it in ``y``.
 
@@ -47,7 +60,8 @@ obs_dim <= 128, act_dim <= 64.  Anything else raises ``NativeEngineError``
 
 Out of scope: parameter noise and layer norm (``LnMlpPolicy``), observation
 and return normalisation, pop-art, ``critic_l2_reg``, ``clip_norm``, DDPG
-under ``distributed.GradientExchange``, graph capture of the loop.
+under ``distributed.GradientExchange``, graph capture of the loop, a C-side
+``[act, env step] x K`` rollout (the collect loop stays Python-issued).
 """
 import ctypes
 from collections import OrderedDict, namedtuple
@@ -55,9 +69,11 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 
 from custom_envs_amd import _native, learner
-from custom_envs_amd._native import CeDdpgConfig, check
+from custom_envs_amd import rng as _rng
+from custom_envs_amd._native import CeDdpgConfig, CeDdpgNoise, check
 from custom_envs_amd.learner import N_STATS
-from custom_envs_amd.policy import MlpPolicy, dict_to_flat, flat_to_dict, layout_size
+from custom_envs_amd.policy import MlpPolicy as _DevicePolicy
+from custom_envs_amd.policy import dict_to_flat, flat_to_dict, layout_size
 from custom_envs_amd.ppo2 import adam_step_numpy
 
 # the first four of the N_STATS (8) floats a call writes; then two zeros,
@@ -304,6 +320,184 @@ def train_step_numpy(params, target_params, m, v, t, batch, n_actor, hp=HyperPar
     return new[0], soft_update_numpy(target_params, new[0], tau), new[1], new[2], stats
 
 
+# ----------------------------------------------------------------------- noise
+class MlpPolicy:
+    """The marker stable-baselines scripts pass as DDPG's ``policy``
+    (``ddpg.MlpPolicy``): the relu actor and critic of this module."""
+
+
+def _noise_params(mean, sigma, act_dim):
+    """``mean`` and ``sigma`` as float32 ``[A]`` (a scalar broadcasts)."""
+    out = []
+    for name, value in (('mean', mean), ('sigma', sigma)):
+        v = np.asarray(value, np.float32)
+        if v.ndim > 1 or (v.ndim == 1 and v.size not in (1, act_dim)):
+            raise ValueError('%s must be a scalar or have shape (%d,), got %s'
+                             % (name, act_dim, v.shape))
+        v = np.array(np.broadcast_to(v.reshape(-1) if v.ndim else v, (act_dim,)))
+        if not np.all(np.isfinite(v)):
+            raise ValueError('%s must be finite' % name)
+        out.append(v)
+    if np.any(out[1] < 0):
+        raise ValueError('sigma must not be negative')
+    return out[0], out[1]
+
+
+def normal_noise_numpy(mean, sigma, z, dtype=np.float64):
+    """``n = mean + sigma * z`` in ``dtype``; ``z [rows][A]`` is
+    ``rng.normal_numpy(..., purpose=rng.ACTION_NOISE)``.  ``mean`` / ``sigma``
+    are the float32 values the kernel holds (a scalar broadcasts to ``[A]``)."""
+    z = np.asarray(z, dtype)
+    mean, sigma = _noise_params(mean, sigma, z.shape[-1])
+    return mean.astype(dtype) + sigma.astype(dtype) * z
+
+
+def ou_scale_numpy(sigma, dt):
+    """``s = float32(sigma * sqrt(dt))``, formed in double from the float32
+    ``sigma``."""
+    return (np.asarray(sigma, np.float32).astype(np.float64) * np.sqrt(np.float64(dt))).astype(
+        np.float32)
+
+
+def ou_noise_numpy(x, mean, sigma, z, theta=0.15, dt=1e-2, reset=None, dtype=np.float64):
+    """One Ornstein-Uhlenbeck step in ``dtype``: ``x' = (x + (theta * (mean -
+    x)) * dt) + s * z`` with ``s = ou_scale_numpy(sigma, dt)``, where ``x
+    [rows][A]`` reads as 0 at the rows with ``reset [rows]`` non-zero.  The
+    noise is ``x'``, which is also the next state."""
+    z = np.asarray(z, dtype)
+    mean, sigma = _noise_params(mean, sigma, z.shape[-1])
+    x = np.asarray(x, dtype)
+    if reset is not None:
+        x = np.where((np.asarray(reset) != 0)[:, None], dtype(0), x)
+    s = ou_scale_numpy(sigma, dt).astype(dtype)
+    return (x + (dtype(theta) * (mean.astype(dtype) - x)) * dtype(dt)) + s * z
+
+
+class ActionNoise:
+    """What ``DDPGAgent.act`` forms inside its kernel when it is passed
+    ``noise=(action_noise, device_rng)``; see the module docstring."""
+    KIND = None
+    theta, dt = 0.0, 0.0
+
+    def __init__(self, mean, sigma):
+        self.mean, self.sigma = np.asarray(mean, np.float32), np.asarray(sigma, np.float32)
+        _noise_params(self.mean, self.sigma, max(self.mean.size, self.sigma.size))
+        self._struct = None
+
+    def params(self, act_dim):
+        return _noise_params(self.mean, self.sigma, act_dim)
+
+    def struct(self, act_dim):
+        """The ``ce_ddpg_noise`` of this object at ``act_dim`` (built once)."""
+        if self._struct is None or self._struct[0] != act_dim:
+            mean, sigma = self.params(act_dim)
+            c = CeDdpgNoise(kind=self.KIND, theta=float(self.theta), dt=float(self.dt))
+            for i in range(act_dim):
+                c.mean[i], c.sigma[i] = float(mean[i]), float(sigma[i])
+            self._struct = (act_dim, c)
+        return self._struct[1]
+
+    def reset(self):
+        pass
+
+    def describe(self):
+        """JSON-able constructor arguments (``from_description`` inverts)."""
+        d = {'kind': type(self).__name__, 'mean': [float(v) for v in self.mean.reshape(-1)],
+             'sigma': [float(v) for v in self.sigma.reshape(-1)]}
+        if self.KIND == _native.CE_DDPG_NOISE_OU:
+            d.update(theta=float(self.theta), dt=float(self.dt))
+        return d
+
+    @staticmethod
+    def from_description(d):
+        if d is None:
+            return None
+        mean, sigma = np.asarray(d['mean'], np.float32), np.asarray(d['sigma'], np.float32)
+        if d['kind'] == 'NormalActionNoise':
+            return NormalActionNoise(mean, sigma)
+        if d['kind'] == 'OrnsteinUhlenbeckActionNoise':
+            return OrnsteinUhlenbeckActionNoise(mean, sigma, theta=d['theta'], dt=d['dt'])
+        raise ValueError('unknown action noise %r' % (d['kind'],))
+
+
+class NormalActionNoise(ActionNoise):
+    """stable-baselines' ``NormalActionNoise(mean, sigma)``, per column."""
+    KIND = _native.CE_DDPG_NOISE_NORMAL
+
+    def noise_numpy(self, z, dtype=np.float64):
+        return normal_noise_numpy(self.mean, self.sigma, z, dtype)
+
+
+class OrnsteinUhlenbeckActionNoise(ActionNoise):
+    """stable-baselines' ``OrnsteinUhlenbeckActionNoise(mean, sigma, theta,
+    dt)`` with ``initial_noise=None``.  The object owns the process state ``x
+    [rows][A]`` (``state``, a device tensor made at the first use) and the
+    last step's ``dones`` (``last_dones``), which restart the rows whose
+    episode ended (SB's ``action_noise.reset()``)."""
+    KIND = _native.CE_DDPG_NOISE_OU
+
+    def __init__(self, mean, sigma, theta=0.15, dt=1e-2):
+        super().__init__(mean, sigma)
+        self.theta, self.dt = float(theta), float(dt)
+        if not np.isfinite(self.theta) or not self.dt > 0 or not np.isfinite(self.dt):
+            raise ValueError('theta must be finite and dt positive')
+        self.state = self.last_dones = None
+        self._pending = None         # a loaded host state, until a device is known
+
+    def step_numpy(self, x, z, reset=None, dtype=np.float64):
+        return ou_noise_numpy(x, self.mean, self.sigma, z, self.theta, self.dt, reset, dtype)
+
+    def ensure_state(self, rows, act_dim, device):
+        """``state`` and ``last_dones`` as tensors on ``device`` (a torch
+        device), zero at the first use."""
+        import torch
+        if self.state is None or tuple(self.state.shape) != (rows, act_dim) \
+                or self.state.device != device:
+            self.state = torch.zeros((rows, act_dim), dtype=torch.float32, device=device)
+            self.last_dones = torch.zeros(rows, dtype=torch.uint8, device=device)
+            if self._pending is not None:
+                x, d = self._pending
+                if x.shape == (rows, act_dim):
+                    self.state.copy_(torch.from_numpy(x))
+                    self.last_dones.copy_(torch.from_numpy(d))
+                self._pending = None
+        return self.state
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+            self.last_dones.zero_()
+        self._pending = None
+
+    def get_state(self):
+        """(x ``[rows][A]`` float32, dones ``[rows]`` uint8) as numpy, or
+        None before the first use."""
+        if self.state is None:
+            return self._pending
+        return self.state.cpu().numpy(), self.last_dones.cpu().numpy()
+
+    def set_state(self, x, dones):
+        x = np.ascontiguousarray(x, np.float32)
+        dones = np.ascontiguousarray(dones, np.uint8)
+        if x.ndim != 2 or dones.shape != (x.shape[0],):
+            raise ValueError('OU state must be [rows][A] with dones [rows]')
+        self.state = self.last_dones = None
+        self._pending = (x, dones)
+
+
+def check_generated_noise(noise, rows=None, act_dim=None):
+    """``noise=(action_noise, device_rng)``: the pair's form.  Returns it."""
+    if not isinstance(noise, tuple) or len(noise) != 2 \
+            or not isinstance(noise[0], ActionNoise) or not isinstance(noise[1], _rng.DeviceRng):
+        raise ValueError('noise must be a float32 tensor, None or (ActionNoise, DeviceRng), got %r'
+                         % (noise,))
+    if act_dim is not None:
+        noise[0].struct(act_dim)         # validates the columns once, then cached
+    if rows is not None and noise[1].row_offset + rows > 2 ** 32:
+        raise ValueError('rows row_offset .. row_offset + rows - 1 must stay below 2^32')
+    return noise
+
+
 # ----------------------------------------------------------------------- agent
 class Stats(learner.Stats):
     """The statistics of one ``grad`` / ``step`` call as a device tensor
@@ -379,13 +573,17 @@ class DDPGAgent:
         self.n_actor = n_actor_params(self.obs_dim, self.act_dim, self.hidden)
         self._lib, self._h = lib, None
         self._host_params = self._host_target = None
+        self._host_opt = None
+        self._train_scratch = None
         if device is None:      # shape only: layout, statements and validation, no GPU
+            self._host_opt = {'m': np.zeros(self.n_params, np.float32),
+                              'v': np.zeros(self.n_params, np.float32), 'step': 0}
             return
         handle = ctypes.c_void_p()
         check(lib.ce_ddpg_create(ctypes.byref(cfg), ctypes.byref(handle)), 'ce_ddpg_create')
         self._h = handle
 
-    _stream = staticmethod(MlpPolicy._stream)
+    _stream = staticmethod(_DevicePolicy._stream)
 
     def params_layout(self):
         return params_layout(self.obs_dim, self.act_dim, self.hidden)
@@ -449,6 +647,32 @@ class DDPGAgent:
         self._call('get_params', self._h, flat.ctypes.data, flat.size, flags, self._stream(stream))
         return flat
 
+    # --------------------------------------------------------- optimiser state
+    OPT_BLOCKS = ('m', 'v')
+    check_opt_state = learner.Learner.check_opt_state
+
+    def get_opt_state(self, stream=None):
+        """Adam's state as a dict: ``m`` and ``v`` (new float32 numpy vectors
+        in the flat layout) and ``step``, the shared step count.
+        Synchronises.  The shape-only agent returns what was set (zeros)."""
+        if self._h is None:
+            return {k: (v.copy() if hasattr(v, 'copy') else v) for k, v in self._host_opt.items()}
+        m, v = (np.empty(self.n_params, np.float32) for _ in self.OPT_BLOCKS)
+        step = ctypes.c_int64(0)
+        self._call('get_opt_state', self._h, m.ctypes.data, v.ctypes.data, self.n_params,
+                   ctypes.byref(step), 0, self._stream(stream))
+        return {'m': m, 'v': v, 'step': int(step.value)}
+
+    def set_opt_state(self, state, stream=None):
+        """Install a ``get_opt_state`` dict (validated first).  The
+        parameters and the targets are kept."""
+        m, v, step = self.check_opt_state(state)
+        if self._h is None:
+            self._host_opt = {'m': m.copy(), 'v': v.copy(), 'step': step}
+            return
+        self._call('set_opt_state', self._h, m.ctypes.data, v.ctypes.data, self.n_params, step, 0,
+                   self._stream(stream))
+
     # --------------------------------------------------------------------- act
     def check_act(self, obs, noise=None, out=None):
         """The form of ``act``'s tensors, then where each lives.  Returns the
@@ -456,7 +680,10 @@ class DDPGAgent:
         import torch
         rows = int(obs.shape[0]) if hasattr(obs, 'dim') and obs.dim() == 2 else -1
         check_tensor('obs', obs, torch.float32, (max(rows, 1), self.obs_dim))
-        if noise is not None:
+        generated = isinstance(noise, tuple)
+        if generated:
+            check_generated_noise(noise, max(rows, 1), self.act_dim)
+        elif noise is not None:
             check_tensor('noise', noise, torch.float32, (rows, self.act_dim))
         if out is not None:
             for name in ('action', 'env_action'):
@@ -466,27 +693,59 @@ class DDPGAgent:
         if self._h is None:
             return rows
         self.check_device('obs', obs)
-        if noise is not None:
+        if noise is not None and not generated:
             self.check_device('noise', noise)
         if out is not None:
             for name in ('action', 'env_action'):
                 self.check_device('act output ' + name, out[name])
         return rows
 
-    def act(self, obs, noise=None, out=None, stream=None):
+    def act(self, obs, noise=None, out=None, stream=None, t=None, reset=None):
         """One stream-ordered launch over ``obs [rows][D]`` for any row count
         (``noise [rows][A]`` or None: the caller's Normal or
         Ornstein-Uhlenbeck draw).  Returns ``out`` (allocated when None):
         ``action`` (normalised, what the memory stores) and ``env_action``
-        (``action * scale``, what the env reads)."""
+        (``action * scale``, what the env reads).
+
+        ``noise=(action_noise, device_rng)``: the kernel forms the noise
+        itself at draw ``t`` (default ``device_rng.t``; the generator is not
+        advanced) for the global rows ``device_rng.row_offset + r``.  An
+        Ornstein-Uhlenbeck object's state is read and written in place;
+        ``reset`` (uint8 ``[rows]`` device tensor or None) marks the rows
+        whose state reads as 0, the previous step's ``dones``."""
         import torch
         rows = self.check_act(obs, noise, out)
+        if isinstance(noise, tuple):
+            return self._act_generated(obs, rows, noise, out, stream, t, reset)
         if out is None:
             out = {n: torch.empty((rows, self.act_dim), dtype=torch.float32, device=obs.device)
                    for n in ('action', 'env_action')}
         self._call('act', self._h, obs.data_ptr(), None if noise is None else noise.data_ptr(),
                    rows, out['action'].data_ptr(), out['env_action'].data_ptr(),
                    self._stream(stream))
+        return out
+
+    def _act_generated(self, obs, rows, noise, out, stream, t, reset):
+        import torch
+        action_noise, gen = noise
+        t = int(gen.t) if t is None else int(t)
+        if not 0 <= t < 2 ** 32:
+            raise ValueError('the draw t must be in [0, 2^32), got %d' % t)
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
+        state_ptr = reset_ptr = None
+        if action_noise.KIND == _native.CE_DDPG_NOISE_OU:
+            state_ptr = action_noise.ensure_state(rows, self.act_dim, obs.device).data_ptr()
+            if reset is not None:
+                check_tensor('reset', reset, torch.uint8, (rows,))
+                self.check_device('reset', reset)
+                reset_ptr = reset.data_ptr()
+        if out is None:
+            out = {n: torch.empty((rows, self.act_dim), dtype=torch.float32, device=obs.device)
+                   for n in ('action', 'env_action')}
+        self._call('act_rng', self._h, obs.data_ptr(), rows, gen.seed, t, gen.row_offset,
+                   ctypes.byref(action_noise.struct(self.act_dim)), state_ptr, reset_ptr,
+                   out['action'].data_ptr(), out['env_action'].data_ptr(), self._stream(stream))
         return out
 
     # ------------------------------------------------------------------- batch
@@ -585,6 +844,51 @@ class DDPGAgent:
                    self._stream(stream))
         self._host_params = self._host_target = None
         return Stats(stats, y=y)
+
+    def check_train(self, memory, steps, batch_size, rng):
+        """The form of ``train``'s arguments (no GPU).  Returns (steps, n)."""
+        if not isinstance(memory, ReplayMemory):
+            raise TypeError('memory must be a ReplayMemory')
+        if not isinstance(rng, _rng.DeviceRng):
+            raise TypeError('rng must be a DeviceRng')
+        if (memory.obs_dim, memory.act_dim) != (self.obs_dim, self.act_dim):
+            raise ValueError('the memory holds obs_dim %d, act_dim %d, the agent maps %d -> %d'
+                             % (memory.obs_dim, memory.act_dim, self.obs_dim, self.act_dim))
+        if memory.size < 1:
+            raise ValueError('the memory is empty')
+        steps, n, _ = rng.check_replay(steps, batch_size, memory.size)
+        return steps, n
+
+    def train(self, memory, steps, batch_size, rng, actor_lr=None, critic_lr=None, stream=None):
+        """The train phase as ONE stream-ordered C call: one launch draws the
+        ``[steps][batch_size]`` replay indices (``rng.replay_indices`` of the
+        draws ``rng.replay_t ..`` over the memory's ``size`` valid records),
+        then ``steps`` x the five launches of ``step``.  No allocation beyond
+        the returned statistics (the index and target buffers are kept across
+        calls) and no host read; bit-equal to ``steps`` calls of
+        ``step(memory.as_batch(), idx[s])``.  Advances ``rng.replay_t`` and
+        Adam's count by ``steps``.  Returns the ``[steps][8]`` statistics, a
+        device tensor; ``Stats(result[-1])`` names its last row."""
+        import torch
+        actor_lr, critic_lr = self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
+        steps, n = self.check_train(memory, steps, batch_size, rng)
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
+        self.check_device('memory', memory.obs0)
+        dev = memory.obs0.device
+        sc = self._train_scratch
+        if sc is None or sc['idx'].shape != (steps, n) or sc['idx'].device != dev:
+            sc = self._train_scratch = {
+                'idx': torch.empty((steps, n), dtype=torch.int32, device=dev),
+                'y': torch.empty(n, dtype=torch.float32, device=dev)}
+        stats = torch.empty((steps, N_STATS), dtype=torch.float32, device=dev)
+        self._call('train', self._h, steps, n, memory.size, rng.seed, int(rng.replay_t),
+                   *[getattr(memory, f).data_ptr() for f in BATCH_FIELDS], sc['idx'].data_ptr(),
+                   sc['y'].data_ptr(), actor_lr, critic_lr, stats.data_ptr(),
+                   self._stream(stream))
+        rng.advance_replay(steps)
+        self._host_params = self._host_target = None
+        return stats
 
     def loss_grad_numpy(self, params, target_params, batch, dtype=np.float64):
         """``loss_grad_numpy`` with this agent's shape and hyper-parameters."""

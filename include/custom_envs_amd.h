@@ -471,7 +471,7 @@ int ce_multi_rollout_policy(ce_multi_engine *eng, const ce_policy *p, int32_t k,
  * NumPy): Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) at the
  * counter (row, t, block, purpose) -- the global row, the draw index, the
  * group of four values inside the row, and a tag (0 policy noise, 1
- * permutation keys, 2 predict).  Column a of a row's N(0,1) noise is element
+ * permutation keys, 2 predict, 3 DDPG action noise, 4 replay indices).  Column a of a row's N(0,1) noise is element
  * a % 4 of block a / 4 (Box-Muller on u(x) = ((x >> 8) + 0.5) 2^-24, so
  * |z| <= 5.89).  Each entry below is one plain launch on hip_stream, and every
  * argument is checked before any HIP call.
@@ -487,6 +487,17 @@ int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
                   void *hip_stream);
 int ce_rng_u32(uint32_t *out, int64_t n, uint64_t seed, uint32_t purpose, uint32_t t,
                void *hip_stream);
+/* ce_rng_normal under the caller's purpose tag (3: DDPG's action noise). */
+int ce_rng_normal_purpose(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                          int64_t record_stride_bytes, uint64_t seed, uint32_t purpose, uint32_t t0,
+                          uint32_t row0, void *hip_stream);
+/* Replay indices (purpose 4): out[s][i], s < steps, i < n (int32, contiguous,
+ * device pointer) = (w * size) >> 32 of the word w = ce_rng_u32(seed, 4,
+ * t0 + s)[i], an index in [0, size) drawn with replacement; one launch for all
+ * steps.  n and size in [1, 2^24], t0 + steps <= 2^32.  Index j is drawn with
+ * probability within size / 2^32 (relative) of 1 / size. */
+int ce_rng_replay(int32_t *out, int64_t steps, int64_t n, int64_t size, uint64_t seed, uint32_t t0,
+                  void *hip_stream);
 /* ce_policy_forward / ce_rollout_policy / ce_multi_rollout_policy with the
  * noise formed inside the policy kernel instead of read from a block: row r
  * of the call uses global row row0 + r, and step s of a rollout uses draw
@@ -792,6 +803,48 @@ int ce_ddpg_step(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const flo
                  const float *actions, const float *rewards, const float *obs1,
                  const uint8_t *dones, float *y, double actor_lr, double critic_lr,
                  float *stats, void *hip_stream);
+
+/* The action noise ce_ddpg_act_rng forms from the generator (purpose 3):
+ * z = the N(0,1) value of (global row row0 + r, draw t, column c), then per
+ * column c, in float32 with every operation rounded on its own,
+ *   CE_DDPG_NOISE_NORMAL  n  = mean + sigma * z
+ *   CE_DDPG_NOISE_OU      x' = (x + (theta * (mean - x)) * dt) + s * z,  n = x',
+ *                         s = float32(sigma * sqrt(dt)) formed in double
+ * (stable-baselines' NormalActionNoise / OrnsteinUhlenbeckActionNoise). */
+#define CE_DDPG_NOISE_NORMAL 0
+#define CE_DDPG_NOISE_OU 1
+typedef struct ce_ddpg_noise {
+    int32_t kind;        /* CE_DDPG_NOISE_*                                  */
+    double theta;        /* OU: the pull towards the mean                    */
+    double dt;           /* OU: > 0                                          */
+    float mean[64];      /* [A]                                              */
+    float sigma[64];     /* [A], >= 0                                        */
+} ce_ddpg_noise;
+/* ce_ddpg_act with the noise formed inside the kernel: action = min(max(a + n,
+ * -1), 1).  OU reads and writes ou_state [rows][A] (float32, device; the
+ * caller zeroes it to start) and reads x as 0 at the rows where reset [rows]
+ * (uint8, device, or NULL) is non-zero: the previous step's dones.  Bit-equal
+ * to ce_ddpg_act fed the same n.  CE_EINVAL: OU without ou_state, row0 + rows
+ * > 2^32.  One launch, no allocation, no synchronisation. */
+int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
+                    uint32_t row0, const ce_ddpg_noise *noise, float *ou_state,
+                    const uint8_t *reset, float *action, float *env_action, void *hip_stream);
+/* `steps` train steps in one call: ONE launch draws idx_scratch [steps][n]
+ * (ce_rng_replay at draws t0 .. t0 + steps - 1 over [0, size)), then step s is
+ * ce_ddpg_step over rows idx_scratch[s] of the size-row batch with stats
+ * [steps][8] row s; y [n] is reused by every step.  Bit-equal to the same
+ * ce_ddpg_step calls issued one by one.  Adam's count advances by steps. */
+int ce_ddpg_train(ce_ddpg *l, int32_t steps, int64_t n, int64_t size, uint64_t seed, uint32_t t0,
+                  const float *obs0, const float *actions, const float *rewards,
+                  const float *obs1, const uint8_t *dones, int32_t *idx_scratch, float *y,
+                  double actor_lr, double critic_lr, float *stats, void *hip_stream);
+/* Adam's m and v ([n] float32 each, n = ce_ddpg_n_params, the flat layout) and
+ * the shared step count, as ce_ppo2_get_opt_state / ce_ppo2_set_opt_state:
+ * host pointers synchronise, CE_PTR_DEVICE is stream-ordered. */
+int ce_ddpg_get_opt_state(ce_ddpg *l, float *m, float *v, int64_t n, int64_t *step,
+                          uint32_t flags, void *hip_stream);
+int ce_ddpg_set_opt_state(ce_ddpg *l, const float *m, const float *v, int64_t n, int64_t step,
+                          uint32_t flags, void *hip_stream);
 
 #ifdef __cplusplus
 }
