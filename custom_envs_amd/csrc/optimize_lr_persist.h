@@ -71,7 +71,21 @@ constexpr int kLpMaxTpw = 8;                  // row tiles a wave keeps in regis
 #ifndef CE_LP_LOG_HEAD
 #define CE_LP_LOG_HEAD 1
 #endif
+// the wave-specialised kernel forms W' = W - a, the auto-reset wipe, the
+// forward margins wd, the |u| bound and its tier ONCE per workgroup, on one
+// epilogue wave, and hands wd and the tier to the row waves through a small
+// LDS ring (CE_LP_WD_HANDOVER=0: every row wave forms its own copy, the
+// earlier code path).  The same operations on the same operands in the same
+// lanes, executed by another wave: no bit changes.
+#ifndef CE_LP_WD_HANDOVER
+#define CE_LP_WD_HANDOVER 1
+#endif
 __host__ __device__ constexpr bool lp_g4(int nkf) { return CE_LP_G4 && nkf <= 3; }
+// The epilogue wave that owns the weights (index among the epilogue waves):
+// the parameter roles' second round fills from epilogue wave 0 upwards and
+// the scalar role sits in the last one, so wave 2 has the least other work.
+constexpr int kLpWdWave = 2;
+constexpr int kLpWdRing = 2;                  // hand-over slots (see the ring's comment)
 
 // Row tiles per wave for N rows over W waves: the smallest of 1, 2, 4, 8
 // covering the tiles; 0 when N needs more (the caller then launches step by
@@ -489,6 +503,28 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
     __shared__ __attribute__((aligned(16))) double xgs[G4 ? 1 : W][G4 ? 1 : TPW][4][kWave];
     __shared__ __attribute__((aligned(16))) double xga[G4 ? W : 1][G4 ? TPW : 1][16][G4S];
     __shared__ double tab_s[CE_LR_TEXP ? kLrExpTab : 1];   // the row waves' exp table
+#if CE_LP_WD_HANDOVER
+    // The hand-over ring: slot s mod 2 holds step s's margins wd (lane (h, c):
+    // features 4k + h of env c, the forward B operand's layout) and its tier.
+    // The owner (epilogue wave kLpWdWave) writes; the row waves read wd(t) and
+    // the tier at the top of step t.  With "barrier t" the workgroup barrier
+    // that ends step t:
+    //   - written: wd(0), wd(1) in the prologue, ahead of the table barrier;
+    //     wd(t + 2) by the owner between barriers t and t + 1.  The row waves
+    //     read it in step t + 2, which starts behind barrier t + 1 (the
+    //     owner's LDS writes are drained before it signals a barrier);
+    //   - freed: wd(t + 2) overwrites slot t mod 2 = wd(t), which the row waves
+    //     read at the top of step t and had in registers before their first
+    //     MFMA of that step, ahead of barrier t.  The other slot holds
+    //     wd(t + 1), being read.
+    // A read one step ahead of its use (three slots, the value moved into the
+    // operand registers at the end of a step) measured slower than this form
+    // (DESIGN.md 3.11, round 17).  Nothing here depends on a step's results:
+    // all K action blocks are on the device before the launch.  Steps at or
+    // past k are never formed, so no action block at or past k is read.
+    __shared__ double wd_s[kLpWdRing][NKF][kWave];
+    __shared__ int tier_s[kLpWdRing];
+#endif
 
 #ifdef CE_DIAG
     unsigned long long lp_st[8] = {0};
@@ -509,9 +545,9 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
     const int nenv = E - e0 < kLrEnvs ? E - e0 : kLrEnvs;
 
     // One workgroup barrier before the first step, for the shared exp table
-    // (CE_LR_TEXP): a row wave's LDS tiles are its own (in-order within the
-    // wave), W0 is in its registers, and the staging buffers are the
-    // epilogue waves' alone.
+    // (CE_LR_TEXP) and the owner's first ring slots (CE_LP_WD_HANDOVER): a
+    // row wave's LDS tiles are its own (in-order within the wave), and the
+    // staging buffers are the epilogue waves' alone.
 #if CE_LR_TEXP
     // the exp table behind the image's column maxima, the first loads issued:
     // entries tid + 512 i, split over the row and the epilogue waves, one
@@ -528,6 +564,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
         // per step without it
         __builtin_amdgcn_s_setprio(CE_LP_ROW_PRIO);
 #endif
+#if !CE_LP_WD_HANDOVER
         const int e = e0 + c;
         const bool env_ok = e < E;
         const unsigned pbase = static_cast<unsigned>(env_ok ? e : 0) * P;
@@ -548,11 +585,14 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             xm[k] = colmax[f];
 #endif
         }
+#endif
         double xf[TPW][NKF];
+#if !CE_LP_WD_HANDOVER
         // W0 (the auto-reset's weights) after the first step's operands: its
         // loads are not on the way to the first step's row work
 #pragma unroll
         for (int k = 0; k < NKF; ++k) w0v[k] = *reinterpret_cast<const double2 *>(a.W0 + ioff[k]);
+#endif
         unsigned vmask = 0;
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
@@ -590,12 +630,21 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 for (int q = 0; q < 4; ++q) vmask |= (live && ys[q] >= 0 ? 1u : 0u) << (4 * i + q);
             }
         }
+#if !CE_LP_WD_HANDOVER
         int step_c = stepp[env_ok ? e : 0];
+#endif
 #if CE_LR_TEXP
         tslice.store(tab_s, tid);                           // waits on the table loads only
-        __syncthreads();
+#endif
+#if CE_LR_TEXP || CE_LP_WD_HANDOVER
+        __syncthreads();                                    // the table; the owner's wd(0), wd(1)
 #endif
         double wd[NKF];
+#if CE_LP_WD_HANDOVER
+        // a row wave keeps nothing of the weights: a step's margins and tier
+        // come from the ring at its top
+        int slot = 0;                                       // t mod 2
+#else
         auto margins = [&]() {
 #pragma unroll
             for (int k = 0; k < NKF; ++k) {
@@ -607,6 +656,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             }
         };
         margins();
+#endif
 #ifdef CE_DIAG
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -620,6 +670,16 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
         };
         for (int t = 0; t < m.k; ++t) {
             const int buf = t & 1;
+#if CE_LP_WD_HANDOVER
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) wd[k] = wd_s[slot][k][lane];
+#if CE_LR_NOCLAMP
+            const int tier = __builtin_amdgcn_readfirstlane(tier_s[slot]);
+#else
+            const int tier = kLrClamped;
+#endif
+            slot = slot == kLpWdRing - 1 ? 0 : slot + 1;
+#else
             float2 an[NKF];
             {
                 const float *actn = actp + (t + 1 < m.k ? (t + 1) * m.act_stride : 0);
@@ -633,6 +693,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             const int tier = lr_tier(ub);                   // this step's row body
 #else
             const int tier = kLrClamped;
+#endif
 #endif
             lr_d4 sacc = {0.0, 0.0, 0.0, 0.0};             // one gradient chain, tile order
             double gacc[NKF];                               // G4: one chain per feature group
@@ -755,6 +816,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 red_l[buf][wave][lane] = lsum;
                 red_h[buf][wave][lane] = hsum;
             }
+#if !CE_LP_WD_HANDOVER
             {
                 const bool wipe = step_c + 1 >= a.max_steps && a.auto_reset;
                 step_c = wipe ? 0 : step_c + 1;
@@ -770,6 +832,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                     margins();
                 }
             }
+#endif
 #ifdef CE_DIAG
             if (t == 1) LP_STAMP(7);                        // step 1's row work done
 #endif
@@ -782,6 +845,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
         }
         LP_STAMP(5);
         __syncthreads();                                    // the epilogue's last obs block
+#if !CE_LP_WD_HANDOVER
         if (wave == 0 && env_ok) {
 #pragma unroll
             for (int k = 0; k < NKF; ++k)
@@ -790,6 +854,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                     lr_store(Wp + ioff[k] + 1, wv[k].y);
                 }
         }
+#endif
     } else {
         // ==================== epilogue waves ====================
         const int te = tid - kWave * W;                     // 0 .. EB - 1
@@ -814,6 +879,87 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
         const unsigned es = srole ? e0 + sj : 0;
         double lprev = Lp[es];
         int step_s = stepp[es];
+#if CE_LP_WD_HANDOVER
+        // ---- the weights' owner: wv, w0v, the step counter and the column
+        // maxima in the row waves' lane layout (lane (h, c): features 4k + h
+        // of env c), one copy per workgroup
+        const bool wown = wave == W + kLpWdWave;
+        const int e = e0 + c;
+        const bool env_ok = e < E;
+        unsigned ioff[NKF];
+        double2 wv[NKF], w0v[NKF];
+        float2 an[NKF];                                     // the action block read one step ahead
+        [[maybe_unused]] double xm[NKF];
+        int step_c = 0;
+        // the auto-reset's W0 (utils_venv.py:31) or W' into the next step
+        auto wd_wipe = [&]() {
+            const bool wipe = step_c + 1 >= a.max_steps && a.auto_reset;
+            step_c = wipe ? 0 : step_c + 1;
+            // one step in max_steps wipes: the selects behind a uniform branch
+            if (__any(wipe)) {
+#pragma unroll
+                for (int k = 0; k < NKF; ++k)
+                    if (wipe) wv[k] = w0v[k];
+            }
+        };
+        // W' = W - a (optimize.py:74-75), the margin w'_f0 - w'_f1 of feature
+        // 4k + h for env c, the |u| bound's tier: one ring slot
+        auto wd_emit = [&](int slot, const float2 (&av)[NKF]) {
+            double wd[NKF];
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) {
+                const int f = 4 * k + h;
+                const double w0 = wv[k].x - static_cast<double>(av[k].x);
+                const double w1 = wv[k].y - static_cast<double>(av[k].y);
+                wv[k] = double2{w0, w1};
+                wd[k] = f < F ? w0 - w1 : 0.0;
+            }
+#if CE_LR_NOCLAMP
+            double ub = 0.0;
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) ub = fma(fabs(wd[k]), xm[k], ub);
+            tier_s[slot] = lr_tier(ub);                     // uniform: every lane writes the one word
+#endif
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) wd_s[slot][k][lane] = wd[k];
+        };
+        // step s's action block; the callers keep s < k
+        auto act_load = [&](int s, float2 (&av)[NKF]) {
+            const float *acts = actp + s * m.act_stride;
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) av[k] = *reinterpret_cast<const float2 *>(acts + ioff[k]);
+        };
+        if (wown) {
+            const unsigned pbase = static_cast<unsigned>(env_ok ? e : 0) * P;
+#if CE_LR_NOCLAMP
+            const double *colmax = img + static_cast<unsigned>(ntiles) * TD;
+#endif
+#pragma unroll
+            for (int k = 0; k < NKF; ++k) {
+                const int f = 4 * k + h;
+                ioff[k] = pbase + (f < F ? 2 * f : 0);
+                wv[k] = *reinterpret_cast<const double2 *>(Wp + ioff[k]);
+                w0v[k] = *reinterpret_cast<const double2 *>(a.W0 + ioff[k]);
+#if CE_LR_NOCLAMP
+                xm[k] = colmax[f];
+#endif
+            }
+            step_c = stepp[env_ok ? e : 0];
+            // steps 0 and 1 ahead of the table barrier (fewer in a shorter
+            // launch: step s is formed, and its actions read, only for s < k;
+            // the wipe behind the last step still runs, for the stored W)
+            float2 a0[kLpWdRing][NKF];
+#pragma unroll
+            for (int s = 0; s < kLpWdRing; ++s)
+                if (s < m.k) act_load(s, a0[s]);
+            if (kLpWdRing < m.k) act_load(kLpWdRing, an);
+#pragma unroll
+            for (int s = 0; s < kLpWdRing; ++s) {
+                if (s > 0 && s <= m.k) wd_wipe();
+                if (s < m.k) wd_emit(s, a0[s]);
+            }
+        }
+#endif
 #if CE_LR_TEXP
         tslice.store(tab_s, tid);
 #endif
@@ -821,7 +967,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
         double rL = rcp_newton2(lprev + 0.1);
 #pragma unroll
         for (int r = 0; r < PR; ++r) rG[r] = rcp_newton2(fabs(g_prev[r]) + 1.0);
-#if CE_LR_TEXP
+#if CE_LR_TEXP || CE_LP_WD_HANDOVER
         __syncthreads();                                    // the row waves' table barrier
 #endif
         auto flush_obs = [&](int t) {
@@ -849,6 +995,9 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 if constexpr (decltype(pow2_c)::value) return x * rB;
                 else return div_rcp(x, dB, rB);
             };
+#if CE_LP_WD_HANDOVER
+            int wslot = 0;                                      // t mod 2
+#endif
             for (int t = 0; t < m.k; ++t) {
                 const int buf = t & 1;
                 __syncthreads();                                // the row waves' partials of step t
@@ -861,6 +1010,22 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
     #ifdef CE_DIAG
                 if (t == 1) LP_STAMP(2);                        // epilogue waves: step 1 starts
     #endif
+#if CE_LP_WD_HANDOVER
+                // the owner: step t + 2 into slot t mod 2 (step t's, read at
+                // the top of step t), step t + 3's actions for the next pass;
+                // behind the last step only the wipe
+                if (wown && t + kLpWdRing <= m.k) {
+                    wd_wipe();
+                    if (t + kLpWdRing < m.k) {
+                        float2 av[NKF];
+    #pragma unroll
+                        for (int k = 0; k < NKF; ++k) av[k] = an[k];
+                        if (t + kLpWdRing + 1 < m.k) act_load(t + kLpWdRing + 1, an);
+                        wd_emit(wslot, av);
+                    }
+                }
+                wslot = wslot == kLpWdRing - 1 ? 0 : wslot + 1;
+#endif
                 if (t > 0) flush_obs(t - 1);
                 const long long ro = t * m.out_step;
                 if (srole) {
@@ -938,6 +1103,16 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
             lr_store(&Lp[es], lprev);
             lr_store(&stepp[es], step_s);
         }
+#if CE_LP_WD_HANDOVER
+        if (wown && env_ok) {
+#pragma unroll
+            for (int k = 0; k < NKF; ++k)
+                if (4 * k + h < F) {
+                    lr_store(Wp + ioff[k], wv[k].x);
+                    lr_store(Wp + ioff[k] + 1, wv[k].y);
+                }
+        }
+#endif
     }
 #ifdef CE_DIAG
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
