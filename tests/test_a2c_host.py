@@ -60,9 +60,10 @@ def _torch_loss(case, inputs, hp):
     return {k: float(v.detach()) for k, v in stats.items()}, flat.grad.numpy()
 
 
-@pytest.mark.parametrize('case', cases.CASES, ids=cases.CASE_IDS)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES,
+                         ids=cases.CASE_IDS + cases.SHAPE_CASE_IDS)
 def test_loss_grad_numpy_against_autograd(case):
-    inputs = cases.draw_case(case)
+    inputs = cases.inputs_of(case)
     ref_stats, ref_grad = _torch_loss(case, inputs, HP)
     stats, grad = loss_grad_numpy(inputs['params'], *[inputs[n] for n in FIELDS], hp=HP,
                                   hidden=inputs['hidden'], dtype=np.float64)

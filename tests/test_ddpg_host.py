@@ -1,10 +1,10 @@
 """The DDPG learner's host side (custom_envs_amd/ddpg.py, the argument checks
 of ce_ddpg_* and of collect_ddpg).  Needs the built library, no GPU.
 
-1. The layout: offsets, ``n_params`` and the C count at every case; the
-   rejected shapes.
+1. The layout: offsets, ``n_params`` and the C count at every case (CASES
+   and SHAPE_CASES); the rejected shapes.
 2. ``loss_grad_numpy`` in float64 against central differences of the two
-   losses (cases 1-4): each block within 1e-6 of the largest entry of that
+   losses (cases 1-4 and SHAPE_CASES): each block within 1e-6 of the largest entry of that
    network's gradient; the actor's loss moves no critic parameter's gradient
    and ``y`` does not move with the online parameters.
 3. ``train_step_numpy``: the targets after a step are ``soft_update_numpy`` of
@@ -28,7 +28,7 @@ from custom_envs_amd.vectorize.collect import check_collect_ddpg
 
 
 # ------------------------------------------------------------------- 1. layout
-@pytest.mark.parametrize('case', cases.CASES, ids=str)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES, ids=str)
 def test_layout_and_n_params(case):
     _, D, hidden, A, _ = case
     layout = ddpg.params_layout(D, A, hidden)
@@ -52,6 +52,16 @@ def test_layout_and_n_params(case):
     assert agent.n_params == off == ddpg.n_params(D, A, hidden)
     assert agent.n_actor == layout['critic/w0'][0] == ddpg.n_actor_params(D, A, hidden)
     assert ddpg._act_dim_of(off, D, hidden) == A
+
+
+def test_shape_cases_leave_the_draws_of_cases_alone():
+    """``draw_case`` seeds from the position in CASES + SHAPE_CASES."""
+    both = cases.CASES + cases.SHAPE_CASES
+    assert len(set(both)) == len(both)
+    assert [both.index(c) for c in cases.CASES] == list(range(len(cases.CASES)))
+    for case in cases.SHAPE_CASES:
+        inp = cases.draw_case(case)          # asserts its own margins and shares
+        assert inp['obs0'].shape == (case[0], case[1]) and inp['redraws'] >= 1
 
 
 @pytest.mark.parametrize('D, A, hidden', [(5, 2, (16,)), (5, 2, (96,)), (5, 2, (128,)),
@@ -110,7 +120,7 @@ def _losses(flat, inp):
     return np.mean((q - y) ** 2), -np.mean(qa)
 
 
-@pytest.mark.parametrize('case', cases.CASES[:4], ids=str)
+@pytest.mark.parametrize('case', cases.CASES[:4] + cases.SHAPE_CASES, ids=str)
 def test_loss_grad_against_central_differences(case):
     inp = cases.draw_case(case)
     _, D, hidden, A, _ = case

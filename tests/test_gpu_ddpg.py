@@ -1,6 +1,9 @@
 """The DDPG learner on the device (ce_ddpg_*, csrc/ddpg_kernels.h) against the
 NumPy statements of custom_envs_amd/ddpg.py in float64.
 
+Parts 1 to 3 run over ddpg_cases.CASES and SHAPE_CASES (growing widths, one 64
+layer, (32, 32), a 33-wide action), part 6 also at SHAPE_CASES[0].
+
 1. ``act`` parity at every case's shape, with and without noise: ``action``
    within 1e-5 (max|d| / max|ref|) of ``actor_numpy``; ``env_action`` bit-equal
    to the float32 product ``action * scale``; rows past the last tile's live
@@ -74,7 +77,7 @@ def _agent(case, grid_limit=None, **over):
 
 
 # ------------------------------------------------------------------ 1. act
-@pytest.mark.parametrize('case', cases.CASES, ids=str)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES, ids=str)
 def test_act_parity(case):
     import torch
     agent, inputs = _agent(case)
@@ -103,7 +106,7 @@ def test_act_parity(case):
 
 
 # --------------------------------------------------------------- 2. target
-@pytest.mark.parametrize('case', cases.CASES, ids=str)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES, ids=str)
 def test_target_parity(case):
     agent, inputs = _agent(case)
     N, hidden = case[0], case[2]
@@ -143,7 +146,7 @@ def _check(case, grad, stats, ref, what):
     assert host[4] == 0.0 and host[5] == 0.0
 
 
-@pytest.mark.parametrize('case', cases.CASES, ids=str)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES, ids=str)
 def test_gradient_parity(case):
     agent, inputs = _agent(case)
     grad, stats = agent.grad(_dev(inputs))
@@ -205,7 +208,7 @@ def test_grid_independence(grid_limit):
 
 
 # ----------------------------------------------------------------- 6. step
-@pytest.mark.parametrize('case', [cases.CASES[2], cases.CASES[5]], ids=str)
+@pytest.mark.parametrize('case', [cases.CASES[2], cases.CASES[5], cases.SHAPE_CASES[0]], ids=str)
 def test_three_steps_against_the_statement(case):
     """At the agent's default learning rates (stable-baselines': 1e-4, 1e-3).
     The bound on the parameters is not a bound on the gradient alone: the

@@ -5,7 +5,8 @@ and no second process are involved (tests/test_gpu_dp_ranks.py has those).
 
 1. PPO2 gradient parity: the global gradient and statistics of uneven shards
    within 1e-5 of ``loss_grad_numpy`` in float64 on the whole case
-   (test_gpu_ppo2.py's ``_check``), contiguous array shards and ``idx`` slices.
+   (test_gpu_ppo2.py's ``_check``: per block and per network), contiguous
+   array shards and ``idx`` slices, and array shards of the (32, 64, 96) case.
 2. A2C: the same splits, and the records-in-place form on a real ``collect``
    of K = 3 over 15 rows split [7, 6, 2] by narrowing the [K][R] views.
 3. World 1 is today's step: ``partial`` + ``apply`` of one shard leaves
@@ -29,10 +30,11 @@ from custom_envs_amd.policy import forward_numpy
 pytestmark = pytest.mark.gpu
 
 BOUND = 1e-5
+# the last: three unequal layers, D wider than each (the record follows n_params)
 SPLITS = [(cases.CASES[2], [33, 32, 5], 'array'), (cases.CASES[3], [1, 129], 'idx'),
-          (cases.CASES[4], [96, 96, 65], 'idx')]
-SPLIT_IDS = ['%s_%s_%s' % (cases.CASE_IDS[cases.CASES.index(c)], '_'.join(map(str, s)), m)
-             for c, s, m in SPLITS]
+          (cases.CASES[4], [96, 96, 65], 'idx'), (cases.SHAPE_CASES[2], [33, 32, 5], 'array')]
+_CASE_ID = dict(zip(cases.CASES + cases.SHAPE_CASES, cases.CASE_IDS + cases.SHAPE_CASE_IDS))
+SPLIT_IDS = ['%s_%s_%s' % (_CASE_ID[c], '_'.join(map(str, s)), m) for c, s, m in SPLITS]
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -153,10 +155,11 @@ def test_a2c_records_in_place_split_by_rows():
     flat0 = learner.get_params()
     ret = a2c.returns_numpy(_np(result['rewards']), _np(result['dones']),
                             _np(result['last_values']), 0.99)
-    ref = a2c.loss_grad_numpy(flat0, _np(result['obs']).reshape(K * rows, D),
-                              _np(result['actions']).reshape(K * rows, A), ret.reshape(-1),
-                              _np(result['values']).reshape(-1), hp=ta.HP, hidden=pc.ROLLOUT_HIDDEN)
-    ta._check((K * rows, D, pc.ROLLOUT_HIDDEN, A, 0), _np(grad), stats, ref, 'dp a2c in place')
+    args = (_np(result['obs']).reshape(K * rows, D), _np(result['actions']).reshape(K * rows, A),
+            ret.reshape(-1), _np(result['values']).reshape(-1))
+    ref = a2c.loss_grad_numpy(flat0, *args, hp=ta.HP, hidden=pc.ROLLOUT_HIDDEN)
+    _, g32 = a2c.loss_grad_numpy(flat0, *args, hp=ta.HP, hidden=pc.ROLLOUT_HIDDEN, dtype=np.float32)
+    ta._check((K * rows, D, pc.ROLLOUT_HIDDEN, A, 0), _np(grad), stats, ref, 'dp a2c in place', g32)
     # one shard in place is today's update, bit for bit
     whole = torch.zeros((1, learner.record_doubles), dtype=torch.float64, device='cuda')
     learner.update_partial(result, out=whole[0])

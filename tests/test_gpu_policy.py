@@ -6,7 +6,8 @@ closed-loop K-step rollout (ce_rollout_policy / ce_multi_rollout_policy).
    output array (the project's float32 bound; a float32 NumPy evaluation of
    the same inputs sits at <= 4.1e-6 from the float64 one), at row counts
    below, at and past the 32-row tile, 1- to 64-wide heads, 1 to 3 hidden
-   layers and the widest supported network; the clip bit-exact; noise=None.
+   layers and the widest supported network, and at unequal and 96-wide layers
+   (policy_cases.FORWARD_SHAPE_CASES); the clip bit-exact; noise=None.
 2. Fused equals unfused, bit for bit: ``rollout_policy(k=10)`` against ten
    ``forward_device`` + ``step_device`` pairs on an identically seeded engine.
 3. The closed loop is policy o env: every recorded action / value / neglogp
@@ -40,7 +41,8 @@ def _np(t):
 
 
 # ------------------------------------------------------------ 1. forward parity
-@pytest.mark.parametrize('case', pc.FORWARD_CASES, ids=lambda c: 'r%d_d%d_a%d' % (c[0], c[1], c[3]))
+@pytest.mark.parametrize('case', pc.FORWARD_CASES + pc.FORWARD_SHAPE_CASES,
+                         ids=pc.FORWARD_IDS + pc.FORWARD_SHAPE_IDS)
 def test_forward_parity(case):
     import torch
     rows, D, hidden, A = case

@@ -4,8 +4,9 @@ instance against the explicit-noise one, bit for bit.
 
 Shapes where the kernel can go wrong: rows 1, 33 (a tile edge) and 70 (a
 ragged third tile); act_dim 1, 3 (a partial block), 4 (one block), 20 and 64
-(the 8-thread neglogp sums wrap); hidden (32,) and (64, 64); t0 and row0
-non-zero; a seed with a non-zero high word.
+(the 8-thread neglogp sums wrap); hidden (32,), (64, 64), (96,) (the fourth
+wave idle) and (32, 128) (growing); t0 and row0 non-zero; a seed with a
+non-zero high word.
 
 The normals' bound, 1e-5 absolute against the float64 statement: every
 argument of logf / log1pf / sincospif is exact (rng.h), the functions are
@@ -105,7 +106,8 @@ def test_normal_strided_records():
 
 
 # ---------------------------- 2. forward_device(noise=rng) == explicit, bit for bit
-@pytest.mark.parametrize('hidden', [(32,), (64, 64)], ids=['h32', 'h64x64'])
+@pytest.mark.parametrize('hidden', [(32,), (64, 64), (96,), (32, 128)],
+                         ids=['h32', 'h64x64', 'h96', 'h32x128'])
 @pytest.mark.parametrize('act_dim', ACT_DIMS)
 @pytest.mark.parametrize('rows', ROWS)
 def test_forward_generated_equals_explicit(rows, act_dim, hidden):

@@ -61,8 +61,15 @@ def test_forward_numpy_matches_an_independent_mlp():
 
 
 # ----------------------------------------------------------------------- layout
+_SHAPE_CASES = __import__('policy_cases').FORWARD_SHAPE_CASES      # unequal and 96-wide layers
+
+
 @pytest.mark.parametrize('shape', [(5, 2, (32,)), (41, 20, (64, 64)), (128, 64, (128, 128, 128)),
-                                   (15, 1, (64, 32))])
+                                   (15, 1, (64, 32))] +
+                         [(D, A, hidden) for _, D, hidden, A in _SHAPE_CASES],
+                         ids=['shape%d' % i for i in range(4)] +
+                         ['d%d_a%d_h%s' % (D, A, 'x'.join(map(str, hidden)))
+                          for _, D, hidden, A in _SHAPE_CASES])
 def test_layout_round_trips_and_matches_the_library(shape):
     D, A, hidden = shape
     layout = params_layout(D, A, hidden)

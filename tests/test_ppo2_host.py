@@ -4,7 +4,9 @@ before the first HIP call) and PPO2Learner's tensor validation.
 
 1. ``loss_grad_numpy`` (hand-written backprop) in float64 against torch
    autograd on a torch restatement of the loss written here, every case of
-   ppo2_cases: gradient and every statistic within 1e-9 norm-relative.
+   ppo2_cases (CASES and SHAPE_CASES): gradient and every statistic within
+   1e-9 norm-relative.  ``ppo2_cases.net_errs`` refuses a 1e-4 relative error
+   of the value network that ``block_errs`` lets through.
 2. ``gae_numpy`` against a literal loop, an episode end in the middle and at
    t = K - 1.
 3. ``adam_step_numpy`` against TF-style Adam restated with torch tensors over
@@ -70,9 +72,10 @@ def _torch_loss(case, inputs, hp):
 @pytest.mark.parametrize('hp', [cases.HP, cases.HP._replace(cliprange_vf=-1.0, normalize_adv=False),
                                 cases.HP._replace(cliprange_vf=None)],
                          ids=['default', 'no_vclip_no_norm', 'vclip_from_cliprange'])
-@pytest.mark.parametrize('case', cases.CASES, ids=cases.CASE_IDS)
+@pytest.mark.parametrize('case', cases.CASES + cases.SHAPE_CASES,
+                         ids=cases.CASE_IDS + cases.SHAPE_CASE_IDS)
 def test_loss_grad_numpy_against_autograd(case, hp):
-    inputs = cases.draw_case(case)
+    inputs = cases.inputs_of(case)
     ref_stats, ref_grad = _torch_loss(case, inputs, hp)
     stats, grad = loss_grad_numpy(inputs['params'], *[inputs[n] for n in cases.BATCH_FIELDS],
                                   hp=hp, hidden=inputs['hidden'], dtype=np.float64)
@@ -97,10 +100,74 @@ def test_loss_grad_numpy_runs_in_float32():
 
 def test_case_generator_covers_both_branches():
     """What draw_case asserts, seen from outside: margins and branch shares."""
-    for case in cases.CASES:
-        inputs = cases.draw_case(case)
+    for case in cases.CASES + cases.SHAPE_CASES:
+        inputs = cases.inputs_of(case)
         assert all(inputs[n].dtype == np.float32 for n in cases.BATCH_FIELDS)
         assert np.any(np.abs(inputs['obs']) > 50) or case[0] < 8       # saturated rows
+        assert inputs['hidden'] == case[2] and inputs['grid_limit'] == case[4]
+
+
+def test_pg_terms_are_pg_loss_and_cases_do_not_cancel():
+    """``pg_terms`` restates the statement's pg_loss row by row, and on CASES
+    its condition number stays below ``PG_COND_MAX``: test_gpu_ppo2.py holds
+    pg_loss to 1e-5 of itself there.  Three of the SHAPE_CASES cancel."""
+    cancelling = []
+    for case in cases.CASES + cases.SHAPE_CASES:
+        inputs = cases.inputs_of(case)
+        for hp in (cases.HP, cases.HP._replace(cliprange_vf=-1.0, normalize_adv=False)):
+            stats, _ = loss_grad_numpy(inputs['params'], *[inputs[n] for n in cases.BATCH_FIELDS],
+                                       hp=hp, hidden=inputs['hidden'])
+            terms = cases.pg_terms(inputs, hp)
+            assert terms.shape == (case[0],)
+            assert abs(terms.mean() - float(stats['pg_loss'])) <= 1e-12 * max(np.abs(terms).mean(), 1e-300)
+        terms = cases.pg_terms(inputs)
+        pg = float(terms.mean())
+        cond = float(np.abs(terms).mean() / abs(pg)) if pg != 0.0 else 0.0
+        print(case, 'pg_loss %.4g condition %.1f' % (pg, cond))
+        if case in cases.CASES:
+            assert cond <= cases.PG_COND_MAX, (case, cond)
+        elif cond > cases.PG_COND_MAX:
+            cancelling.append(case[2])
+    assert cancelling == [(32, 128), (96, 96), (64, 96, 128)]
+
+
+def test_net_errs_sees_what_block_errs_hides():
+    """A 1e-4 relative error over the whole value network passes ``block_errs``
+    at 1e-5, because that measure divides by the largest entry of the whole
+    gradient, the policy network's, and the value network's entries are 25
+    times smaller on this case; ``net_errs`` divides by the network's own
+    largest entry, and its bound (twice the float32 statement's own error, at
+    least 1e-5) refuses it."""
+    case = cases.CASES[4]
+    inputs = cases.inputs_of(case)
+    args = [inputs[n] for n in cases.BATCH_FIELDS]
+    _, ref = loss_grad_numpy(inputs['params'], *args, hp=cases.HP, hidden=inputs['hidden'])
+    _, g32 = loss_grad_numpy(inputs['params'], *args, hp=cases.HP, hidden=inputs['hidden'],
+                             dtype=np.float32)
+    wrong = ref.copy()
+    for name, sl in cases.blocks(case).items():
+        if name.startswith('vf/'):
+            wrong[sl] *= 1.0 + 1e-4
+    old, new = cases.block_errs(case, wrong, ref), cases.net_errs(case, wrong, ref)
+    bounds = cases.net_bounds(case, g32, ref)
+    print('block_errs worst %.3g, net_errs %s, bounds %s' % (max(old.values()), new, bounds))
+    assert set(new) == set(bounds) == {'pi', 'vf', 'logstd'}
+    assert max(old.values()) <= 1e-5                        # the gap
+    assert new['vf'] == pytest.approx(1e-4, rel=1e-6) and new['vf'] > bounds['vf']
+    assert new['pi'] == 0.0 and new['logstd'] == 0.0
+    # the bound is the reference's: twice the float32 statement's own error
+    e32 = cases.net_errs(case, g32, ref)
+    assert bounds == {net: max(1e-5, 2.0 * e) for net, e in e32.items()}
+    # a network whose reference is all zero is measured on the whole gradient's scale
+    one = cases.CASES[0]
+    inp = cases.inputs_of(one)
+    _, ref1 = loss_grad_numpy(inp['params'], *[inp[n] for n in cases.BATCH_FIELDS], hp=cases.HP,
+                              hidden=inp['hidden'])
+    sl = cases.blocks(one)['vf/w0']
+    assert not ref1[sl].any()
+    off = ref1.copy()
+    off[sl.start] = 1e-3 * np.abs(ref1).max()
+    assert cases.net_errs(one, off, ref1)['vf'] == pytest.approx(1e-3)
 
 
 # ------------------------------------------------------------------------ 2. GAE
