@@ -59,6 +59,7 @@ EXPORTS = (
     'ce_a2c_set_opt_state',
     'ce_rng_normal_purpose', 'ce_rng_replay', 'ce_ddpg_act_rng', 'ce_ddpg_train',
     'ce_ddpg_get_opt_state', 'ce_ddpg_set_opt_state',
+    'ce_ddpg_record_bytes', 'ce_ddpg_partial', 'ce_ddpg_combine', 'ce_ddpg_apply',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -291,6 +292,10 @@ def _declare(lib):
                            vp], ctypes.c_int),
         'ce_ddpg_get_opt_state': ([vp, vp, vp, i64, ctypes.POINTER(i64), u32, vp], ctypes.c_int),
         'ce_ddpg_set_opt_state': ([vp, vp, vp, i64, i64, u32, vp], ctypes.c_int),
+        'ce_ddpg_record_bytes': ([vp], ctypes.c_int64),
+        'ce_ddpg_partial': ([vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_ddpg_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_ddpg_apply': ([vp, i32, vp, i64, f64, f64, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

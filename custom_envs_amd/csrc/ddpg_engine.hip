@@ -9,6 +9,9 @@
 //   ce_ddpg_step    [target, gradient, reduce, statistics, update]    (five)
 //   ce_ddpg_act_rng [act, the noise formed in the kernel]
 //   ce_ddpg_train   [replay indices] + steps x the five of ce_ddpg_step
+//   ce_ddpg_partial [target, gradient with 1 / n_total, partial]   (one rank's record)
+//   ce_ddpg_combine [combine, statistics]                  (from the W records)
+//   ce_ddpg_apply   [combine, statistics, update]
 // where update is Adam on both blocks, the soft update and both images'
 // repack.  Every argument check precedes the first HIP call, and the checks of
 // the plain arguments precede the check of the handle, so they run without a
@@ -192,14 +195,16 @@ void enqueue_target(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, 
                        stream, g);
 }
 
-// [target, gradient, reduce, statistics] into y / grad / stats
-void enqueue_grad(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
-                  const float *actions, const float *rewards, const float *obs1,
-                  const uint8_t *dones, float *y, float *grad, float *stats, hipStream_t stream) {
+// [target, gradient] of this call's n rows with the row weight 1 / n_total
+// into y and the slab; returns the gradient kernel's workgroups per branch
+int enqueue_slab(const ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                 const float *obs0, const float *actions, const float *rewards, const float *obs1,
+                 const uint8_t *dones, float *y, hipStream_t stream) {
     enqueue_target(l, n, m, idx, obs1, rewards, dones, y, stream);
     ce::DdpgGradArgs g{};
     g.p = l->plan;
     g.n = static_cast<int>(n);
+    g.n_total = static_cast<int>(n_total);
     g.m = static_cast<int>(m);
     g.tiles = static_cast<int>((n + ce::kDdpgTile - 1) / ce::kDdpgTile);
     g.grid = std::min(g.tiles, l->grid_max);
@@ -212,15 +217,57 @@ void enqueue_grad(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, co
     g.stat_slab = l->stat_slab;
     hipLaunchKernelGGL(ce::ddpg_grad_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock), l->lds_grad,
                        stream, g);
+    return g.grid;
+}
+
+// [target, gradient, reduce, statistics] into y / grad / stats
+void enqueue_grad(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs0,
+                  const float *actions, const float *rewards, const float *obs1,
+                  const uint8_t *dones, float *y, float *grad, float *stats, hipStream_t stream) {
+    const int grid = enqueue_slab(l, n, n, m, idx, obs0, actions, rewards, obs1, dones, y, stream);
     ce::DdpgReduceArgs q{};
     q.p = l->plan;
-    q.grid = g.grid;
+    q.grid = grid;
     q.slab = l->slab;
     q.grad = grad;
     const int np = l->plan.n_params;
     hipLaunchKernelGGL(ce::ddpg_reduce_kernel, dim3((np + 255) / 256), dim3(256), 0, stream, q);
-    hipLaunchKernelGGL(ce::ddpg_stats_kernel, dim3(1), dim3(256), 0, stream, g.n, g.grid, np,
-                       l->plan.n_actor, l->stat_slab, grad, stats);
+    hipLaunchKernelGGL(ce::ddpg_stats_kernel, dim3(1), dim3(256), 0, stream, static_cast<int>(n),
+                       grid, 2 * ce::kDdpgRowStats, np, l->plan.n_actor, l->stat_slab, grad, stats);
+}
+
+// [combine, statistics] from the W gathered records into grad / stats
+void enqueue_combine(const ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
+                     float *grad, float *stats, hipStream_t stream) {
+    const int np = l->plan.n_params;
+    ce::DdpgCombineArgs q{};
+    q.n_params = np;
+    q.world = world;
+    q.record_doubles = ce::ddpg_record_doubles(np);
+    q.records = records;
+    q.grad = grad;
+    hipLaunchKernelGGL(ce::ddpg_combine_kernel, dim3((np + 255) / 256), dim3(256), 0, stream, q);
+    hipLaunchKernelGGL(ce::ddpg_stats_kernel, dim3(1), dim3(256), 0, stream,
+                       static_cast<int>(n_total), world, q.record_doubles, np, l->plan.n_actor,
+                       records + np, grad, stats);
+}
+
+constexpr int64_t kMaxTotalRows = int64_t(1) << 30;
+constexpr int kMaxWorld = 1 << 16;
+
+// world, the gathered records, n_total and stats of an apply / combine call
+int records_ok(const char *who, const ce_ddpg *l, int32_t world, const double *records,
+               int64_t n_total, const float *stats) {
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    if (world < 1 || world > kMaxWorld)
+        return bad(": world must be in [1, 2^16], got " + std::to_string(world));
+    if (n_total < 1 || n_total > kMaxTotalRows)
+        return bad(": n_total must be in [1, 2^30], got " + std::to_string(n_total));
+    if (!records) return bad(": null records");
+    if (reinterpret_cast<uintptr_t>(records) & 7) return bad(": the records must be 8-byte aligned");
+    if (!stats) return bad(": null stats");
+    if (!l) return bad(": null learner");
+    return CE_OK;
 }
 
 // [update] from l->grad: Adam on both blocks, one more step; soft update; images.
@@ -512,6 +559,73 @@ int ce_ddpg_train(ce_ddpg *l, int32_t steps, int64_t n, int64_t size, uint64_t s
                      l->grad, stats + s * 8, stream);
         enqueue_update(l, actor_lr, critic_lr, stream);
     }
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int64_t ce_ddpg_record_bytes(const ce_ddpg *l) {
+    if (!l) {
+        fail(CE_EINVAL, "ce_ddpg_record_bytes: null learner");
+        return -1;
+    }
+    return int64_t(ce::ddpg_record_doubles(l->plan.n_params)) * 8;
+}
+
+int ce_ddpg_partial(ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                    const float *obs0, const float *actions, const float *rewards,
+                    const float *obs1, const uint8_t *dones, float *y, double *record,
+                    void *hip_stream) {
+    const char *who = "ce_ddpg_partial";
+    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
+    int rc = rows_ok(who, n, m, idx);
+    if (rc != CE_OK) return rc;
+    if (n_total < n || n_total > kMaxTotalRows)
+        return bad(": n_total must be in [n, 2^30], got " + std::to_string(n_total) + " for n = " +
+                   std::to_string(n));
+    if (!record) return bad(": null record");
+    if (reinterpret_cast<uintptr_t>(record) & 7) return bad(": the record must be 8-byte aligned");
+    // `record` stands in for stats in the null checks the entry points share
+    rc = batch_ok(who, l, n, m, idx, obs0, actions, rewards, obs1, dones, y,
+                  reinterpret_cast<const float *>(record));
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    ce::DdpgPartialArgs q{};
+    q.p = l->plan;
+    q.n = static_cast<int>(n);
+    q.grid = enqueue_slab(l, n, n_total, m, idx, obs0, actions, rewards, obs1, dones, y, stream);
+    q.slab = l->slab;
+    q.stat_slab = l->stat_slab;
+    q.record = record;
+    hipLaunchKernelGGL(ce::ddpg_partial_kernel, dim3((l->plan.n_params + 255) / 256), dim3(256), 0,
+                       stream, q);
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_combine(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
+                    float *grad, float *stats, void *hip_stream) {
+    const char *who = "ce_ddpg_combine";
+    if (!grad) return fail(CE_EINVAL, std::string(who) + ": null grad");
+    const int rc = records_ok(who, l, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    enqueue_combine(l, world, records, n_total, grad, stats, static_cast<hipStream_t>(hip_stream));
+    CE_HIP(hipGetLastError());
+    return CE_OK;
+}
+
+int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
+                  double actor_lr, double critic_lr, float *stats, void *hip_stream) {
+    const char *who = "ce_ddpg_apply";
+    if (std::isnan(actor_lr) || std::isnan(critic_lr))
+        return fail(CE_EINVAL, std::string(who) + ": a learning rate is not a number");
+    const int rc = records_ok(who, l, world, records, n_total, stats);
+    if (rc != CE_OK) return rc;
+    CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    enqueue_combine(l, world, records, n_total, l->grad, stats, stream);
+    enqueue_update(l, actor_lr, critic_lr, stream);
     CE_HIP(hipGetLastError());
     return CE_OK;
 }

@@ -36,12 +36,20 @@
 //             action, the critic's backward to dQ / d action only (no dW; relu
 //             masks from the kept activations) started from dZ = -1 / N, the
 //             head's dZ = that o (1 - a^2), the actor's backward with dW, db.
-//     Rows past N contribute exact zeros (their head dZ is 0).  The partials
-//     leave the workgroup once, as partial x of a slab of images.
+//     Rows past n contribute exact zeros (their head dZ is 0).  N is the
+//     call's n_total: its own n, or every rank's rows under a gradient
+//     exchange.  The partials leave the workgroup once, as partial x of a
+//     slab of images.
 // ddpg_reduce_kernel   grad[p] = the G partials of parameter p's image element,
 //                      added in workgroup order in float64, rounded once.
-// ddpg_stats_kernel    one workgroup: the statistic sums over G in order and
-//                      the two squared gradient norms, float64.
+// ddpg_stats_kernel    one workgroup: the statistic sums over the partials (the
+//                      G workgroups' of the slab, or the W ranks' inside their
+//                      records) in order and the two squared gradient norms,
+//                      float64.
+// ddpg_partial_kernel  the reduce kernel's sums left in float64, with the
+// ddpg_combine_kernel  statistic sums and the row count, as one rank's record;
+//                      the W records added in rank order and rounded once (the
+//                      gradient exchange, below the reduce kernel).
 // ddpg_update_kernel   per parameter: Adam (TF form, eps outside the root, the
 //                      block's own lr_t), the soft update with its float32
 //                      multiplies and adds unfused and in the statement's
@@ -523,6 +531,7 @@ __global__ __launch_bounds__(kDdpgBlock) void ddpg_target_kernel(const DdpgTarge
 struct DdpgGradArgs {
     DdpgPlan p;
     int n, m, tiles, grid;
+    int n_total;             // the N of 1 / N: n, or every rank's rows together
     const float *img;        // the online image
     const int32_t *idx;
     const float *obs0, *actions;
@@ -539,7 +548,7 @@ __global__ __launch_bounds__(kDdpgBlock) void ddpg_grad_kernel(const DdpgGradArg
     const int li = lane & 31, h = lane >> 5;
     const int branch = blockIdx.y;
     const int L = a.n_hidden, h0 = a.out_dim[1][0];
-    const float inv_n = 1.0f / static_cast<float>(g.n);
+    const float inv_n = 1.0f / static_cast<float>(g.n_total);
     float *const axs[kDdpgLayers] = {s.buf[0], s.buf[1], s.buf[2]};
     float *const cxs[kDdpgLayers] = {s.buf[0], s.buf[3], s.buf[4]};
     float *c1 = s.buf[3], *dzh = s.buf[5];
@@ -686,11 +695,13 @@ __device__ __forceinline__ double ddpg_block_sum(double v, double *red) {
     return red[0];
 }
 
-// One workgroup: the statistics of n rows from the G partials, and the two
-// blocks' squared gradient norms.
-__global__ __launch_bounds__(256) void ddpg_stats_kernel(int n, int grid, int n_params, int n_actor,
-                                                         const double *stat_slab, const float *grad,
-                                                         float *stats) {
+// One workgroup: the statistics of n rows from `parts` statistic partials,
+// `stat_stride` doubles apart (the G workgroups' of stat_slab, or the W ranks'
+// inside their records), and the two blocks' squared gradient norms.
+__global__ __launch_bounds__(256) void ddpg_stats_kernel(int n, int parts, int stat_stride,
+                                                         int n_params, int n_actor,
+                                                         const double *stat_parts,
+                                                         const float *grad, float *stats) {
     __shared__ double red[256];
     __shared__ double sums[2 * kDdpgRowStats];
     const int tid = threadIdx.x;
@@ -706,7 +717,7 @@ __global__ __launch_bounds__(256) void ddpg_stats_kernel(int n, int grid, int n_
     const double critic_sq = ddpg_block_sum(sc, red);
     if (tid < 2 * kDdpgRowStats) {
         double t = 0.0;
-        for (int gi = 0; gi < grid; ++gi) t += stat_slab[static_cast<long long>(gi) * 2 * kDdpgRowStats + tid];
+        for (int gi = 0; gi < parts; ++gi) t += stat_parts[static_cast<long long>(gi) * stat_stride + tid];
         sums[tid] = t;
     }
     __syncthreads();
@@ -720,6 +731,71 @@ __global__ __launch_bounds__(256) void ddpg_stats_kernel(int n, int grid, int n_
         stats[6] = static_cast<float>(critic_sq);
         stats[7] = static_cast<float>(actor_sq);
     }
+}
+
+// ------------------------------------------------------ the gradient exchange
+// W ranks, rank r with n_r rows, take the single agent's step on all N = sum
+// n_r rows: each runs [target, gradient with 1 / N, partial] into slot r of a
+// [W][record] buffer, the caller all-gathers the buffer in place, and each
+// runs [combine, statistics, update].  One rank's record, float64:
+//   [ n_params sums | 2 * kDdpgRowStats statistic sums | n_r | zeros ]
+// padded to a multiple of 256 B.  Every rank adds the same float64 values in
+// rank order, so every rank gets the same bits; at W = 1 they are the bits of
+// [gradient, reduce, statistics] (0.0 + x is x, and the one rounding to
+// float32 is the reduce kernel's).
+__host__ __device__ constexpr int ddpg_record_doubles(int n_params) {
+    return (n_params + 2 * kDdpgRowStats + 1 + 31) / 32 * 32;
+}
+
+struct DdpgPartialArgs {
+    DdpgPlan p;
+    int grid, n;             // this rank's workgroups per branch and rows
+    const float *slab;
+    const double *stat_slab;
+    double *record;          // [ddpg_record_doubles(n_params)]
+};
+
+// The reduce kernel's grid and sum, left unrounded.  Block 0 also folds the
+// statistic sums over the G workgroups (the statistics kernel's loop) and
+// writes the row count and the padding.
+__global__ __launch_bounds__(256) void ddpg_partial_kernel(const DdpgPartialArgs q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < q.p.n_params) {
+        const float *at = q.slab + ddpg_image_pos(q.p, p);
+        double sum = 0.0;
+        for (int gi = 0; gi < q.grid; ++gi) sum += at[static_cast<long long>(gi) * q.p.img_floats];
+        q.record[p] = sum;
+    }
+    if (blockIdx.x == 0) {
+        const int tid = threadIdx.x;
+        if (tid < 2 * kDdpgRowStats) {
+            double t = 0.0;
+            for (int gi = 0; gi < q.grid; ++gi)
+                t += q.stat_slab[static_cast<long long>(gi) * 2 * kDdpgRowStats + tid];
+            q.record[q.p.n_params + tid] = t;
+        } else if (tid < ddpg_record_doubles(q.p.n_params) - q.p.n_params) {
+            // the row count, then zeros to the record's padded end (at most
+            // 2 * kDdpgRowStats + 1 + 31 entries: one block covers them)
+            q.record[q.p.n_params + tid] = tid == 2 * kDdpgRowStats ? static_cast<double>(q.n) : 0.0;
+        }
+    }
+}
+
+struct DdpgCombineArgs {
+    int n_params, world, record_doubles;
+    const double *records;   // [world][record_doubles]
+    float *grad;             // [n_params]
+};
+
+// grad[p] = the W records' values of parameter p added in rank order in
+// float64, rounded once.  The statistics kernel takes its norms from grad.
+__global__ __launch_bounds__(256) void ddpg_combine_kernel(const DdpgCombineArgs q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q.n_params) return;
+    double sum = 0.0;
+    for (int r = 0; r < q.world; ++r)
+        sum += q.records[static_cast<long long>(r) * q.record_doubles + p];
+    q.grad[p] = static_cast<float>(sum);
 }
 
 // --------------------------------------- Adam x2, soft update, both images

@@ -59,9 +59,21 @@ obs_dim <= 128, act_dim <= 64.  Anything else raises ``NativeEngineError``
 (CE_EUNSUPPORTED); there is no eager fallback.
 
 Out of scope: parameter noise and layer norm (``LnMlpPolicy``), observation
-and return normalisation, pop-art, ``critic_l2_reg``, ``clip_norm``, DDPG
-under ``distributed.GradientExchange``, graph capture of the loop, a C-side
-``[act, env step] x K`` rollout (the collect loop stays Python-issued).
+and return normalisation, pop-art, ``critic_l2_reg``, ``clip_norm``, graph
+capture of the loop, a C-side ``[act, env step] x K`` rollout (the collect
+loop stays Python-issued), an uneven ``batch_size`` per rank.
+
+Data-parallel training (``distributed.GradientExchange(agent, rank, world)``,
+as stable-baselines' MPI workers average gradients through ``MpiAdam``): W
+ranks, rank r holding n_r sampled rows of its own memory, take the single
+agent's train step on the concatenation, N = sum n_r.  ``partial`` writes the
+rank's float64 record (``learner.pack_record_numpy``'s layout: the per
+parameter sums of its rows' gradient terms weighted 1 / N, before any
+rounding, the statistic sums, n_r), ONE in-place all-gather gives every rank
+every record, and ``apply`` adds them in rank order and rounds once
+(``combine_records_numpy``), so the replicas stay bit-identical; at W = 1
+``partial`` + ``apply`` leave the bits of ``step``.  With an exchange attached
+``step`` / ``grad`` / ``train`` do this themselves.
 """
 import ctypes
 from collections import OrderedDict, namedtuple
@@ -318,6 +330,19 @@ def train_step_numpy(params, target_params, m, v, t, batch, n_actor, hp=HyperPar
         for dst, src in zip(new, out):
             dst[block] = src
     return new[0], soft_update_numpy(target_params, new[0], tau), new[1], new[2], stats
+
+
+# ---------------------------------------------------- the gradient exchange
+# One rank's record is ``learner.pack_record_numpy``'s: ``[n_params sums | 2 *
+# ROW_STATS statistic sums | n_r]`` in float64, padded to a multiple of 256 B
+# (``learner.record_doubles``); the sums are ``loss_grad_numpy`` of the rank's
+# rows weighted ``n_r / N``.
+def combine_records_numpy(records, n_params, dtype=np.float64):
+    """The statement of ``partial`` + ``combine``: the gradient of all the
+    ranks' rows from their records ``[W][>= n_params]``, added in rank order
+    in float64, then rounded to ``dtype`` (``learner.combine_records_numpy``
+    without an entropy term)."""
+    return learner.combine_records_numpy(records, n_params, 0, 0.0, dtype)
 
 
 # ----------------------------------------------------------------------- noise
@@ -807,6 +832,11 @@ class DDPGAgent:
         """Both loss gradients of the rows ``idx`` (None: all) of ``batch``,
         no update.  Returns (grad ``[n_params]`` device tensor, ``Stats``)."""
         import torch
+        if self.exchange is not None:      # the gradient of every rank's rows
+            records, n_total, y = self._exchange_records(batch, idx, stream)
+            grad, stats = self.combine(records, n_total, stream=stream)
+            stats.y = y
+            return grad, stats
         head, N = self._head(batch, idx)
         dev = batch['obs0'].device
         grad = torch.empty(self.n_params, dtype=torch.float32, device=dev)
@@ -815,6 +845,114 @@ class DDPGAgent:
         self._call('grad', *head, y.data_ptr(), grad.data_ptr(), stats.data_ptr(),
                    self._stream(stream))
         return grad, Stats(stats, y=y)
+
+    # ------------------------------------------------------- gradient exchange
+    # W ranks, rank r holding n_r sampled rows, take the single agent's train
+    # step on the concatenation, N = sum n_r: ``partial`` (target, gradient
+    # with 1 / N, this rank's float64 record), the caller's all-gather of the
+    # ``[W][record]`` buffer, ``apply`` (combine in rank order, statistics,
+    # Adam x2 + soft update).  Every rank computes the same bits; at W = 1 they
+    # are ``step``'s.
+    exchange = None      # a distributed.GradientExchange attaches itself here
+
+    @property
+    def record_doubles(self):
+        return learner.record_doubles(self.n_params)
+
+    def check_record_tensor(self, name, t, shape):
+        """A float64 tensor the exchange kernels read or write: dtype, shape,
+        contiguity, then (with a handle) the device."""
+        import torch
+        check_tensor(name, t, torch.float64, shape)
+        if self._h is not None:
+            self.check_device(name, t)
+
+    check_total = staticmethod(learner.Learner.check_total)
+
+    @staticmethod
+    def _rows_of(batch, idx):
+        t = idx if idx is not None else batch.get('obs0')
+        return int(t.shape[0]) if hasattr(t, 'dim') and t.dim() >= 1 else 0
+
+    def partial(self, batch, idx=None, n_total=None, out=None, stream=None, y=None):
+        """This rank's share of a train step of ``n_total`` rows (None: its
+        own ``n``): the targets and both loss gradients of the rows ``idx``
+        with the row weight ``1 / n_total``, as one float64 record in ``out``
+        (``[record_doubles]``; None: a new tensor).  ``y`` (float32 ``[N]``
+        or None: a new tensor) receives the rows' targets.  Returns the
+        record."""
+        return self._partial(batch, idx, n_total, out, y, stream)[0]
+
+    def _partial(self, batch, idx, n_total, out, y, stream):
+        """``partial``: (the record, y)."""
+        import torch
+        n_total = self.check_total(self._rows_of(batch, idx), n_total)
+        if out is not None:
+            self.check_record_tensor('out', out, (self.record_doubles,))
+        M, N = self.check_batch(batch, idx)
+        if y is not None:
+            check_tensor('y', y, torch.float32, (N,))
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
+        dev = batch['obs0'].device
+        if y is None:
+            y = torch.empty(N, dtype=torch.float32, device=dev)
+        else:
+            self.check_device('y', y)
+        if out is None:
+            out = torch.zeros(self.record_doubles, dtype=torch.float64, device=dev)
+        self._call('partial', self._h, N, n_total, M, None if idx is None else idx.data_ptr(),
+                   *[batch[n].data_ptr() for n in BATCH_FIELDS], y.data_ptr(), out.data_ptr(),
+                   self._stream(stream))
+        return out, y
+
+    def _records_head(self, records, n_total, stats=None):
+        """The checked leading arguments of ``combine`` / ``apply`` and the
+        statistics tensor the call writes."""
+        import torch
+        if not hasattr(records, 'dim') or records.dim() != 2:
+            raise ValueError('records must have shape [world][%d]' % self.record_doubles)
+        world = int(records.shape[0])
+        self.check_record_tensor('records', records, (world, self.record_doubles))
+        n_total = int(n_total)
+        if world < 1 or n_total < 1:
+            raise ValueError('records of %d ranks and n_total = %d' % (world, n_total))
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
+        if stats is None:
+            stats = torch.empty(N_STATS, dtype=torch.float32, device=records.device)
+        else:
+            check_tensor('stats', stats, torch.float32, (N_STATS,))
+            self.check_device('stats', stats)
+        return [self._h, world, records.data_ptr(), n_total], stats
+
+    def combine(self, records, n_total, stream=None):
+        """The gradient and statistics of all ``n_total`` rows from the ranks'
+        records ``[world][record_doubles]``, no update.  Returns (grad,
+        ``Stats``)."""
+        import torch
+        head, stats = self._records_head(records, n_total)
+        grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
+        self._call('combine', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
+        return grad, Stats(stats)
+
+    def apply(self, records, n_total, actor_lr=None, critic_lr=None, stream=None, stats=None):
+        """Combine, statistics, then ``step``'s update (Adam on both blocks,
+        one step; the soft update; both images) from the ranks' records.
+        ``stats``: the float32 ``[8]`` device tensor to write (None: a new
+        one).  Returns ``Stats``."""
+        actor_lr, critic_lr = self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
+        head, stats = self._records_head(records, n_total, stats)
+        self._call('apply', *head, actor_lr, critic_lr, stats.data_ptr(), self._stream(stream))
+        self._host_params = self._host_target = None
+        return Stats(stats)
+
+    def _exchange_records(self, batch, idx, stream, y=None):
+        """partial, the gather: (the gathered records, n_total, y)."""
+        ex = self.exchange
+        n_total = ex.total_rows(self._rows_of(batch, idx))
+        _, y = self._partial(batch, idx, n_total, ex.records[ex.rank], y, stream)
+        return ex.gather_records(), n_total, y
 
     @staticmethod
     def _rate(name, value):
@@ -833,8 +971,16 @@ class DDPGAgent:
         gradient, reduce, statistics, and Adam x2 + soft update + the images'
         repack.  ``actor_lr`` / ``critic_lr`` override the agent's for this
         call; 0 leaves that network's parameters where they are (Adam's
-        moments and the soft update still move).  Returns ``Stats``."""
+        moments and the soft update still move).  Returns ``Stats``.  With a
+        gradient exchange attached it is the step on every rank's rows:
+        partial, one in-place all-gather, apply."""
         import torch
+        if self.exchange is not None:
+            self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
+            records, n_total, y = self._exchange_records(batch, idx, stream)
+            stats = self.apply(records, n_total, actor_lr, critic_lr, stream=stream)
+            stats.y = y
+            return stats
         actor_lr, critic_lr = self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
         head, N = self._head(batch, idx)
         dev = batch['obs0'].device
@@ -868,8 +1014,19 @@ class DDPGAgent:
         calls) and no host read; bit-equal to ``steps`` calls of
         ``step(memory.as_batch(), idx[s])``.  Advances ``rng.replay_t`` and
         Adam's count by ``steps``.  Returns the ``[steps][8]`` statistics, a
-        device tensor; ``Stats(result[-1])`` names its last row."""
+        device tensor; ``Stats(result[-1])`` names its last row.
+
+        With a gradient exchange attached a gather sits between a step's two
+        halves, so the call is one launch for the indices, then ``steps`` x
+        (partial, all-gather, apply) issued from here on one stream.  A step's
+        index stream has ``world * batch_size`` words; rank r maps the columns
+        ``[r * batch_size, (r + 1) * batch_size)`` onto its own memory's
+        ``size`` (``rng.replay_indices_numpy(..., offset, total)``), and the
+        step is the single agent's on the ``world * batch_size`` rows."""
         import torch
+        if self.exchange is not None:
+            return self._train_exchange(memory, steps, batch_size, rng, actor_lr, critic_lr,
+                                        stream)
         actor_lr, critic_lr = self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
         steps, n = self.check_train(memory, steps, batch_size, rng)
         if self._h is None:
@@ -888,6 +1045,34 @@ class DDPGAgent:
                    self._stream(stream))
         rng.advance_replay(steps)
         self._host_params = self._host_target = None
+        return stats
+
+    def _train_exchange(self, memory, steps, batch_size, rng, actor_lr, critic_lr, stream):
+        """``train`` under a gradient exchange (see there)."""
+        import torch
+        ex = self.exchange
+        self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
+        steps, n = self.check_train(memory, steps, batch_size, rng)
+        total = ex.world * n
+        rng.check_replay(steps, total, memory.size)
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
+        self.check_device('memory', memory.obs0)
+        dev = memory.obs0.device
+        sc = self._train_scratch
+        if sc is None or sc['idx'].shape != (steps, total) or sc['idx'].device != dev:
+            sc = self._train_scratch = {
+                'idx': torch.empty((steps, total), dtype=torch.int32, device=dev),
+                'y': torch.empty(n, dtype=torch.float32, device=dev)}
+        stats = torch.empty((steps, N_STATS), dtype=torch.float32, device=dev)
+        idx = rng.replay_indices(steps, n, memory.size, stream=stream, offset=ex.rank * n,
+                                 total=total, out=sc['idx'])
+        batch, record = memory.as_batch(), ex.records[ex.rank]
+        for s in range(steps):
+            self._partial(batch, idx[s], total, record, sc['y'], stream)
+            self.apply(ex.gather_records(), total, actor_lr, critic_lr, stream=stream,
+                       stats=stats[s])
+        rng.advance_replay(steps)
         return stats
 
     def loss_grad_numpy(self, params, target_params, batch, dtype=np.float64):

@@ -320,10 +320,24 @@ class ShardedEnvs:
         return (res, work) if async_op else res
 
 
+def host_all_gather_int(value, world, group=None):
+    """``value`` (an int below 2^62) of every rank, in rank order, on every
+    rank: one tiny collective (a CUDA tensor under ``nccl``, a CPU tensor
+    otherwise)."""
+    import torch.distributed as dist
+    dev = torch.device('cuda', torch.cuda.current_device()) \
+        if dist.get_backend(group) == 'nccl' else torch.device('cpu')
+    out = torch.zeros(world, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(out, torch.tensor([int(value)], dtype=torch.int64, device=dev),
+                                group=group)
+    return [int(v) for v in out.cpu()]
+
+
 class GradientExchange:
-    """The gradient exchange of a data-parallel learner (``PPO2Learner`` or
-    ``A2CLearner``): every rank acts and differentiates on its own rows with
-    its own replica of the policy, and only the gradient crosses GPUs.
+    """The gradient exchange of a data-parallel learner (``PPO2Learner``,
+    ``A2CLearner`` or a ``ddpg.DDPGAgent``): every rank acts and
+    differentiates on its own rows with its own replica of the policy, and
+    only the gradient crosses GPUs.
 
     Constructing one attaches it (``learner.exchange``); from then on the
     learner's ``grad`` / ``step`` / ``update`` are the single learner's on the
@@ -333,7 +347,10 @@ class GradientExchange:
     every rank every record (RCCL under ``nccl``; gloo in the one-GPU
     rehearsals and the CPU tests), and every rank adds them in rank order, so
     the replicas stay bit-identical.  PPO2 with advantage normalisation
-    gathers ``moments`` ``[world][3]`` the same way first.
+    gathers ``moments`` ``[world][3]`` the same way first (a ``DDPGAgent``
+    has none: ``moments`` is None).  A ``DDPGAgent``'s ``train`` becomes ``steps`` x
+    (partial, gather, apply); its rows per call are its ``batch_size``, equal
+    on every rank, so its exchange takes the default ``counts``.
 
     ``counts``: every rank's env rows (``shard_range`` gives them; default:
     equal shards).  The rows of one call must be in proportion to them on
@@ -363,7 +380,9 @@ class GradientExchange:
                 else torch.device('cpu')
         self.records = torch.zeros((world, learner.record_doubles), dtype=torch.float64,
                                    device=device)
-        self.moments = torch.zeros((world, 3), dtype=torch.float64, device=device)
+        # a DDPGAgent (the one with an actor's block) normalises nothing
+        self.moments = None if hasattr(learner, 'n_actor') else \
+            torch.zeros((world, 3), dtype=torch.float64, device=device)
         learner.exchange = self
 
     @property
@@ -401,14 +420,50 @@ class GradientExchange:
     def gather_moments(self):
         return self._gather(self.moments)
 
+    def _src(self, src):
+        """``src`` (a rank of the group) as ``dist.broadcast`` wants it."""
+        import torch.distributed as dist
+        return src if self.group is None else dist.get_global_rank(self.group, src)
+
     def broadcast_params(self, src=0):
-        """Rank ``src``'s master parameters to every replica, on the device."""
+        """Rank ``src``'s master parameters (a ``DDPGAgent``'s target
+        parameters too) to every replica, on the device."""
         import torch.distributed as dist
         flat = torch.empty(self.learner.n_params, dtype=torch.float32, device=self.records.device)
-        self.learner.get_params(out=flat)
+        targets = hasattr(self.learner, 'n_actor')       # a DDPGAgent
+        kinds = (False, True) if targets else (False,)
+        got = []
+        for target in kinds:
+            buf = torch.empty_like(flat)
+            if targets:
+                self.learner.get_params(target=target, out=buf)
+            else:
+                self.learner.get_params(out=buf)
+            if self.world > 1 or self.collective:
+                dist.broadcast(buf, self._src(src), group=self.group)
+            got.append(buf)
+        self.learner.set_params(got[0])                  # a DDPGAgent's targets follow
+        if targets:
+            self.learner.set_params(got[1], target_only=True)
+
+    def broadcast_opt_state(self, src=0):
+        """Rank ``src``'s optimiser state (Adam's ``m``, ``v`` and step count,
+        or RMSProp's ``ms`` and ``mom``) to every replica.  It goes through
+        ``get_opt_state`` / ``set_opt_state``, so it synchronises: a thing of
+        the start of a run, not of a step."""
+        import numpy as np
+        import torch.distributed as dist
+        state = self.learner.get_opt_state()
         if self.world > 1 or self.collective:
-            dist.broadcast(flat, src, group=self.group)
-        self.learner.set_params(flat)
+            dev = self.records.device
+            for name in self.learner.OPT_BLOCKS:
+                buf = torch.from_numpy(np.ascontiguousarray(state[name], np.float32)).to(dev)
+                dist.broadcast(buf, self._src(src), group=self.group)
+                state[name] = buf.cpu().numpy()
+            step = torch.tensor([int(state['step'])], dtype=torch.int64, device=dev)
+            dist.broadcast(step, self._src(src), group=self.group)
+            state['step'] = int(step.cpu()[0])
+        self.learner.set_opt_state(state)
 
     def detach(self):
         if self.learner.exchange is self:

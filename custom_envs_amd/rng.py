@@ -120,10 +120,30 @@ def u32_numpy(seed, purpose, t, n):
     return np.ascontiguousarray(np.stack(words, axis=-1).reshape(-1)[:n])
 
 
-def permutation_numpy(seed, t, n):
+def _check_slice(n, offset, total):
+    """``[offset, offset + n)`` of a stream of ``total`` (None: ``offset +
+    n``) words.  Returns ``total``."""
+    n, offset = int(n), int(offset)
+    total = offset + n if total is None else int(total)
+    if n < 1 or offset < 0 or offset + n > total:
+        raise ValueError('the slice [%d, %d) does not lie inside a stream of %d words'
+                         % (offset, offset + n, total))
+    return total
+
+
+def permutation_numpy(seed, t, n, offset=0, total=None):
     """The permutation of ``range(n)`` of epoch ``t``: the stable argsort of
-    ``u32_numpy(seed, PERMUTATION, t, n)``, int32."""
-    return np.argsort(u32_numpy(seed, PERMUTATION, t, n), kind='stable').astype(np.int32)
+    ``u32_numpy(seed, PERMUTATION, t, n)``, int32.
+
+    ``offset`` / ``total``: the keys are the slice ``[offset, offset + n)`` of
+    the epoch's stream drawn at length ``total`` -- rank r of a data-parallel
+    run permutes its own ``n = K * R_r`` rows by the keys at ``offset = K *
+    off_r`` of the ``total = K * sum(R)`` the ranks share, so the ranks use
+    disjoint keys.  A word of the stream does not depend on the stream's
+    length, so ``offset=0`` is the three-argument call bit for bit."""
+    total = _check_slice(n, offset, total)
+    keys = u32_numpy(seed, PERMUTATION, t, total)[int(offset):int(offset) + int(n)]
+    return np.argsort(keys, kind='stable').astype(np.int32)
 
 
 def _check_replay(n, size):
@@ -133,13 +153,20 @@ def _check_replay(n, size):
         raise ValueError('size must be in [1, 2^24], got %d' % size)
 
 
-def replay_indices_numpy(seed, t, n, size):
+def replay_indices_numpy(seed, t, n, size, offset=0, total=None):
     """The ``n`` replay indices of train step ``t`` over ``size`` records:
     ``(u32_numpy(seed, REPLAY, t, n) * size) >> 32``, int32 in ``[0, size)``,
-    drawn with replacement (see the module docstring for the bias)."""
+    drawn with replacement (see the module docstring for the bias).
+
+    ``offset`` / ``total``: the words are the columns ``[offset, offset + n)``
+    of the step's stream of ``total`` words -- rank r of W data-parallel
+    ranks maps the columns ``[r * B, (r + 1) * B)`` of the ``W * B`` onto its
+    own memory's ``size``."""
     n, size = int(n), int(size)
     _check_replay(n, size)
-    words = u32_numpy(seed, REPLAY, t, n).astype(np.uint64)
+    total = _check_slice(n, offset, total)
+    _check_replay(total, size)
+    words = u32_numpy(seed, REPLAY, t, total)[int(offset):int(offset) + n].astype(np.uint64)
     return ((words * np.uint64(size)) >> np.uint64(32)).astype(np.int32)
 
 
@@ -246,19 +273,29 @@ class DeviceRng:
         _check_draws(int(self.replay_t), steps)
         return steps, n, size
 
-    def replay_indices(self, steps, n, size, stream=None):
+    def replay_indices(self, steps, n, size, stream=None, offset=0, total=None, out=None):
         """``[steps][n]`` int32 on the device: ``replay_indices_numpy`` of the
         draws ``replay_t .. replay_t + steps - 1`` from ONE launch.  Does not
-        advance ``replay_t``."""
+        advance ``replay_t``.  ``offset`` / ``total``: the launch draws the
+        whole ``[steps][total]`` stream against ``size`` (into ``out``, or a
+        new tensor) and the result is the view of its columns ``[offset,
+        offset + n)``, every row of it contiguous."""
         import torch
         steps, n, size = self.check_replay(steps, n, size)
+        total = _check_slice(n, offset, total)
+        _check_replay(total, size)
         dev = self._torch_device()
-        out = torch.empty((steps, n), dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty((steps, total), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or tuple(out.shape) != (steps, total) \
+                or not out.is_contiguous() or out.device != dev:
+            raise ValueError('out must be a contiguous int32 [%d][%d] tensor on %s'
+                             % (steps, total, dev))
         with torch.cuda.device(dev):
-            check(_native.load().ce_rng_replay(out.data_ptr(), steps, n, size, self.seed,
+            check(_native.load().ce_rng_replay(out.data_ptr(), steps, total, size, self.seed,
                                                int(self.replay_t), self._stream(stream)),
                   'ce_rng_replay')
-        return out
+        return out if total == n else out[:, int(offset):int(offset) + n]
 
     def u32(self, purpose, t, n, stream=None):
         """``u32_numpy(seed, purpose, t, n)`` on the device, as an int64 tensor
@@ -275,11 +312,15 @@ class DeviceRng:
                                             self._stream(stream)), 'ce_rng_u32')
         return raw.to(torch.int64) & 0xffffffff
 
-    def permutation(self, n):
-        """The permutation of epoch ``epoch`` (``permutation_numpy``) as an
-        int32 device tensor; advances the epoch counter."""
+    def permutation(self, n, offset=0, total=None):
+        """The permutation of epoch ``epoch`` (``permutation_numpy``, with its
+        ``offset`` / ``total``: the whole key stream is drawn and sliced) as
+        an int32 device tensor; advances the epoch counter."""
         import torch
-        keys = self.u32(PERMUTATION, self.epoch, n)
+        total = _check_slice(n, offset, total)
+        keys = self.u32(PERMUTATION, self.epoch, total)
+        if total != int(n):
+            keys = keys[int(offset):int(offset) + int(n)]
         perm = torch.argsort(keys, stable=True).to(torch.int32)
         self.epoch += 1
         return perm

@@ -846,6 +846,32 @@ int ce_ddpg_get_opt_state(ce_ddpg *l, float *m, float *v, int64_t n, int64_t *st
 int ce_ddpg_set_opt_state(ce_ddpg *l, const float *m, const float *v, int64_t n, int64_t step,
                           uint32_t flags, void *hip_stream);
 
+/* DDPG's side of the gradient exchange (as ce_ppo2_partial / _combine /
+ * _apply above): W ranks, rank r holding n_r sampled rows, take the single
+ * agent's train step on the concatenation, N = sum n_r.  A record is
+ * ce_ddpg_record_bytes(l) bytes of float64, a multiple of 256:
+ *   [n_params sums over this rank's rows in flat parameter order, before any
+ *    rounding | 8 statistic sums | n_r | zeros].
+ * `records` is [world][record], rank r's record in slot r; every rank adds
+ * them in rank order in float64 and rounds once, so every rank computes the
+ * same bits, and at world 1 _partial + _apply leave the bits of ce_ddpg_step.
+ * Device pointers, 8-byte aligned; stream-ordered, no synchronisation, no
+ * allocation. */
+int64_t ce_ddpg_record_bytes(const ce_ddpg *l);              /* -1: null learner */
+/* ce_ddpg_grad's target and gradient of these n rows with the row weight 1 /
+ * n_total (n <= n_total <= 2^30), into `record`.  Three launches. */
+int ce_ddpg_partial(ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const int32_t *idx,
+                    const float *obs0, const float *actions, const float *rewards,
+                    const float *obs1, const uint8_t *dones, float *y, double *record,
+                    void *hip_stream);
+/* grad [n_params] and stats [8] of all n_total rows from the records; no update. */
+int ce_ddpg_combine(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
+                    float *grad, float *stats, void *hip_stream);
+/* ce_ddpg_combine into the agent's gradient, then ce_ddpg_step's update (Adam
+ * on both blocks, one step; the soft update; both images). */
+int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
+                  double actor_lr, double critic_lr, float *stats, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
