@@ -60,6 +60,9 @@ EXPORTS = (
     'ce_rng_normal_purpose', 'ce_rng_replay', 'ce_ddpg_act_rng', 'ce_ddpg_train',
     'ce_ddpg_get_opt_state', 'ce_ddpg_set_opt_state',
     'ce_ddpg_record_bytes', 'ce_ddpg_partial', 'ce_ddpg_combine', 'ce_ddpg_apply',
+    'ce_monitor_record_bytes', 'ce_monitor_create', 'ce_monitor_destroy', 'ce_monitor_reset',
+    'ce_monitor_scan', 'ce_monitor_write', 'ce_monitor_get_state', 'ce_monitor_set_state',
+    'ce_explained_variance',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -150,6 +153,15 @@ class CeDdpgNoise(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('theta', ctypes.c_double), ('dt', ctypes.c_double),
                 ('mean', ctypes.c_float * CE_DDPG_MAX_ACT),
                 ('sigma', ctypes.c_float * CE_DDPG_MAX_ACT)]
+
+
+CE_MONITOR_MAX_INFO = 16
+MONITOR_RECORD_HEAD = 32     # bytes of an episode record before its info columns
+
+
+class CeMonitorColumn(ctypes.Structure):
+    _fields_ = [('base', ctypes.c_void_p), ('stride_bytes', ctypes.c_int64),
+                ('row_floats', ctypes.c_int32), ('col', ctypes.c_int32)]
 
 
 class CeState(ctypes.Structure):
@@ -296,6 +308,16 @@ def _declare(lib):
         'ce_ddpg_partial': ([vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_ddpg_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
         'ce_ddpg_apply': ([vp, i32, vp, i64, f64, f64, vp, vp], ctypes.c_int),
+        'ce_monitor_record_bytes': ([i32], ctypes.c_int64),
+        'ce_monitor_create': ([i32, i32, ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_monitor_destroy': ([vp], None),
+        'ce_monitor_reset': ([vp, vp, i32, vp], ctypes.c_int),
+        'ce_monitor_scan': ([vp, i32, i32, i32, vp, i64, vp, i64, ctypes.POINTER(CeMonitorColumn),
+                             i32, vp, i64, vp, vp], ctypes.c_int),
+        'ce_monitor_write': ([vp, vp, i64, vp], ctypes.c_int),
+        'ce_monitor_get_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_monitor_set_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        'ce_explained_variance': ([i32, i64, vp, i64, vp, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -29,7 +29,7 @@ on the policy's device and writes every update through to the policy's image.
 One learner per policy: a second learner (of either algorithm) on the same
 policy would overwrite the image from its own master copy.
 
-Out of scope: ``MlpLstmPolicy``, ``explained_variance``, SB's ``Scheduler``
+Out of scope: ``MlpLstmPolicy``, SB's ``Scheduler``
 class (pass ``lr=`` per call instead).  DDPG is ``custom_envs_amd/ddpg.py``.
 
 On several GPUs a ``distributed.GradientExchange`` attached to the learner

@@ -32,7 +32,7 @@ def sources():
     return [os.path.join(CSRC, f) for f in ('engine.hip', 'optimize_mfma.hip', 'optimize_lr_persist.hip',
                                             'multi_engine.hip', 'multinn_engine.hip', 'net_engine.hip',
                                             'policy_engine.hip', 'ppo2_engine.hip', 'a2c_engine.hip',
-                                            'ddpg_engine.hip',
+                                            'ddpg_engine.hip', 'monitor_engine.hip',
                                             'seeding.cpp')]
 
 

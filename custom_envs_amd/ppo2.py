@@ -397,6 +397,7 @@ class PPO2Learner(Learner):
                 raise ValueError('%s must have shape %s, got %s'
                                  % (name, (k, rows) + tail, tuple(t.shape)))
         adv, ret = self.gae(result, stream=stream)
+        self.last_returns = ret      # [K][R], for a caller's explained variance
         batch = self.flatten(result, adv, ret)
         self.check_batch(batch)
         size = total // nminibatches

@@ -63,9 +63,13 @@ class GPUVecEnv:
                  model='linear', hidden=64, monitor=None, data_dir=None):
         """``monitor``: None, or (file paths, Monitor keywords) -- the batched
         form of wrapping every env in utils_logging.Monitor
-        (utils_logging.py:159-175); writes the same ``.mon.csv`` chunks."""
+        (utils_logging.py:159-175); writes the same ``.mon.csv`` chunks.  With
+        ``'device': True`` among the keywords the bookkeeping runs on the
+        device (``utils_logging.DeviceVecMonitor``): ``collect`` /
+        ``collect_ddpg`` then leave the K records where they are and only the
+        finished episodes' rows come to the host; ``callbacks`` raise."""
         from custom_envs_amd.engine import OptimizeEngine
-        from custom_envs_amd.utils.utils_logging import VecMonitor
+        from custom_envs_amd.utils.utils_logging import make_vec_monitor
         features, targets = resolve_dataset(data_set, batch_size, data_dir)
         self.engine = OptimizeEngine(features, targets, num_envs, batch_size=batch_size,
                                      max_steps=max_steps, precision=precision, device=device,
@@ -75,18 +79,18 @@ class GPUVecEnv:
         self.monitor = None
         if monitor is not None:
             paths, mkw = monitor
-            self.monitor = VecMonitor(self.num_envs, paths,
-                                      info_keywords=mkw.get('info_keywords', ()),
-                                      chunk_size=mkw.get('chunk_size', 1),
-                                      callbacks=mkw.get('callbacks'),
-                                      style=mkw.get('style', 'logging'),
-                                      allow_early_resets=mkw.get('allow_early_resets', True),
-                                      reset_keywords=mkw.get('reset_keywords', ()))
+            self.monitor = make_vec_monitor(self.num_envs, paths, mkw, self.engine.device)
+            if self._device_monitor:
+                self.monitor.bind({'objective': ('objective', 0), 'accuracy': ('accuracy', 0)})
         self.current_step = np.zeros(self.num_envs, np.int64)
         self.waiting = False
         self.closed = False
         self._last_obs = None      # what collect() starts from
         self.seed(seed)
+
+    @property
+    def _device_monitor(self):
+        return getattr(self.monitor, 'on_device', False)
 
     # ----------------------------------------------------------- VecEnv API
     def seed(self, seed=None):
@@ -126,7 +130,9 @@ class GPUVecEnv:
         reward = out['reward'].copy()
         infos = LazyInfos(out['objective'].copy(), out['accuracy'].copy(), reward, ep_len)
         obs = out['obs'].copy()
-        if self.monitor is not None:
+        if self._device_monitor:
+            infos.episodes.update(self.monitor.step(reward, dones, infos, fields=out))
+        elif self.monitor is not None:
             infos.episodes.update(self.monitor.step(reward, dones, infos, obs))
         self._last_obs = obs
         return obs, reward, dones, infos
@@ -157,7 +163,11 @@ class GPUVecEnv:
                                      self.num_envs)
         self._last_obs = result['last_obs']
         k = int(n_steps)
-        if self.monitor is not None:
+        if self._device_monitor:
+            self.monitor.scan(fields, k)
+            dones = result['dones'][k - 1].cpu().numpy().astype(bool)
+            ep_len = result['episode_len'][k - 1].cpu().numpy()
+        elif self.monitor is not None:
             host = host_records(fields)
             for t in range(k):
                 infos = LazyInfos(host['objective'][t], host['accuracy'][t], host['reward'][t],
@@ -189,22 +199,33 @@ class GPUVecEnv:
             self.monitor.check_step()
         if getattr(self, '_ddpg_stream', None) is None:
             self._ddpg_stream = torch.cuda.Stream(torch.device('cuda', self.engine.device))
-        keep = ('obs1', 'rewards', 'dones') if self.monitor is not None else ()
+        if self._device_monitor:
+            keep = ('rewards', 'dones')
+        else:
+            keep = ('obs1', 'rewards', 'dones') if self.monitor is not None else ()
         result, kept = run_collect_ddpg(self.engine, agent, memory, n_steps, self._last_obs, noise,
                                         self.num_envs, self.engine.obs_dim, self.engine.act_dim,
                                         self._ddpg_stream, keep)
         self._last_obs = result['last_obs']
         k = int(n_steps)
-        host = {n: v.cpu().numpy() for n, v in result.items() if n not in ('env_actions', 'last_obs')}
-        if self.monitor is not None:
-            rewards, dones, obs = (kept[n].cpu().numpy() for n in ('rewards', 'dones', 'obs1'))
-            for t in range(k):
-                infos = LazyInfos(host['objective'][t], host['accuracy'][t], rewards[t],
-                                  host['episode_len'][t])
-                self.monitor.step(rewards[t], dones[t].astype(bool), infos, obs[t])
+        if self._device_monitor:
+            self.monitor.scan({'reward': kept['rewards'], 'done': kept['dones'],
+                               'objective': result['objective'],
+                               'accuracy': result['accuracy']}, k)
+            last_len = result['episode_len'][k - 1].cpu().numpy()
+        else:
+            host = {n: v.cpu().numpy() for n, v in result.items()
+                    if n not in ('env_actions', 'last_obs')}
+            last_len = host['episode_len'][k - 1]
+            if self.monitor is not None:
+                rewards, dones, obs = (kept[n].cpu().numpy() for n in ('rewards', 'dones', 'obs1'))
+                for t in range(k):
+                    infos = LazyInfos(host['objective'][t], host['accuracy'][t], rewards[t],
+                                      host['episode_len'][t])
+                    self.monitor.step(rewards[t], dones[t].astype(bool), infos, obs[t])
         last = (memory.pos - memory.rows) % memory.capacity      # the slot of step K - 1
         dones = memory.dones[last:last + memory.rows].cpu().numpy().astype(bool)
-        self.current_step[:] = np.where(dones, 0, host['episode_len'][k - 1])
+        self.current_step[:] = np.where(dones, 0, last_len)
         return result
 
     def close(self):

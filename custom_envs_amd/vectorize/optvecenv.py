@@ -141,7 +141,11 @@ class _RowInfos:
 
 
 class OptVecEnv:
-    def __init__(self, environment_fns, callbacks=()):
+    def __init__(self, environment_fns, callbacks=(), device_monitor=False):
+        """``device_monitor``: on the engine path, the ``partial(Monitor, ...)``
+        factories become one ``utils_logging.DeviceVecMonitor`` instead of one
+        ``VecMonitor``: the episode bookkeeping of ``collect`` / ``collect_ddpg``
+        runs on the device (Monitor ``callbacks`` raise ``ValueError``)."""
         self.callbacks = callbacks
         self.closed = False
         self.waiting = False
@@ -150,7 +154,7 @@ class OptVecEnv:
         self._last_obs = None      # what collect() starts from (engine path)
         if request is not None:
             from custom_envs_amd.multi_engine import create_engine
-            from custom_envs_amd.utils.utils_logging import VecMonitor
+            from custom_envs_amd.utils.utils_logging import make_vec_monitor
             kwargs, mon, built = request
             for env in built:      # single-env engines the caller built eagerly
                 env.close()
@@ -161,13 +165,14 @@ class OptVecEnv:
             self.observation_space = Box(low=-1e6, high=1e6, dtype=np.float32, shape=(3 * H,))
             self.action_space = Box(low=-1e3, high=1e4, dtype=np.float32, shape=(1,))
             if mon is not None:
+                from custom_envs_amd._native import MULTI_INFO_KEYS
                 paths, mkw = mon
-                self.monitor = VecMonitor(E, paths, info_keywords=mkw.get('info_keywords', ()),
-                                          chunk_size=mkw.get('chunk_size', 1),
-                                          callbacks=mkw.get('callbacks'),
-                                          style=mkw.get('style', 'logging'),
-                                          allow_early_resets=mkw.get('allow_early_resets', True),
-                                          reset_keywords=mkw.get('reset_keywords', ()))
+                if device_monitor:
+                    mkw = dict(mkw, device=True)
+                self.monitor = make_vec_monitor(E, paths, mkw, getattr(self._engine, 'device', 0))
+                if self._device_monitor:
+                    self.monitor.bind({key: ('info', c) for c, key in enumerate(MULTI_INFO_KEYS)},
+                                      row_stride=P)
         else:
             runners = [functools.partial(OptEnvRunner, fn) for fn in environment_fns]
             self._host = ThreadVecEnv(runners)
@@ -179,6 +184,10 @@ class OptVecEnv:
     @property
     def engine_backed(self):
         return self._engine is not None
+
+    @property
+    def _device_monitor(self):
+        return getattr(self.monitor, 'on_device', False)
 
     def step_async(self, actions):
         if self._engine is not None and self.monitor is not None:
@@ -206,7 +215,10 @@ class OptVecEnv:
             info = out['info'].copy()
             episodes = {}
             infos = _RowInfos(info, env_rewards, env_dones, lengths, P, episodes)
-            if self.monitor is not None:
+            if self._device_monitor:
+                episodes.update(self.monitor.step(env_rewards, env_dones, infos.per_env(),
+                                                  fields={'info': info}))
+            elif self.monitor is not None:
                 episodes.update(self.monitor.step(env_rewards, env_dones, infos.per_env()))
                 for env, ep in episodes.items():
                     infos.env_info(env)['episode'] = ep
@@ -256,7 +268,9 @@ class OptVecEnv:
         result, fields = run_collect(self._engine, policy, n_steps, self._last_obs, noise,
                                      self._engine.rows)
         self._last_obs = result['last_obs']
-        if self.monitor is not None:
+        if self._device_monitor:
+            self.monitor.scan(fields, int(n_steps))
+        elif self.monitor is not None:
             host, P = host_records(fields), self._engine.n_params
             for t in range(int(n_steps)):
                 env_rewards, env_dones = host['reward'][t][::P], host['done'][t][::P].astype(bool)
@@ -292,7 +306,10 @@ class OptVecEnv:
         result, kept = run_collect_ddpg(eng, agent, memory, n_steps, self._last_obs, noise,
                                         eng.rows, 3 * eng.max_history, 1, self._ddpg_stream, keep)
         self._last_obs = result['last_obs']
-        if self.monitor is not None:
+        if self._device_monitor:
+            self.monitor.scan({'reward': kept['rewards'], 'done': kept['dones'],
+                               'info': result['info']}, int(n_steps))
+        elif self.monitor is not None:
             P = eng.n_params
             info, lengths = result['info'].cpu().numpy(), result['episode_len'].cpu().numpy()
             rewards, dones = kept['rewards'].cpu().numpy(), kept['dones'].cpu().numpy()

@@ -872,6 +872,68 @@ int ce_ddpg_combine(ce_ddpg *l, int32_t world, const double *records, int64_t n_
 int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
                   double actor_lr, double critic_lr, float *stats, void *hip_stream);
 
+/* The episode monitor on the device: utils_logging.VecMonitor's bookkeeping
+ * (custom_envs/utils/utils_logging.py:98-116 per env) over K-step rollout
+ * records where the rollout left them.  The carry -- per env ep_reward
+ * (float64), ep_len (int32), episode (int64), total_steps (int64) -- lives on
+ * the device between calls.  Records are read in place: an env's reward and
+ * done at step t are row num_envs-index * row_stride of record t (base + t *
+ * stride bytes), so a multi-agent env is seen through its first agent row. */
+typedef struct ce_monitor ce_monitor;
+#define CE_MONITOR_MAX_INFO 16
+/* One info column: element (t, env) is
+ * ((const float *)((const char *)base + t * stride_bytes))[env * row_floats + col]. */
+typedef struct ce_monitor_column {
+    const void *base;      /* device, 4-byte aligned                          */
+    int64_t stride_bytes;  /* multiple of 4, >= num_envs * row_floats * 4     */
+    int32_t row_floats;    /* floats per env in one record, >= 1              */
+    int32_t col;           /* in [0, row_floats)                              */
+} ce_monitor_column;
+/* Bytes of one episode record with n_info columns (-1: n_info out of range):
+ *   {int32 env, int32 t, float64 r, int32 l, float32 current_reward,
+ *    int64 episode, float32 info[n_info]}  padded to a multiple of 8
+ * r is the float64 sum of the episode's float32 rewards in step order (the
+ * bits of VecMonitor's np.float64 sum), unrounded. */
+int64_t ce_monitor_record_bytes(int32_t n_info);
+/* A monitor of num_envs envs on `device`, the carry zeroed. */
+int ce_monitor_create(int32_t device, int32_t num_envs, ce_monitor **out);
+void ce_monitor_destroy(ce_monitor *m);
+/* VecMonitor.reset: ep_reward and ep_len cleared and episode advanced by one,
+ * of every env (indices NULL) or of the n envs listed in the host array
+ * indices (duplicates count once).  CE_EINVAL: an index outside the envs. */
+int ce_monitor_reset(ce_monitor *m, const int32_t *indices, int32_t n, void *hip_stream);
+/* K steps of VecMonitor.step as four launches, stream-ordered, no host read:
+ * the forward scan per env (ep_reward += (double)reward, ep_len += 1; at a done
+ * (r, l, current_reward, episode) is staged at [t][env], the sums are cleared
+ * and episode advanced), the finished episodes' count per 256 flags of the
+ * flattened [k][num_envs] dones, the one-workgroup scan of the counts, and the
+ * write of one record per finished episode into out [capacity] in (t, env)
+ * order.  The count of finished episodes goes to total[0] (device, 8-byte
+ * aligned) whatever the capacity; nothing is written at or past out +
+ * capacity * ce_monitor_record_bytes(n_info).  The rollout records and
+ * `columns`' targets must stay as they are until the last ce_monitor_write of
+ * this scan.  Allocates only when k * num_envs exceeds every earlier call's. */
+int ce_monitor_scan(ce_monitor *m, int32_t k, int32_t num_envs, int32_t row_stride,
+                    const float *rewards, int64_t reward_stride_bytes, const uint8_t *dones,
+                    int64_t done_stride_bytes, const ce_monitor_column *columns, int32_t n_info,
+                    void *out, int64_t capacity, int64_t *total, void *hip_stream);
+/* The last scan's records again, into another (larger) buffer: the write
+ * launch only, the carry is untouched.  CE_ESTATE before the first scan. */
+int ce_monitor_write(ce_monitor *m, void *out, int64_t capacity, void *hip_stream);
+/* The carry to / from host arrays of num_envs entries each; synchronises. */
+int ce_monitor_get_state(ce_monitor *m, double *ep_reward, int32_t *ep_len, int64_t *episode,
+                         int64_t *total_steps, void *hip_stream);
+int ce_monitor_set_state(ce_monitor *m, const double *ep_reward, const int32_t *ep_len,
+                         const int64_t *episode, const int64_t *total_steps, void *hip_stream);
+/* stable-baselines' explained_variance of a rollout: 1 - Var[returns - values]
+ * / Var[returns] over k * rows entries (population variances; NaN when
+ * Var[returns] == 0) into out[0] (float64, device).  values is read strided in
+ * the policy records, returns is the learner's flat [k * rows] array.  Two
+ * passes in float64 in a fixed order by one workgroup: the same inputs give the
+ * same bits.  One launch on the current device, no synchronisation. */
+int ce_explained_variance(int32_t k, int64_t rows, const float *values, int64_t value_stride_bytes,
+                          const float *returns, double *out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
