@@ -43,9 +43,9 @@ import numpy as np
 from custom_envs_amd import learner
 from custom_envs_amd._native import CeA2cConfig
 from custom_envs_amd.learner import GRAD_SQ  # noqa: F401  (part of this module's names)
-from custom_envs_amd.learner import (N_STATS, Learner, clip_by_global_norm_numpy, gaussian_head,
-                                     gaussian_head_backward, mlp_backward, mlp_forward,
-                                     statement_inputs)
+from custom_envs_amd.learner import (N_STATS, Learner, check_rate, clip_by_global_norm_numpy,
+                                     gaussian_head, gaussian_head_backward, mlp_backward,
+                                     mlp_forward, statement_inputs)
 from custom_envs_amd.policy import dict_to_flat
 
 # the first four of the N_STATS (8) floats a call writes; then two zeros,
@@ -238,15 +238,18 @@ class A2CLearner(Learner):
     def step(self, batch, idx=None, stream=None, lr=None):
         """Gradient, global-norm clip, RMSProp and the policy image's repack
         as one stream-ordered call.  ``lr`` overrides the learner's for this
-        call (a learning-rate schedule is the caller's ``lr=`` per call).
-        Returns ``Stats``.  With a gradient exchange attached it is the step
-        on every rank's rows: partial, gather, apply."""
+        call (a learning-rate schedule is the caller's ``lr=`` per call): None
+        means the learner's own, a finite positive number is used, and
+        anything else (0.0 from a schedule, a negative number, NaN, inf)
+        raises ``ValueError`` before any device call.  Returns ``Stats``.
+        With a gradient exchange attached it is the step on every rank's
+        rows: partial, gather, apply."""
+        rate = check_rate('lr', lr)
         if self.exchange is not None:
             records, n_total = self._exchange_records(batch, idx, stream)
             return self.apply(records, n_total, lr=lr, stream=stream)
         head, stats = self._head(batch, idx)
-        self._call('step', *head, -1.0 if lr is None else lr, stats.data_ptr(),
-                   self._stream(stream))
+        self._call('step', *head, rate, stats.data_ptr(), self._stream(stream))
         self.policy._host_params = None
         return Stats(stats)
 
@@ -285,10 +288,12 @@ class A2CLearner(Learner):
         """The whole A2C update of one rollout as one call: the returns scan,
         the gradient over the records in place, reduce, finish, RMSProp and
         the policy image's repack (six launches; no copy, no allocation once
-        the returns buffer has its size, no synchronisation).  Returns
-        ``Stats``.  With a gradient exchange attached: ``update_partial`` with
-        ``n_total = K`` times every rank's rows, the gather, ``apply``."""
+        the returns buffer has its size, no synchronisation).  ``lr`` as in
+        ``step``, checked before anything else.  Returns ``Stats``.  With a
+        gradient exchange attached: ``update_partial`` with ``n_total = K``
+        times every rank's rows, the gather, ``apply``."""
         import torch
+        rate = check_rate('lr', lr)
         if self.exchange is not None:
             ex = self.exchange
             if result.get('rewards') is None:
@@ -305,7 +310,7 @@ class A2CLearner(Learner):
             'update', self._h, k, rows, result['obs'].data_ptr(), result['actions'].data_ptr(),
             sb(result['actions']), result['values'].data_ptr(), sb(result['values']),
             result['rewards'].data_ptr(), sb(result['rewards']), result['dones'].data_ptr(),
-            sb(result['dones']), result['last_values'].data_ptr(), -1.0 if lr is None else lr,
-            stats.data_ptr(), self._stream(stream))
+            sb(result['dones']), result['last_values'].data_ptr(), rate, stats.data_ptr(),
+            self._stream(stream))
         self.policy._host_params = None
         return Stats(stats)

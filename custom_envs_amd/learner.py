@@ -93,6 +93,23 @@ def clip_by_global_norm_numpy(grad, max_grad_norm, dt=None):
     return grad
 
 
+def check_rate(name, value):
+    """A per-call override (``lr``, PPO2's ``cliprange``): None, which means
+    the learner's own and goes to the native side as -1, or a finite positive
+    number.  Anything else raises: the native side reads every value that is
+    not positive as "none given", so a schedule's 0.0 would train at the
+    learner's own rate."""
+    if value is None:
+        return -1.0
+    try:
+        rate = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be None or a finite positive number, got %r' % (name, value))
+    if not (np.isfinite(rate) and rate > 0.0):
+        raise ValueError('%s must be None or a finite positive number, got %r' % (name, value))
+    return rate
+
+
 # ---------------------------------------------------- the gradient exchange
 ROW_STATS = 4        # per-row statistic sums a workgroup keeps per network (kPpoRowStats)
 RECORD_TAIL = 2 * ROW_STATS + 1      # the statistic sums of both networks, then n_r
@@ -408,9 +425,12 @@ class Learner:
 
     def apply(self, records, n_total, lr=None, stream=None):
         """Combine, finish, the optimiser's step (one) and the repack from the
-        ranks' records.  Returns ``Stats``."""
+        ranks' records.  ``lr`` overrides the learner's for this call: None
+        (the learner's own) or a finite positive number, anything else raises
+        ``ValueError`` before any device call.  Returns ``Stats``."""
+        lr = check_rate('lr', lr)
         head, stats = self._records_head(records, n_total)
-        self._call('apply', *head, -1.0 if lr is None else lr, stats.data_ptr(),
+        self._call('apply', *head, lr, stats.data_ptr(),
                    self._stream(stream))
         self.policy._host_params = None
         return self.STATS(stats)

@@ -37,7 +37,7 @@ import numpy as np
 from custom_envs_amd import learner
 from custom_envs_amd._native import CePpo2Config
 from custom_envs_amd.learner import N_STATS  # noqa: F401  (part of this module's names)
-from custom_envs_amd.learner import (Learner, clip_by_global_norm_numpy, gaussian_head,
+from custom_envs_amd.learner import (Learner, check_rate, clip_by_global_norm_numpy, gaussian_head,
                                      gaussian_head_backward, mlp_backward, mlp_forward,
                                      statement_inputs)
 from custom_envs_amd.policy import dict_to_flat
@@ -239,14 +239,16 @@ class PPO2Learner(Learner):
     # ---------------------------------------------------------- gradient, step
     def grad(self, batch, idx=None, stream=None, cliprange=None):
         """The loss gradient of the rows ``idx`` (None: all) of ``batch``, no
-        update.  Returns (grad ``[n_params]`` device tensor, ``Stats``)."""
+        update.  ``cliprange`` as in ``step``.  Returns (grad ``[n_params]``
+        device tensor, ``Stats``)."""
         import torch
+        clip = check_rate('cliprange', cliprange)
         if self.exchange is not None:      # the gradient of every rank's rows
             records, n_total = self._exchange_records(batch, idx, stream, cliprange)
             return self.combine(records, n_total, stream=stream)
         head, stats = self._head(batch, idx)
         grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
-        self._call('grad', *head, -1.0 if cliprange is None else cliprange, grad.data_ptr(),
+        self._call('grad', *head, clip, grad.data_ptr(),
                    stats.data_ptr(), self._stream(stream))
         return grad, Stats(stats)
 
@@ -272,7 +274,9 @@ class PPO2Learner(Learner):
         n_total``, normalised by the merged ``moments`` (``[world][3]``
         float64, every rank's ``adv_moments``; None with ``n_total == n``:
         this call's own), as one float64 record in ``out`` (``[record_doubles]``;
-        None: a new tensor).  Returns the record."""
+        None: a new tensor).  ``cliprange`` as in ``step``.  Returns the
+        record."""
+        cliprange = check_rate('cliprange', cliprange)
         n_total = self.check_total(self._rows_of(batch, idx), n_total)
         if out is not None:
             self.check_record_tensor('out', out, (self.record_doubles,))
@@ -293,7 +297,7 @@ class PPO2Learner(Learner):
         out = self._record_out(out, batch['obs'])
         ptrs = [batch[n].data_ptr() for n in self.BATCH_FIELDS]
         self._call('partial', self._h, N, n_total, M, None if idx is None else idx.data_ptr(),
-                   *ptrs, -1.0 if cliprange is None else cliprange, world,
+                   *ptrs, cliprange, world,
                    None if moments is None else moments.data_ptr(), out.data_ptr(),
                    self._stream(stream))
         return out
@@ -313,16 +317,18 @@ class PPO2Learner(Learner):
     def step(self, batch, idx=None, stream=None, lr=None, cliprange=None):
         """Gradient, global-norm clip, Adam and the policy image's repack as
         one stream-ordered call.  ``lr`` / ``cliprange`` override the
-        learner's for this call.  Returns ``Stats``.  With a gradient exchange
-        attached it is the step on every rank's rows: [moments, gather,]
-        partial, gather, apply."""
+        learner's for this call: None means the learner's own, a finite
+        positive number is used, and anything else (0.0 from a schedule, a
+        negative number, NaN, inf) raises ``ValueError`` before any device
+        call.  Returns ``Stats``.  With a gradient exchange attached it is
+        the step on every rank's rows: [moments, gather,] partial, gather,
+        apply."""
+        rate, clip = check_rate('lr', lr), check_rate('cliprange', cliprange)
         if self.exchange is not None:
             records, n_total = self._exchange_records(batch, idx, stream, cliprange)
             return self.apply(records, n_total, lr=lr, stream=stream)
         head, stats = self._head(batch, idx)
-        self._call('step', *head, -1.0 if lr is None else lr,
-                   -1.0 if cliprange is None else cliprange, stats.data_ptr(),
-                   self._stream(stream))
+        self._call('step', *head, rate, clip, stats.data_ptr(), self._stream(stream))
         self.policy._host_params = None
         return Stats(stats)
 
@@ -361,12 +367,16 @@ class PPO2Learner(Learner):
         or of ``perms[epoch]`` when ``perms`` is given: ``noptepochs`` int32
         device permutations of the ``K * R`` rows (``rng.DeviceRng.
         permutation``), so the split does not depend on torch's generator.
+        ``lr`` / ``cliprange`` reach every minibatch step and are checked as
+        ``step`` checks them, before anything else.
         Nothing is read back; returns the ``Stats`` of every step, in order.
         With a gradient exchange attached every rank splits its own ``K * R_r``
         rows with its own ``generator``, and ``K * R_r`` must divide by
         ``nminibatches`` on every rank (checked on every rank, before any
         launch)."""
         import torch
+        check_rate('lr', lr)
+        check_rate('cliprange', cliprange)
         for name in ('obs', 'actions', 'values', 'neglogps', 'rewards', 'dones', 'last_values'):
             if result.get(name) is None:
                 raise ValueError('result lacks %r' % name)

@@ -1,6 +1,8 @@
 """Inputs shared by the PPO2 learner tests (test_ppo2_host.py,
-test_gpu_ppo2.py): the loss-gradient cases and the two error measures of a
-gradient (``block_errs``, ``net_errs``).  Not a test module.
+test_gpu_ppo2.py): the loss-gradient cases, the two error measures of a
+gradient (``block_errs``, ``net_errs``), and consistent rollouts with the
+statement of a whole update (``draw_rollout``, ``update_numpy``).  Not a test
+module.
 
 The loss has kinks at ratio = 1 +- c, at |vpred - old_value| = cv and at
 vf1 = vf2; a float32 kernel that lands on the other side of one from the
@@ -217,3 +219,171 @@ def pg_terms(inputs, hp=HP):
         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
     c = hp.cliprange
     return np.maximum(-adv * ratio, -adv * np.clip(ratio, 1 - c, 1 + c))
+
+
+# ------------------------------------------------------------ whole updates
+# (K, R, D, hidden, A, nminibatches) of test_gpu_ppo2.py's section 8: K R = 40
+# rows in minibatches of 20 (under one 32-row tile), 65 rows in minibatches of
+# 13, 96 rows as one minibatch of three full tiles.  Two epochs each.
+UPDATE_CASES = [(5, 8, 7, (32,), 3, 2), (5, 13, 7, (32,), 3, 5), (6, 16, 7, (32,), 3, 1)]
+UPDATE_CASE_IDS = ['k%d_r%d_mb%d' % (c[0], c[1], c[5]) for c in UPDATE_CASES]
+UPDATE_EPOCHS = 2
+# per call of ``update``: (lr, cliprange or None for the learner's own)
+UPDATE_CALLS = {'own_clip': (1e-2, None), 'call_clip': (5e-3, 0.1)}
+# The draw seed per (case, call): the first seed, counting from 0, at which
+# the statements alone meet ``update_input_holds`` -- every minibatch row
+# MARGIN away from a kink on the float64 trajectory, a step with 0 <
+# clipfrac, and a float32 NumPy trajectory that stays within F32_ROOM of the
+# float64 one in every step's statistics and grad_norm (seed 0 of the 13-row
+# minibatches at lr 1e-2 does not: its last gradient's norm is 6.2e-5 off in
+# float32 NumPy, six times the bound a kernel is held to).  test_ppo2_host.py
+# asserts all of it on the CPU, and that no earlier seed qualifies.  A seed
+# that fails has failed as an input; take the next.
+UPDATE_SEEDS = {(case, call): 0 for case in UPDATE_CASES for call in UPDATE_CALLS}
+UPDATE_SEEDS[UPDATE_CASES[1], 'own_clip'] = 1
+F32_ROOM = 5e-6           # half the 1e-5 every step's statistics and grad_norm are held to
+ROLLOUT_FIELDS = ('obs', 'actions', 'neglogps', 'values', 'rewards', 'dones', 'last_values')
+
+
+def f32(x):
+    """``x`` as the learner's float32 config struct holds it."""
+    return float(np.float32(x))
+
+
+# what the device holds of the learner's defaults
+UPDATE_GAMMA, UPDATE_LAM, UPDATE_MAX_GRAD_NORM = f32(0.99), f32(0.95), f32(0.5)
+UPDATE_ADAM = dict(beta1=f32(0.9), beta2=f32(0.999), eps=f32(1e-5))
+
+
+@functools.lru_cache(maxsize=None)
+def draw_rollout(case, seed):
+    """A consistent rollout as float32 / uint8 host arrays: ``obs [K][R][D]``;
+    ``actions``, ``neglogps`` and ``values`` are ``forward_numpy``'s at
+    ``params`` with unit noise, so the old policy is the current one, as after
+    ``collect``; random ``rewards`` and ``last_values``; ``dones`` at p = 0.3
+    with a row that is never done, one that always is, a done at (K - 1, 2)
+    and at (0, 3), a set flag stored as 1, 2 or 0xFF.  Also ``params`` (flat)
+    and ``perms``: UPDATE_EPOCHS int32 permutations of the K R rows."""
+    K, R, D, hidden, A, _ = case
+    obs, _, params = pc.forward_inputs((K * R, D, hidden, A), seed)
+    flat = dict_to_flat(params, params_layout(D, A, hidden), np.float32)
+    rs = np.random.RandomState(3000 + seed)
+    out = forward_numpy(obs, rs.normal(0, 1, (K * R, A)), flat.astype(np.float64), hidden)
+    done = rs.rand(K, R) < 0.3
+    done[:, 0], done[:, 1], done[K - 1, 2], done[0, 3] = False, True, True, True
+    dones = np.where(done, np.array([1, 2, 0xFF], np.uint8)[rs.randint(0, 3, (K, R))], 0)
+    return {'params': flat, 'hidden': hidden,
+            'obs': np.asarray(obs, np.float32).reshape(K, R, D),
+            'actions': out['action'].astype(np.float32).reshape(K, R, A),
+            'neglogps': out['neglogp'].astype(np.float32).reshape(K, R),
+            'values': out['value'].astype(np.float32).reshape(K, R),
+            'rewards': rs.normal(0, 1, (K, R)).astype(np.float32),
+            'dones': dones.astype(np.uint8),
+            'last_values': rs.normal(0, 1, R).astype(np.float32),
+            'perms': [rs.permutation(K * R).astype(np.int32) for _ in range(UPDATE_EPOCHS)]}
+
+
+def flatten_numpy(rollout, advantages, returns):
+    """``PPO2Learner.flatten`` on host arrays: the [K R] batch."""
+    n = rollout['rewards'].size
+    return {'obs': rollout['obs'].reshape(n, -1), 'actions': rollout['actions'].reshape(n, -1),
+            'advantages': advantages.reshape(n), 'returns': returns.reshape(n),
+            'neglogps': rollout['neglogps'].reshape(n), 'values': rollout['values'].reshape(n)}
+
+
+def update_numpy(params, rollout, perms, nminibatches, hp, lr, dtype=np.float64,
+                 gamma=UPDATE_GAMMA, lam=UPDATE_LAM, max_grad_norm=UPDATE_MAX_GRAD_NORM,
+                 adam=None):
+    """The statement of ``PPO2Learner.update`` in ``dtype``, composed of
+    ``gae_numpy``, ``loss_grad_numpy`` on the gathered rows of each slice of
+    ``perms[epoch]`` and ``adam_step_numpy`` with ``t`` counting across the
+    epochs; no arithmetic of its own.  Returns a dict: ``params``, ``m``, ``v``
+    after the last step, ``returns`` ``[K][R]``, and per step ``stats``,
+    ``grads``, the parameters it started from (``before``) and its gathered
+    ``batches``."""
+    from custom_envs_amd.ppo2 import adam_step_numpy, gae_numpy, loss_grad_numpy
+    adam = UPDATE_ADAM if adam is None else adam
+    adv, ret = gae_numpy(rollout['rewards'], rollout['values'], rollout['dones'],
+                         rollout['last_values'], gamma, lam, dtype=dtype)
+    flat = flatten_numpy(rollout, adv, ret)
+    p = np.asarray(params, dtype)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    size = flat['obs'].shape[0] // nminibatches
+    out = {'stats': [], 'grads': [], 'before': [], 'batches': [], 'returns': ret}
+    for perm in perms:
+        for b in range(nminibatches):
+            idx = np.asarray(perm[b * size:(b + 1) * size])
+            batch = {n: flat[n][idx] for n in BATCH_FIELDS}
+            stats, grad = loss_grad_numpy(p, *[batch[n] for n in BATCH_FIELDS], hp=hp,
+                                          hidden=rollout['hidden'], dtype=dtype)
+            out['stats'].append(stats)
+            out['grads'].append(grad)
+            out['before'].append(p)
+            out['batches'].append(batch)
+            p, m, v = adam_step_numpy(p, grad, m, v, len(out['stats']), lr, max_grad_norm, **adam)
+    out.update(params=p, m=m, v=v)
+    return out
+
+
+def step_margins(before, batch, hidden, hp):
+    """``kink_margins`` of one minibatch at the float64 parameters ``before``
+    (float64 throughout: the statement alone decides)."""
+    A = batch['actions'].shape[1]
+    p = np.asarray(before, np.float64)
+    now = forward_numpy(batch['obs'], None, p, hidden)
+    nlp = true_neglogp(now['mean'], p[-A:], batch['actions'].astype(np.float64))
+    ratio = np.exp(batch['neglogps'].astype(np.float64) - nlp)
+    return kink_margins(ratio, now['value'], batch['values'].astype(np.float64),
+                        batch['returns'].astype(np.float64), hp)
+
+
+def f32_room(ref, ref32):
+    """The float32 statement's largest relative deviation from the float64
+    one over every step's loss, vf_loss, entropy, approxkl (from the second
+    step on: the first step's is rounding noise, the old policy being the
+    current one) and grad_norm.  pg_loss is left out: it cancels by
+    construction at the first step and is held on the scale of its terms."""
+    worst = 0.0
+    for i, (s64, s32, g64, g32) in enumerate(zip(ref['stats'], ref32['stats'], ref['grads'],
+                                                 ref32['grads'])):
+        for name in ('loss', 'vf_loss', 'entropy') + (('approxkl',) if i else ()):
+            worst = max(worst, abs(float(s32[name]) - float(s64[name])) / abs(float(s64[name])))
+        norm = float(np.sqrt(np.sum(g64 * g64)))
+        worst = max(worst, abs(float(np.sqrt(np.sum(g32.astype(np.float64) ** 2))) - norm) / norm)
+    return worst
+
+
+def update_input_holds(rollout, hp, ref, ref32):
+    """The conditions on a draw, from the statements alone (``ref``: the
+    float64 ``update_numpy``, ``ref32``: the float32 one): every minibatch row
+    at least MARGIN from a kink at the float64 parameters its step starts
+    from; a step with 0 < clipfrac; the float32 trajectory's statistics and
+    grad_norm within F32_ROOM of the float64 one's (``f32_room``), so that a
+    kernel held to 1e-5 is not held to what float32 arithmetic cannot give on
+    this draw.  Returns (the smallest margin, the largest clipfrac, the
+    float32 deviation).  A draw that fails has failed as an input."""
+    margin = min(float(step_margins(before, batch, rollout['hidden'], hp).min())
+                 for before, batch in zip(ref['before'], ref['batches']))
+    clipfrac = max(float(s['clipfrac']) for s in ref['stats'])
+    room = f32_room(ref, ref32)
+    assert margin >= MARGIN, 'a minibatch row within %g of a kink: %g' % (MARGIN, margin)
+    assert clipfrac > 0.0, 'no step clips'
+    assert room <= F32_ROOM, 'the float32 statement is %g off the float64 one' % room
+    return margin, clipfrac, room
+
+
+def update_hp(cliprange):
+    """HP with the per-call ``cliprange`` (None: HP's), as float32 holds it.
+    A per-call cliprange moves the policy clip only."""
+    return HP._replace(cliprange=f32(HP.cliprange if cliprange is None else cliprange),
+                       cliprange_vf=f32(HP.cliprange_vf))
+
+
+def update_reference(case, call, dtype=np.float64, seed=None):
+    """``update_numpy`` of the case's committed draw (or of ``seed``) for one
+    UPDATE_CALLS entry: (rollout, hp, lr, the statement's dict)."""
+    lr, cliprange = UPDATE_CALLS[call]
+    rollout = draw_rollout(case, UPDATE_SEEDS[case, call] if seed is None else seed)
+    hp = update_hp(cliprange)
+    return rollout, hp, f32(lr), update_numpy(rollout['params'], rollout, rollout['perms'],
+                                              case[5], hp, f32(lr), dtype=dtype)

@@ -381,3 +381,34 @@ def test_update_validation(change, match):
     change(result, torch)
     with pytest.raises(ValueError, match=match):
         _learner().update(result)
+
+
+# ------------------------------------------------------ 6. per-call rates
+BAD_RATES = [0.0, -1.0, -7e-4, float('nan'), float('inf'), 'fast']
+
+
+@pytest.mark.parametrize('lr', BAD_RATES)
+def test_a_per_call_lr_that_is_not_positive_is_refused(lr):
+    """The native side reads every lr that is not positive as "none given"
+    (Python sends -1 for None), so a schedule's 0.0 would train at the
+    learner's own rate: refused before anything else is looked at."""
+    import torch
+    learner = _learner()
+    records = torch.zeros(1, learner.record_doubles, dtype=torch.float64)
+    for call in (lambda: learner.step(_cpu_batch(), lr=lr),
+                 lambda: learner.step({}, lr=lr),                     # before the batch is looked at
+                 lambda: learner.update(_cpu_result(), lr=lr),
+                 lambda: learner.update({}, lr=lr),
+                 lambda: learner.apply(records, 6, lr=lr),
+                 lambda: learner.apply(None, 0, lr=lr)):
+        with pytest.raises(ValueError, match='lr must be None or a finite positive number'):
+            call()
+
+
+@pytest.mark.parametrize('lr', [None, 1e-30, 7e-4, np.float32(0.1), 3])
+def test_a_positive_per_call_lr_passes_the_check(lr):
+    """The call goes on to the next check, the tensors' device."""
+    for call in (lambda: _learner().step(_cpu_batch(), lr=lr),
+                 lambda: _learner().update(_cpu_result(), lr=lr)):
+        with pytest.raises(ValueError, match='must be on device cuda:0'):
+            call()

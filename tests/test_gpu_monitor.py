@@ -1,7 +1,9 @@
 """The episode monitor's kernels (csrc/monitor_kernels.h) on synthetic rollout
 records: torch tensors built from NumPy, no engine, so any done pattern is
 reachable.  ``utils_logging.episodes_numpy`` / ``explained_variance_numpy`` are
-the statements the kernels are held against."""
+the statements the kernels are held against.  The block scan runs at up to 8
+count blocks in the first test and at 256, 257 and 261 in MANY_BLOCKS' tests
+(more than one count per thread of its one workgroup)."""
 import ctypes
 import math
 
@@ -61,15 +63,18 @@ class Monitor:
         torch.cuda.synchronize()
 
 
-def _records(K, E, P, rs, n_cols=9, pad=5, p_done=0.3, force=True):
+def _records(K, E, P, rs, n_cols=9, pad=5, p_done=0.3, force=True, also=()):
     """Host arrays and their device records: reward / done [K][E * P] (an
     env's are its first agent row's; the other rows hold decoys) and info
-    [K][E][n_cols], every record stride longer than the row."""
+    [K][E][n_cols], every record stride longer than the row.  ``also``: (t,
+    env) pairs whose done is set whatever was drawn."""
     import torch
     reward = rs.normal(0, 3, (K, E * P)).astype(np.float32)
     done = (rs.rand(K, E * P) < p_done).astype(np.uint8)
     if force:
         done[K - 1, 0] = 1               # at least one finished episode
+    for t, e in also:
+        done[t, e * P] = 1
     info = rs.normal(0, 1, (K, E, n_cols)).astype(np.float32)
 
     def strided(a, extra):
@@ -122,6 +127,87 @@ def test_records_equal_episodes_numpy(E, K, P, n_info):
         None), 'get_state')
     for name in state:
         assert state[name].tobytes() == carry[name].tobytes(), name
+    mon.close()
+
+
+# The exclusive scan of the block counts (monitor_blockscan_kernel, one
+# workgroup of 256 threads, thread i sums chunk = ceil(nb / 256) counts from
+# i * chunk) beyond what the cases above reach (nb <= 8): nb = 256 is the last
+# size with chunk = 1; nb = 257 has chunk = 2, the threads from 129 on with an
+# empty range and thread 128 with a range clamped to one block; nb = 261 is
+# the same with K > 1.  p_done = 0.02 keeps the records few.
+MANY_BLOCKS = [(256, 256, 256), (1, 65537, 257), (65, 1025, 261)]
+
+
+def _many_blocks(K, E, nb, seed):
+    """Records with K * E flags in ``nb`` count blocks and a finished episode
+    at the very last flag, at the first flag of block 256 and seven flags on
+    (where they exist)."""
+    n = K * E
+    assert (n + 255) // 256 == nb
+    flags = [i for i in (n - 1, 256 * 256, 256 * 256 + 7) if i < n]
+    return _records(K, E, 1, np.random.RandomState(seed), p_done=0.02,
+                    also=[divmod(i, E) for i in flags])
+
+
+def _blocks_of(want, E):
+    return (want['t'].astype(np.int64) * E + want['env']) // 256
+
+
+@pytest.mark.parametrize('K,E,nb', MANY_BLOCKS)
+@pytest.mark.parametrize('n_info', [0, 2])
+def test_records_equal_episodes_numpy_beyond_256_count_blocks(K, E, nb, n_info):
+    rec = _many_blocks(K, E, nb, 7 * nb + n_info)
+    reward, done, info = rec['np']
+    cols = COLS[n_info]
+    dtype = ul.record_dtype(n_info)
+    want, carry = ul.episodes_numpy(reward, done, info[:, :, list(cols)] if cols else None)
+    blocks = _blocks_of(want, E)
+    assert blocks.max() == nb - 1                    # a finished episode in the last count block
+    if nb > 256:
+        assert (blocks == 256).any()                 # and one past index 255
+    assert len(np.unique(blocks)) > 200              # the offsets differ from block to block
+    mon = Monitor(E)
+    out = mon.out_buffer(len(want) + 8, dtype.itemsize)
+    total = mon.scan(rec, cols, out, len(want) + 8)
+    assert total == len(want)
+    _equal(_host(out, total, dtype), want)
+    assert (out[total * dtype.itemsize:].cpu().numpy() == GUARD).all()
+    state = ul.new_carry(E)
+    _native.check(mon.lib.ce_monitor_get_state(
+        mon.h, *(state[n].ctypes.data for n in ('ep_reward', 'ep_len', 'episode', 'total_steps')),
+        None), 'get_state')
+    for name in state:
+        assert state[name].tobytes() == carry[name].tobytes(), name
+    mon.close()
+
+
+def test_overflow_inside_a_count_block_past_255():
+    """``capacity`` ends between two finished episodes of one count block
+    past index 255: the first ``capacity`` records are written, the guard
+    bytes after them are untouched, and ``ce_monitor_write`` delivers all."""
+    K, E, nb = MANY_BLOCKS[2]
+    cols = COLS[2]
+    rec = _many_blocks(K, E, nb, 11)
+    reward, done, info = rec['np']
+    dtype = ul.record_dtype(2)
+    rb = dtype.itemsize
+    want, _ = ul.episodes_numpy(reward, done, info[:, :, list(cols)])
+    blocks = _blocks_of(want, E)
+    inside = [i for i in range(1, len(want)) if blocks[i] == blocks[i - 1] >= 256]
+    assert inside
+    capacity = inside[0]          # want[capacity - 1] and want[capacity]: one block past 255
+    assert 0 < capacity < len(want)
+    mon = Monitor(E)
+    out = mon.out_buffer(capacity, rb, guard=4096)
+    total = mon.scan(rec, cols, out, capacity)
+    assert total == len(want)
+    _equal(_host(out, capacity, dtype), want[:capacity])
+    assert (out[capacity * rb:].cpu().numpy() == GUARD).all()
+    big = mon.out_buffer(total, rb)
+    mon.write(big, total)
+    _equal(_host(big, total, dtype), want)
+    assert (big[total * rb:].cpu().numpy() == GUARD).all()
     mon.close()
 
 
@@ -239,3 +325,10 @@ def test_explained_variance():
     assert math.isnan(float(_ev(values, const)[0]))         # Var[ret] == 0
     one = _ev(values[:1], returns[:1])                      # K = 1
     assert abs(float(one[0]) - ul.explained_variance_numpy(val[:1], ret[:1])) <= 1e-9
+    # n = 3: 253 of the 256 threads hold no term; n = 256: one term each.
+    # Fewer terms than above, so the same derivation and the same bound.
+    for k, r in ((1, 3), (1, 256), (2, 128)):
+        assert np.var(ret[:k, :r].astype(np.float64)) >= 1e-3
+        few = _ev(values[:k, :r], returns[:k, :r].contiguous())
+        want = ul.explained_variance_numpy(val[:k, :r], ret[:k, :r])
+        assert abs(float(few[0]) - want) <= 1e-9, (k, r, float(few[0]), want)

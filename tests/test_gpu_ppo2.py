@@ -22,6 +22,10 @@ NumPy statements of custom_envs_amd/ppo2.py in float64.
 6. Three ``step`` calls against ``loss_grad_numpy`` + ``adam_step_numpy`` in
    float64, the norm clip biting and idle; the policy image follows.
 7. collect -> gae -> update -> collect, and its bit-identical replay.
+8. The whole ``update`` on consistent synthetic rollouts with explicit
+   permutations: bit-identical to the hand-written gae -> flatten -> step
+   loop, and against ``ppo2_cases.update_numpy`` in float64 (the bounds and
+   the measured values are in the test's docstring).
 """
 import numpy as np
 import pytest
@@ -117,6 +121,21 @@ def _check(case, grad, stats, ref, what, inputs=None, hp=cases.HP):
     print(what, case, 'per network', nerrs, 'bounds', nbounds)
     errs = cases.block_errs(case, grad, ref_grad)
     got = stats.stats()
+    serr, pg_cond, pg_scaled = _stat_errs(got, ref_stats, terms)
+    print(what, case, 'worst block %.3g' % max(errs.values()), errs, serr,
+          'pg_loss: condition %.1f, |d| / mean|term| %.3g' % (pg_cond, pg_scaled))
+    if case in cases.CASES:
+        assert pg_cond <= cases.PG_COND_MAX, (what, pg_cond)
+    for name, err in errs.items():
+        assert err <= BOUND, (what, name, err)
+    for net, err in nerrs.items():
+        assert err <= nbounds[net], (what, net, err, nbounds[net])
+    _hold_stats(what, got, ref_stats, ref_grad, serr, pg_cond, pg_scaled)
+
+
+def _stat_errs(got, ref_stats, terms):
+    """(the relative error of every statistic but clipfrac, pg_loss's
+    condition number, pg_loss's error on the scale of its ``terms``)."""
     # relative; a statistic that is exactly zero (pg_loss of a single
     # normalised row) must come out exactly zero
     serr = {n: abs(got[n] - float(ref_stats[n])) / abs(float(ref_stats[n]))
@@ -126,15 +145,15 @@ def _check(case, grad, stats, ref, what, inputs=None, hp=cases.HP):
     assert abs(float(np.mean(terms)) - pg_ref) <= 1e-12 * max(pg_scale, 1e-300)    # the terms are pg_loss's
     pg_cond = pg_scale / abs(pg_ref) if pg_ref != 0.0 else 0.0
     pg_scaled = abs(got['pg_loss'] - pg_ref) / pg_scale if pg_scale > 0.0 else abs(got['pg_loss'])
-    print(what, case, 'worst block %.3g' % max(errs.values()), errs, serr,
-          'pg_loss: condition %.1f, |d| / mean|term| %.3g' % (pg_cond, pg_scaled))
-    if case in cases.CASES:
-        assert pg_cond <= cases.PG_COND_MAX, (what, pg_cond)
-    for name, err in errs.items():
-        assert err <= BOUND, (what, name, err)
-    for net, err in nerrs.items():
-        assert err <= nbounds[net], (what, net, err, nbounds[net])
+    return serr, pg_cond, pg_scaled
+
+
+def _hold_stats(what, got, ref_stats, ref_grad, serr, pg_cond, pg_scaled, but=()):
+    """The statistics' assertions of ``_check`` (every name but those in
+    ``but``, which the caller holds in another way)."""
     for name, err in serr.items():
+        if name in but:
+            continue
         if name != 'pg_loss' or pg_cond <= cases.PG_COND_MAX:
             assert err <= BOUND, (what, name, err)
     assert pg_scaled <= BOUND, (what, 'pg_loss on the scale of its terms', pg_scaled)
@@ -381,3 +400,165 @@ def test_collect_gae_update_collect():
     b = _closed_loop()
     for key in a:
         assert np.array_equal(a[key], b[key]), key
+
+
+# --------------------------------------- 8. the whole update, the statement
+def _strided_rollout(rollout):
+    """The rollout's records on the device as ``collect`` leaves them: each
+    field a [K]-row view into a wider buffer with its own pad (NaN in the
+    float pads, so a read outside a record shows), ``last_values`` [R]."""
+    import torch
+    K = rollout['rewards'].shape[0]
+    out = {}
+    for extra, name in enumerate(cases.ROLLOUT_FIELDS[:-1], 3):
+        a = rollout[name]
+        row = a.reshape(K, -1)
+        buf = np.full((K, row.shape[1] + extra), 1 if a.dtype == np.uint8 else np.nan, a.dtype)
+        buf[:, :row.shape[1]] = row
+        view = torch.from_numpy(buf).cuda()[:, :row.shape[1]]
+        out[name] = view.unflatten(1, a.shape[1:]) if a.ndim == 3 else view
+        assert out[name].stride(0) > row.shape[1]
+    out['last_values'] = torch.from_numpy(rollout['last_values']).cuda()
+    return out
+
+
+def _update_learner(case, rollout):
+    _, _, D, hidden, A, _ = case
+    learner = PPO2Learner(MlpPolicy(D, A, hidden), cliprange=cases.HP.cliprange,
+                          cliprange_vf=cases.HP.cliprange_vf, ent_coef=cases.HP.ent_coef,
+                          vf_coef=cases.HP.vf_coef, normalize_adv=cases.HP.normalize_adv)
+    learner.set_params(rollout['params'])
+    return learner
+
+
+def _learner_state(learner):
+    import torch
+    torch.cuda.synchronize()
+    state = learner.get_opt_state()
+    return {'params': learner.get_params(), 'm': state['m'], 'v': state['v'], 'step': state['step']}
+
+
+@pytest.mark.parametrize('call', sorted(cases.UPDATE_CALLS))
+@pytest.mark.parametrize('case', cases.UPDATE_CASES, ids=cases.UPDATE_CASE_IDS)
+def test_update_follows_the_statement(case, call):
+    """``update(perms=...)`` (GAE, flatten, two epochs of ``step`` calls over
+    slices of explicit permutations, per-minibatch advantage normalisation,
+    Adam's counter, the repack after every step) with a per-call ``lr`` (and,
+    for ``call_clip``, ``cliprange``) against
+
+    1. the hand-written gae -> flatten -> step(batch, perm[slice]) loop on a
+       second learner: parameters, optimiser state, every step's statistics
+       and ``last_returns`` bit-identical;
+    2. ``ppo2_cases.update_numpy`` in float64: ``last_returns`` bit-equal to the
+       float32 GAE statement and 1e-5 norm-relative to the float64 one; ``m``,
+       ``v`` and ``dp = p_after - p_before`` within max(1e-5, 2 e32) in
+       max|d| / max|ref|, e32 being the float32 ``update_numpy``'s own error in
+       that measure; every step's statistics as ``_check`` holds them,
+       clipfrac exact.
+
+    The draw is chosen from the statements alone (``cases.update_input_holds``,
+    asserted here and in test_ppo2_host.py): every minibatch row
+    ``cases.MARGIN`` off the loss's kinks on the float64 trajectory, a step
+    that clips, and a float32 NumPy trajectory within ``cases.F32_ROOM`` of the
+    float64 one in every step's statistics and grad_norm; a seed that fails it
+    failed as an input.
+    lr = 1e-2 (5e-3) on purpose: at the default 2.5e-4 four steps move a
+    parameter by less than a thousand float32 ulps and the float32 statement
+    itself is 1e-4 off in dp.
+
+    One exception to 1e-5 relative: the first step's approxkl.  The old policy
+    is the current one there, so neglogp - old_neglogp is zero but for the
+    float32 rounding of the stored actions and neglogp, and approxkl (6e-15 in
+    the float64 statement, 6e-14 in the float32 one) is rounding noise with no
+    digits to compare.  It is held to 0.5 (1e-5 max|neglogp|)^2, the project's
+    float32 bound on the scale of what is subtracted (3e-9 here; the device
+    gives 1.9e-14 at the most).
+
+    Measured on the MI355X, worst over the six runs (smallest margin 1.7e-3,
+    clipfrac up to 1.0, float32 statement's statistics and grad_norm within
+    3.4e-6):
+
+        returns  7.7e-08 norm-relative (bound 1e-5), bit-equal in float32
+        dp       device 6.3e-06   e32 up to 1.7e-05   (bound max(1e-5, 2 e32))
+        m        device 3.5e-06   e32 up to 4.0e-06
+        v        device 5.8e-06   e32 up to 8.2e-06
+        loss 2.4e-07, vf_loss 1.8e-07, entropy 5.8e-08, approxkl 2.5e-06 (steps
+        after the first), grad_norm 7.0e-06, pg_loss 9.3e-06 where its condition
+        number is under 50 and 2.9e-07 of mean|term| everywhere (bound 1e-5
+        each); clipfrac exact
+    """
+    import torch
+    K, R, _, hidden, _, nminibatches = case
+    lr, cliprange = cases.UPDATE_CALLS[call]
+    rollout, hp, lr32, ref = cases.update_reference(case, call)
+    f32 = cases.update_reference(case, call, dtype=np.float32)[3]
+    margin, top_clip, _ = cases.update_input_holds(rollout, hp, ref, f32)
+    result = _strided_rollout(rollout)
+    perms = [torch.from_numpy(p).cuda() for p in rollout['perms']]
+
+    learner = _update_learner(case, rollout)
+    stats = learner.update(result, noptepochs=cases.UPDATE_EPOCHS, nminibatches=nminibatches,
+                           perms=perms, lr=lr, cliprange=cliprange)
+    got = _learner_state(learner)
+    got_ret = _np(learner.last_returns)
+    n_steps = cases.UPDATE_EPOCHS * nminibatches
+    assert len(stats) == n_steps and got['step'] == n_steps
+
+    # 1. device against device
+    loop = _update_learner(case, rollout)
+    adv, ret = loop.gae(result)
+    batch = loop.flatten(result, adv, ret)
+    size = K * R // nminibatches
+    loop_stats = [loop.step(batch, perm[b * size:(b + 1) * size], lr=lr, cliprange=cliprange)
+                  for perm in perms for b in range(nminibatches)]
+    want = _learner_state(loop)
+    for name in ('params', 'm', 'v'):
+        assert np.array_equal(got[name], want[name]), name
+    assert got['step'] == want['step']
+    for i, (a, b) in enumerate(zip(stats, loop_stats)):
+        assert np.array_equal(_np(a.tensor), _np(b.tensor)), i
+    assert np.array_equal(got_ret, _np(ret))
+
+    # 2. device against the statement
+    assert got_ret.shape == (K, R) and not np.isnan(got_ret).any()
+    assert np.array_equal(got_ret, f32['returns'])
+    ret_err = np.linalg.norm(got_ret - ref['returns']) / np.linalg.norm(ref['returns'])
+    assert ret_err <= BOUND, ret_err
+    p0 = rollout['params'].astype(np.float64)
+    measures = {}
+    for name in ('dp', 'm', 'v'):
+        r = ref['params'] - p0 if name == 'dp' else ref[name]
+        g = got['params'].astype(np.float64) - p0 if name == 'dp' else got[name]
+        s = f32['params'].astype(np.float64) - p0 if name == 'dp' else f32[name]
+        measures[name] = (pc.rel_err(g, r), pc.rel_err(s, r))
+    print('update', case, call, 'margin %.3g, largest clipfrac %.2f, returns %.3g; '
+          % (margin, top_clip, ret_err),
+          ', '.join('%s device %.3g e32 %.3g' % (n, e[0], e[1]) for n, e in measures.items()))
+    for name, (err, e32) in measures.items():
+        assert err <= max(BOUND, 2 * e32), (name, err, e32)
+    for i, (stat, ref_stats) in enumerate(zip(stats, ref['stats'])):
+        what = 'update %s %s step %d' % (case, call, i)
+        inputs = dict(ref['batches'][i], params=ref['before'][i], hidden=hidden)
+        step_stats = stat.stats()
+        serr, pg_cond, pg_scaled = _stat_errs(step_stats, ref_stats, cases.pg_terms(inputs, hp))
+        norm = np.sqrt(np.sum(ref['grads'][i] ** 2))
+        n32 = abs(np.sqrt(np.sum(f32['grads'][i].astype(np.float64) ** 2)) - norm) / norm
+        print(what, serr, 'clipfrac %g' % step_stats['clipfrac'],
+              'pg_loss: condition %.1f, |d| / mean|term| %.3g' % (pg_cond, pg_scaled),
+              'grad_norm device %.3g e32 %.3g' % (abs(step_stats['grad_norm'] - norm) / norm, n32))
+        _hold_stats(what, step_stats, ref_stats, ref['grads'][i], serr, pg_cond, pg_scaled,
+                    but=('approxkl',) if i == 0 else ())
+    top = float(np.max(np.abs(rollout['neglogps'])))
+    first_kl = stats[0].stats()['approxkl']
+    print('update', case, call, 'first approxkl %.3g, bound %.3g' % (first_kl, 0.5 * (BOUND * top) ** 2))
+    assert first_kl <= 0.5 * (BOUND * top) ** 2, first_kl
+    # the repack followed the last step
+    obs = torch.from_numpy(rollout['obs'][0]).cuda()
+    out = learner.policy.forward_device(obs)
+    torch.cuda.synchronize()
+    fwd = forward_numpy(rollout['obs'][0], None, got['params'].astype(np.float64), hidden)
+    assert pc.rel_err(_np(out['action']), fwd['mean']) <= BOUND
+    assert pc.rel_err(_np(out['value']), fwd['value']) <= BOUND
+    for l in (learner, loop):
+        l.close()
+        l.policy.close()

@@ -415,3 +415,82 @@ def test_update_validation(change, match):
         _learner().update(result, noptepochs=1, nminibatches=2)
     with pytest.raises(ValueError, match='do not split'):
         _learner().update(dict(result, actions=torch.zeros(4, 3, 2)), nminibatches=5)
+
+
+# ------------------------------------------------------ 6. per-call rates
+BAD_RATES = [0.0, -1.0, -2.5e-4, float('nan'), float('inf'), 'fast']
+
+
+def _cpu_result():
+    import torch
+    return {'obs': torch.zeros(4, 3, 5), 'actions': torch.zeros(4, 3, 2),
+            'values': torch.zeros(4, 3), 'neglogps': torch.zeros(4, 3),
+            'rewards': torch.zeros(4, 3), 'dones': torch.zeros(4, 3, dtype=torch.uint8),
+            'last_values': torch.zeros(3)}
+
+
+@pytest.mark.parametrize('name', ['lr', 'cliprange'])
+@pytest.mark.parametrize('rate', BAD_RATES)
+def test_a_per_call_rate_that_is_not_positive_is_refused(name, rate):
+    """The native side reads every lr / cliprange that is not positive as
+    "none given" (Python sends -1 for None), so a schedule's 0.0 would train
+    at the learner's own rate: refused before anything else is looked at."""
+    import torch
+    learner = _learner()
+    kw = {name: rate}
+    calls = [lambda: learner.step(_cpu_batch(), **kw),
+             lambda: learner.step({}, **kw),                          # before the batch is looked at
+             lambda: learner.update(_cpu_result(), nminibatches=2, **kw),
+             lambda: learner.update({}, **kw)]
+    if name == 'lr':
+        records = torch.zeros(1, learner.record_doubles, dtype=torch.float64)
+        calls += [lambda: learner.apply(records, 6, lr=rate), lambda: learner.apply(None, 0, lr=rate)]
+    else:
+        calls += [lambda: learner.grad(_cpu_batch(), cliprange=rate),
+                  lambda: learner.partial(_cpu_batch(), cliprange=rate)]
+    for call in calls:
+        with pytest.raises(ValueError, match='%s must be None or a finite positive number' % name):
+            call()
+
+
+@pytest.mark.parametrize('rate', [None, 1e-30, 2.5e-4, np.float32(0.1), 3])
+def test_a_positive_per_call_rate_passes_the_check(rate):
+    """The call goes on to the next check, the tensors' device."""
+    for call in (lambda: _learner().step(_cpu_batch(), lr=rate, cliprange=rate),
+                 lambda: _learner().update(_cpu_result(), nminibatches=2, lr=rate, cliprange=rate),
+                 lambda: _learner().grad(_cpu_batch(), cliprange=rate)):
+        with pytest.raises(ValueError, match='must be on device cuda:0'):
+            call()
+
+
+# ------------------------------------------------- 7. whole updates' inputs
+@pytest.mark.parametrize('call', sorted(cases.UPDATE_CALLS))
+@pytest.mark.parametrize('case', cases.UPDATE_CASES, ids=cases.UPDATE_CASE_IDS)
+def test_update_draws_stay_off_the_kinks_and_clip(case, call):
+    """What test_gpu_ppo2.py's section 8 needs of its committed draws, from
+    the statements alone (``cases.update_input_holds``: off the kinks, a step
+    that clips, a float32 NumPy trajectory within ``cases.F32_ROOM`` of the
+    float64 one); and the committed seed is the first that meets it."""
+    rollout, hp, lr, ref = cases.update_reference(case, call)
+    ref32 = cases.update_reference(case, call, dtype=np.float32)[3]
+    margin, clipfrac, room = cases.update_input_holds(rollout, hp, ref, ref32)
+    print(case, call, 'smallest margin %.3g, largest clipfrac %.2f, float32 statement %.3g'
+          % (margin, clipfrac, room))
+    for seed in range(cases.UPDATE_SEEDS[case, call]):
+        earlier = cases.update_reference(case, call, seed=seed)
+        with pytest.raises(AssertionError):
+            cases.update_input_holds(earlier[0], hp, earlier[3],
+                                     cases.update_reference(case, call, np.float32, seed)[3])
+    K, R, _, _, _, nminibatches = case
+    assert len(ref['stats']) == cases.UPDATE_EPOCHS * nminibatches
+    assert ref['returns'].shape == (K, R) and ref['params'].dtype == np.float64
+    for perm in rollout['perms']:
+        assert sorted(perm) == list(range(K * R))
+    # the old policy is the current one: the first step's ratio is 1
+    assert float(ref['stats'][0]['approxkl']) < 1e-12 and float(ref['stats'][0]['clipfrac']) == 0.0
+    assert all(ref32[n].dtype == np.float32 for n in ('params', 'm', 'v', 'returns'))
+    assert pc_rel(ref32['params'], ref['params']) < 1e-5
+
+
+def pc_rel(got, ref):
+    return float(np.max(np.abs(got.astype(np.float64) - ref)) / np.max(np.abs(ref)))
