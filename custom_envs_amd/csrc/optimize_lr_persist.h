@@ -80,6 +80,16 @@ constexpr int kLpMaxTpw = 8;                  // row tiles a wave keeps in regis
 #ifndef CE_LP_WD_HANDOVER
 #define CE_LP_WD_HANDOVER 1
 #endif
+// the wave-specialised kernel keeps the gradient A operands of a row wave's
+// first CE_LP_GA_REGS tiles (all of them by default: it has at most 4) in
+// VGPRs for the whole launch: they are the data set, read back once from the
+// wave's LDS transposition tile in the prologue, where the step loop read
+// them from LDS every step (6 ds_read_b128 per tile on the benchmark
+// instance).  The same operands in the same MFMAs: no bit changes.
+// CE_LP_GA_REGS=0 is the earlier code path, every tile's operands in LDS.
+#ifndef CE_LP_GA_REGS
+#define CE_LP_GA_REGS 4
+#endif
 __host__ __device__ constexpr bool lp_g4(int nkf) { return CE_LP_G4 && nkf <= 3; }
 // The epilogue wave that owns the weights (index among the epilogue waves):
 // the parameter roles' second round fills from epilogue wave 0 upwards and
@@ -474,9 +484,14 @@ __global__ __launch_bounds__(kWave * W) void optimize_lr_persist_kernel(StepArgs
 // next barrier finds them done.  The LDS partials and staged observation
 // blocks are double-buffered by step parity, as above, so one barrier per
 // step orders both (row waves: rows t, partials t -> buf, barrier t;
-// epilogue waves: barrier t, flush obs t - 1, epilogue t from buf).  To fit
-// two waves per SIMD (256 registers each) the gradient A operands live in
-// the row wave's own LDS tiles instead of registers.  Same arithmetic, same summation
+// epilogue waves: barrier t, flush obs t - 1, epilogue t from buf).  Two
+// waves per SIMD leave each 256 registers.  The row wave holds its tiles'
+// forward and gradient A operands in them (CE_LP_GA_REGS; the 4x4x4 gradient
+// operands are transposed once through one LDS tile per row wave in the
+// prologue): the largest instance, <3,4,true>, takes 223.  With
+// CE_LP_GA_REGS below TPW the other tiles' gradient operands stay in the row
+// wave's own LDS tiles and are read every step, as every tile's were when the
+// row wave also carried the weights.  Same arithmetic, same summation
 // order as optimize_lr_persist_kernel<NKF, TPW, PAD, 4>: bit-identical.
 template <int NKF, int TPW, bool PAD>
 __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
@@ -500,8 +515,15 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
     // twice
     constexpr bool G4 = lp_g4(NKF);
     constexpr int G4S = 14;
-    __shared__ __attribute__((aligned(16))) double xgs[G4 ? 1 : W][G4 ? 1 : TPW][4][kWave];
-    __shared__ __attribute__((aligned(16))) double xga[G4 ? W : 1][G4 ? TPW : 1][16][G4S];
+    // A wave's first NR tiles keep these operands in registers (gvr below),
+    // so LDS holds the other TPW - NR only: 16x16x4 tile i in slot i - NR; 4x4x4
+    // tile i in slot i - NR + 1 behind slot 0, the transposition tile that every
+    // register-held tile passes through in the prologue (NR = 0: slot i).
+    constexpr int NR = CE_LP_GA_REGS < TPW ? CE_LP_GA_REGS : TPW;
+    constexpr int GS0 = G4 && NR > 0 ? 1 - NR : -NR;        // slot of tile i >= NR: i + GS0
+    constexpr int NGS = TPW + GS0 > 0 ? TPW + GS0 : 1;      // slots per row wave
+    __shared__ __attribute__((aligned(16))) double xgs[G4 ? 1 : W][G4 ? 1 : NGS][4][kWave];
+    __shared__ __attribute__((aligned(16))) double xga[G4 ? W : 1][G4 ? NGS : 1][16][G4S];
     __shared__ double tab_s[CE_LR_TEXP ? kLrExpTab : 1];   // the row waves' exp table
 #if CE_LP_WD_HANDOVER
     // The hand-over ring: slot s mod 2 holds step s's margins wd (lane (h, c):
@@ -593,6 +615,8 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
 #pragma unroll
         for (int k = 0; k < NKF; ++k) w0v[k] = *reinterpret_cast<const double2 *>(a.W0 + ioff[k]);
 #endif
+        // the gradient A operands of tiles 0 .. NR - 1, in the step loop's order
+        [[maybe_unused]] double gvr[NR > 0 ? NR : 1][G4 ? 4 * NKF : 4];
         unsigned vmask = 0;
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
@@ -602,6 +626,9 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
 #pragma unroll
             for (int k = 0; k < NKF; ++k) xf[i][k] = live ? ti[k * kWave + lane] : 0.0;
             if constexpr (G4) {
+                // tile i >= NR into its LDS slot (a dead tile: zeros); a
+                // register-held one goes through slot 0, below
+                const int s = i < NR ? 0 : i + GS0;
 #if CE_LP_G4_XF
                 // from the forward operands already in registers (no second
                 // copy of the tile read from L2 in the prologue): lane (h, c)
@@ -609,18 +636,25 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 // (k = c & 3, m = h), column j = c >> 2, group g
                 const int km = 4 * (c & 3) + h, j4 = c >> 2;
 #pragma unroll
-                for (int g = 0; g < NKF; ++g) xga[wave][i][km][j4 * NKF + g] = xf[i][g];
+                for (int g = 0; g < NKF; ++g)
+                    if (i >= NR) xga[wave][s][km][j4 * NKF + g] = xf[i][g];
 #else
                 // lane (k, b, m) keeps feature group g = b: its own lane of the
                 // tile's gradient slot j is X~[16t + 4j + k][4b + m]
                 const int b4 = (lane >> 2) & 3, km = 4 * (lane >> 4) + (lane & 3);
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    if (b4 < NKF) xga[wave][i][km][q * NKF + b4] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
+                    if (i >= NR && b4 < NKF) xga[wave][s][km][q * NKF + b4] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
 #endif
-            } else {
+            } else if (i >= NR) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) xgs[wave][i][q][lane] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
+                for (int q = 0; q < 4; ++q)
+                    xgs[wave][i + GS0][q][lane] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
+            } else {
+                // the 16x16x4 operand is the lane's own value of the image's
+                // gradient slot: no LDS on its way
+#pragma unroll
+                for (int q = 0; q < 4; ++q) gvr[i][q] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
             }
             if constexpr (PAD) {
                 const int2 ya = reinterpret_cast<const int2 *>(ti + (NKF + 4) * kWave)[lane];
@@ -628,6 +662,41 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                 const int ys[4] = {ya.x, ya.y, yb.x, yb.y};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) vmask |= (live && ys[q] >= 0 ? 1u : 0u) << (4 * i + q);
+            }
+        }
+        if constexpr (G4 && NR > 0) {
+            // The register-held tiles, behind every tile's loads: tile i is
+            // transposed through slot 0 and read back with the step loop's
+            // per-lane address, then the next one takes the slot.  A wave's
+            // LDS operations execute in order, so the read-back finds the
+            // wave's own writes landed and is itself done before the next
+            // tile's; the wave barriers (no instruction) hold the compiler to
+            // that order.
+            typedef double lp_d2 __attribute__((ext_vector_type(2)));
+            const lp_d2 *src = reinterpret_cast<const lp_d2 *>(&xga[wave][0][4 * (lane >> 4) + (lane & 3)][0]);
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+#if CE_LP_G4_XF
+                const int km = 4 * (c & 3) + h, j4 = c >> 2;    // as above
+#pragma unroll
+                for (int g = 0; g < NKF; ++g) xga[wave][0][km][j4 * NKF + g] = xf[i][g];
+#else
+                const int t = wave + W * i;
+                const bool live = !PAD || t < ntiles;
+                const double *ti = img + static_cast<unsigned>(live ? t : 0) * TD;
+                const int b4 = (lane >> 2) & 3, km = 4 * (lane >> 4) + (lane & 3);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (b4 < NKF) xga[wave][0][km][q * NKF + b4] = live ? ti[(NKF + q) * kWave + lane] : 0.0;
+#endif
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int p2 = 0; p2 < 2 * NKF; ++p2) {
+                    const lp_d2 v = src[p2];
+                    gvr[i][2 * p2] = v.x;
+                    gvr[i][2 * p2 + 1] = v.y;
+                }
+                __builtin_amdgcn_wave_barrier();
             }
         }
 #if !CE_LP_WD_HANDOVER
@@ -716,10 +785,13 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
 #pragma unroll
                     for (int i = 0; i < NG; ++i) {
                         double gv[G4 ? 4 * NKF : 4];
-                        if constexpr (G4) {
+                        if (g0 + i < NR) {                  // static: the loops are unrolled
+#pragma unroll
+                            for (int j = 0; j < (G4 ? 4 * NKF : 4); ++j) gv[j] = gvr[g0 + i < NR ? g0 + i : 0][j];
+                        } else if constexpr (G4) {
                             typedef double lp_d2 __attribute__((ext_vector_type(2)));
                             const lp_d2 *src = reinterpret_cast<const lp_d2 *>(
-                                &xga[wave][g0 + i][4 * (lane >> 4) + (lane & 3)][0]);
+                                &xga[wave][g0 + i + GS0][4 * (lane >> 4) + (lane & 3)][0]);
 #pragma unroll
                             for (int p2 = 0; p2 < 2 * NKF; ++p2) {
                                 const lp_d2 v = src[p2];
@@ -728,7 +800,7 @@ __global__ __launch_bounds__(512) void optimize_lr_persist_ws_kernel(
                             }
                         } else {
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) gv[q] = xgs[wave][g0 + i][q][lane];
+                            for (int q = 0; q < 4; ++q) gv[q] = xgs[wave][g0 + i + GS0][q][lane];
                         }
                         double qv[4];
                         static_assert(QC == 4, "the tile's four values go through the exp together");
