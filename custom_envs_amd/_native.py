@@ -63,6 +63,8 @@ EXPORTS = (
     'ce_monitor_record_bytes', 'ce_monitor_create', 'ce_monitor_destroy', 'ce_monitor_reset',
     'ce_monitor_scan', 'ce_monitor_write', 'ce_monitor_get_state', 'ce_monitor_set_state',
     'ce_explained_variance',
+    'ce_vecnorm_create', 'ce_vecnorm_destroy', 'ce_vecnorm_step', 'ce_vecnorm_get_state',
+    'ce_vecnorm_set_state', 'ce_rollout_policy_vecnorm', 'ce_multi_rollout_policy_vecnorm',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -162,6 +164,25 @@ MONITOR_RECORD_HEAD = 32     # bytes of an episode record before its info column
 class CeMonitorColumn(ctypes.Structure):
     _fields_ = [('base', ctypes.c_void_p), ('stride_bytes', ctypes.c_int64),
                 ('row_floats', ctypes.c_int32), ('col', ctypes.c_int32)]
+
+
+CE_VECNORM_TRAINING, CE_VECNORM_RESET, CE_VECNORM_OBS_ONLY = 1, 2, 4
+CE_NOISE_BLOCK, CE_NOISE_GENERATED = 0, 1
+
+
+class CeVecnormConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('device', ctypes.c_int32),
+                ('rows', ctypes.c_int64), ('obs_dim', ctypes.c_int32),
+                ('norm_obs', ctypes.c_int32), ('norm_reward', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('clip_obs', ctypes.c_double),
+                ('clip_reward', ctypes.c_double), ('gamma', ctypes.c_double),
+                ('epsilon', ctypes.c_double)]
+
+
+class CeRolloutNoise(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('ptr', ctypes.c_void_p), ('stride', ctypes.c_int64), ('seed', ctypes.c_uint64),
+                ('t0', ctypes.c_uint32), ('row0', ctypes.c_uint32)]
 
 
 class CeState(ctypes.Structure):
@@ -318,6 +339,18 @@ def _declare(lib):
         'ce_monitor_get_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_monitor_set_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_explained_variance': ([i32, i64, vp, i64, vp, vp, vp], ctypes.c_int),
+        'ce_vecnorm_create': ([ctypes.POINTER(CeVecnormConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_vecnorm_destroy': ([vp], None),
+        'ce_vecnorm_step': ([vp, vp, vp, vp, vp, vp, u32, vp], ctypes.c_int),
+        'ce_vecnorm_get_state': ([vp] * 9, ctypes.c_int),
+        'ce_vecnorm_set_state': ([vp] * 9, ctypes.c_int),
+        'ce_rollout_policy_vecnorm': ([vp, vp, vp, i32, vp, i64, vp, i64, u32,
+                                       ctypes.POINTER(CeRolloutNoise), ctypes.POINTER(CeOutputs),
+                                       i64, ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
+        'ce_multi_rollout_policy_vecnorm': ([vp, vp, vp, i32, vp, i64, vp, i64, u32,
+                                             ctypes.POINTER(CeRolloutNoise),
+                                             ctypes.POINTER(CeMultiOutputs), i64,
+                                             ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

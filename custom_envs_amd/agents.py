@@ -20,8 +20,10 @@ generator's position, so a resumed run continues bit for bit.
 
 What differs from stable-baselines, on purpose:
 
-* ``env`` is a ``GPUVecEnv`` or an engine-backed ``OptVecEnv``; rows are envs x
-  agents.  ``seed`` seeds the agent (initial parameters, noise,
+* ``env`` is a ``GPUVecEnv`` or an engine-backed ``OptVecEnv``, bare or inside
+  a ``vectorize.vecnormalize.VecNormalize`` (``PPO2`` and ``A2C``; the running
+  moments are saved with its ``save_running_average``, not by ``save``); rows
+  are envs x agents.  ``seed`` seeds the agent (initial parameters, noise,
   permutations), not the env, which is seeded where it is built.
 * ``learn`` resets the env only when it has no observation to start from, so
   a second ``learn`` (``reset_num_timesteps=False``) continues the episodes.
@@ -87,7 +89,8 @@ records.  What differs from stable-baselines there:
   cycle trains only when every rank's memory holds ``batch_size`` records
   (decided on every rank from ``counts`` and the cycle number, without
   communication), and ``save(memory=True)`` holds that rank's memory only;
-* parameter noise, layer norm, observation / return normalisation, pop-art,
+* parameter noise, layer norm, observation / return normalisation (DDPG's own,
+  and a ``VecNormalize`` env), pop-art,
   ``critic_l2_reg``, ``clip_norm``, ``reward_scale != 1``,
   ``random_exploration``, ``eval_env`` and ``render`` raise ``ValueError``.
 """
@@ -123,9 +126,13 @@ class EnvSpec:
 def env_spec(env):
     """``EnvSpec`` of a ``GPUVecEnv`` or an engine-backed ``OptVecEnv`` (rows
     are envs x agents; widths from the env's engine, bounds from its action
-    space); an ``EnvSpec`` passes through.  Anything else: ``TypeError``."""
+    space), or of a ``VecNormalize`` around one; an ``EnvSpec`` passes
+    through.  Anything else: ``TypeError``."""
     if isinstance(env, EnvSpec):
         return env
+    from custom_envs_amd.vectorize.vecnormalize import VecNormalize
+    if isinstance(env, VecNormalize):        # the wrapped env's shape
+        return env_spec(env.venv)
     from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
     from custom_envs_amd.vectorize.optvecenv import OptVecEnv
     if isinstance(env, GPUVecEnv):
@@ -313,6 +320,10 @@ class BaseAgent:
         from ``counts`` alone wherever another rank would refuse.  Returns the
         exchange."""
         from custom_envs_amd.distributed import GradientExchange
+        from custom_envs_amd.vectorize.vecnormalize import VecNormalize
+        if isinstance(self.env, VecNormalize):
+            raise NotImplementedError('distribute() with a VecNormalize env is not supported: the '
+                                      'ranks\' running moments are not merged')
         if self.dist is not None:
             raise RuntimeError('distribute() was already called on this model')
         world, rank = int(world), int(rank)
@@ -714,6 +725,10 @@ class DDPG(BaseAgent):
                  buffer_size=50000, random_exploration=0.0, verbose=0, seed=None,
                  policy_kwargs=None, diagnostics=False):
         self.diagnostics = bool(diagnostics)
+        from custom_envs_amd.vectorize.vecnormalize import VecNormalize
+        if isinstance(env, VecNormalize):
+            raise ValueError('DDPG on a VecNormalize env is not supported (collect_ddpg has no '
+                             'normalised form)')
         if policy is not ddpg.MlpPolicy and policy != 'MlpPolicy':
             if getattr(policy, '__name__', policy) == 'LnMlpPolicy':
                 raise ValueError('layer_norm (LnMlpPolicy) is not supported')

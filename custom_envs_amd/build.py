@@ -33,6 +33,7 @@ def sources():
                                             'multi_engine.hip', 'multinn_engine.hip', 'net_engine.hip',
                                             'policy_engine.hip', 'ppo2_engine.hip', 'a2c_engine.hip',
                                             'ddpg_engine.hip', 'monitor_engine.hip',
+                                            'vecnorm_engine.hip',
                                             'seeding.cpp')]
 
 

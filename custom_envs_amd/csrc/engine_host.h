@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "policy_engine.h"
+#include "vecnorm_engine.h"
 
 namespace ce {
 
@@ -372,11 +373,14 @@ int host_step_many_strided(E *e, int32_t k, const float *actions, int64_t stride
 // [policy, env step] x k: step s reads the observation step s - 1 wrote
 // (obs0 first) and writes record s of `out` and `pout`; its noise is
 // `noise.at(s)`: the caller's block s, or draw t0 + s of the generator.  The
-// arguments are checked before was_reset.
+// arguments are checked before was_reset.  With `vn` a third launch per step
+// normalises record s's obs and reward into vn's slot s + 1 and record s, and
+// the policy reads the normalised slots (obs0 is slot 0); the raw records stay.
 template <class Ops, class E, class O>
 int host_rollout_policy(const char *who, E *e, const ce_policy *p, int32_t k, const float *obs0,
                         const PolicyNoise &noise, const O *out, int64_t out_step,
-                        const ce_policy_outputs *pout, int64_t pout_step) {
+                        const ce_policy_outputs *pout, int64_t pout_step,
+                        const VecnormRollout *vn = nullptr) {
     const auto bad = [who](int code, const char *what) { return fail(code, std::string(who) + what); };
     if (noise.generated) {      // needs no engine: checked first
         const int rc = policy_rng_args_ok(who, k, 0, noise.t0, noise.row0);
@@ -395,6 +399,7 @@ int host_rollout_policy(const char *who, E *e, const ce_policy *p, int32_t k, co
     if (rc != CE_OK) return rc;
     if (noise.generated && (rc = policy_rng_args_ok(who, k, rows, noise.t0, noise.row0)) != CE_OK)
         return rc;
+    if (vn && (rc = vecnorm_rollout_shape_ok(who, *vn, rows, obs_dim)) != CE_OK) return rc;
     if (!h.was_reset) return bad(CE_ESTATE, " before the first reset()");
     CE_CLEAR_STALE_ERROR();
     const float *obs = obs0;
@@ -404,6 +409,11 @@ int host_rollout_policy(const char *who, E *e, const ce_policy *p, int32_t k, co
         policy_launch(p, obs, noise.at(s), rows, po, h.stream);
         if ((rc = Ops::step(e, po.env_action, eo, true)) != CE_OK) return rc;
         obs = eo.obs;
+        if (vn) {
+            vecnorm_launch(vn->vn, eo.obs, eo.reward, eo.done, vn->obs_slot(s + 1),
+                           vn->reward_slot(s), vn->flags, h.stream);
+            obs = vn->obs_slot(s + 1);
+        }
     }
     CE_HIP(hipGetLastError());
     return CE_OK;

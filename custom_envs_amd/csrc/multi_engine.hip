@@ -264,6 +264,22 @@ int ce_multi_rollout_policy_rng(ce_multi_engine *e, const ce_policy *p, int32_t 
                                              pout, pout_step);
 }
 
+int ce_multi_rollout_policy_vecnorm(ce_multi_engine *e, const ce_policy *p, ce_vecnorm *vn,
+                                    int32_t k, float *obs_norm, int64_t obs_norm_step,
+                                    float *reward_norm, int64_t reward_norm_step,
+                                    uint32_t vn_flags, const ce_rollout_noise *noise,
+                                    const ce_multi_outputs *out, int64_t out_step,
+                                    const ce_policy_outputs *pout, int64_t pout_step) {
+    const char *who = "ce_multi_rollout_policy_vecnorm";
+    const int rc = ce::vecnorm_rollout_plain_ok(who, e != nullptr, p, vn, k, obs_norm,
+                                                obs_norm_step, reward_norm, reward_norm_step,
+                                                vn_flags, noise, out, pout);
+    if (rc != CE_OK) return rc;
+    const ce::VecnormRollout v{vn, obs_norm, obs_norm_step, reward_norm, reward_norm_step, vn_flags};
+    return ce::host_rollout_policy<MultiOps>(who, e, p, k, obs_norm, ce::vecnorm_noise(noise), out,
+                                             out_step, pout, pout_step, &v);
+}
+
 int ce_multi_set_persistent(ce_multi_engine *e, int32_t on) { return ce::host_set_persistent(e, on); }
 
 const char *ce_multi_step_many_kernel(const ce_multi_engine *e) {

@@ -398,7 +398,7 @@ class OptimizeEngine:
         return fields, rec, pfields, prec
 
     def rollout_policy(self, k, policy, obs0, noise, fields, record_bytes, policy_fields,
-                       policy_record_bytes=None):
+                       policy_record_bytes=None, normalizer=None):
         """A K-step closed-loop rollout as ONE foreign call
         (``ce_rollout_policy``): for t < k, on the engine's stream, the policy
         (``custom_envs_amd.policy.MlpPolicy``) reads ``obs0`` (t = 0) or
@@ -409,7 +409,11 @@ class OptimizeEngine:
         ``rng.DeviceRng``: step t's noise is its draw ``t + step`` formed in the
         policy kernel (``ce_rollout_policy_rng``; the caller advances it).
         Needs the full output form.  Every tensor is validated first
-        (``policy.validate_rollout``)."""
+        (``policy.validate_rollout``).  ``normalizer``: a
+        ``vecnormalize.NormalizedRollout`` whose slot 0 is ``obs0``: a third
+        launch per step normalises record t's obs and reward into its slot
+        t + 1 and record t, and the policy reads the normalised slots
+        (``ce_rollout_policy_vecnorm``); ``fields`` stay raw."""
         from custom_envs_amd.policy import validate_rollout
         if self.compact:
             raise ValueError('rollout_policy needs the full output form (compact outputs are on)')
@@ -420,6 +424,12 @@ class OptimizeEngine:
         o = self._outputs(first)
         po = policy.outputs_struct({n: policy_fields[n][0] for n in
                                     ('action', 'env_action', 'neglogp', 'value')})
+        if normalizer is not None:
+            from custom_envs_amd.vectorize.vecnormalize import rollout_call
+            rollout_call(self._lib.ce_rollout_policy_vecnorm, 'ce_rollout_policy_vecnorm', self._h,
+                         policy, normalizer, k, self.num_envs, self.obs_dim, self.act_dim,
+                         self.device, noise, o, record_bytes, po, prec)
+            return
         if hasattr(noise, 'row_offset'):       # a DeviceRng (validated above)
             check(self._lib.ce_rollout_policy_rng(
                 self._h, policy._h, int(k), obs0.data_ptr(), noise.seed, int(noise.t),

@@ -123,10 +123,11 @@ class MultiOptEngine:
         return fields, rec, pfields, prec
 
     def rollout_policy(self, k, policy, obs0, noise, fields, record_bytes, policy_fields,
-                       policy_record_bytes=None):
+                       policy_record_bytes=None, normalizer=None):
         """K closed-loop steps as one foreign call (``ce_multi_rollout_policy``):
         the policy maps every (env, agent) row ``[3 max_history] -> [1]``; see
-        ``OptimizeEngine.rollout_policy``."""
+        ``OptimizeEngine.rollout_policy`` (``normalizer`` likewise:
+        ``ce_multi_rollout_policy_vecnorm``)."""
         from custom_envs_amd.policy import validate_rollout
         first, prec = validate_rollout(self.output_fields(), self.num_envs, self.rows,
                                        3 * self.max_history, 1, getattr(self, 'device', 0), k,
@@ -135,6 +136,12 @@ class MultiOptEngine:
         o = self._outputs(first)
         po = policy.outputs_struct({n: policy_fields[n][0] for n in
                                     ('action', 'env_action', 'neglogp', 'value')})
+        if normalizer is not None:
+            from custom_envs_amd.vectorize.vecnormalize import rollout_call
+            rollout_call(self._fn('rollout_policy_vecnorm'), self._prefix + 'rollout_policy_vecnorm',
+                         self._h, policy, normalizer, k, self.rows, 3 * self.max_history, 1,
+                         getattr(self, 'device', 0), noise, o, record_bytes, po, prec)
+            return
         if hasattr(noise, 'row_offset'):       # a DeviceRng (validated above)
             self._call('rollout_policy_rng', policy._h, int(k), obs0.data_ptr(), noise.seed,
                        int(noise.t), noise.row_offset, ctypes.byref(o), int(record_bytes),

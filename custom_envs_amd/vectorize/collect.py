@@ -18,13 +18,18 @@ for the single C call (README), so it has no C rollout entry.
 import numpy as np
 
 
-def run_collect(engine, policy, n_steps, last_obs, noise, rows):
+def run_collect(engine, policy, n_steps, last_obs, noise, rows, normalizer=None):
     """Returns (result dict of device tensors, env fields).  ``last_obs``:
     the observation the env last returned (numpy or a device tensor).
     ``noise``: ``[K][rows][A]`` N(0,1) device tensor, None to draw it here
     (one ``torch.randn``), False for the deterministic policy, or a
     ``rng.DeviceRng``: the policy kernel forms draws ``t .. t + K - 1`` itself
-    (no noise tensor exists) and the generator is advanced by K afterwards."""
+    (no noise tensor exists) and the generator is advanced by K afterwards.
+    ``normalizer``: a ``vecnormalize.VecNormalize``: a third launch per step
+    normalises the step's observation and reward, the policy reads the
+    normalised observations, and ``obs``, ``rewards``, ``last_obs`` and
+    ``last_values`` are the normalised ones (the raw ones are added as
+    ``original_obs`` and ``original_rewards``; the env fields stay raw)."""
     import torch
     from custom_envs_amd.rng import DeviceRng
     k = int(n_steps)
@@ -43,24 +48,42 @@ def run_collect(engine, policy, n_steps, last_obs, noise, rows):
     elif noise is False:
         noise = None
     fields, rec, pfields, prec = engine.alloc_policy_rollout(k, policy)
+    roll = None
+    if normalizer is not None:
+        vn = normalizer.normalizer
+        roll = vn.begin_rollout(k, normalizer.training)
+        raw0 = vn.original_obs
     # the tensors above were produced on torch's stream, the rollout runs on
     # the engine's: one synchronisation each way per K steps.  It stays with
     # generated noise too: the record buffers are zero-filled on torch's
     # stream, and their memory may be a block the learner's last update (on
     # torch's stream) still reads.
     torch.cuda.current_stream(dev).synchronize()
-    engine.rollout_policy(k, policy, obs0, noise, fields, rec, pfields, prec)
+    if roll is None:
+        engine.rollout_policy(k, policy, obs0, noise, fields, rec, pfields, prec)
+    else:
+        engine.rollout_policy(k, policy, roll.obs[0], noise, fields, rec, pfields, prec,
+                              normalizer=roll)
     engine.wait()
     if generated:
         noise.advance(k)
-    last = policy.forward_device(fields['obs'][k - 1])
+    if roll is None:
+        obs, rewards, last_obs = (torch.cat([obs0[None], fields['obs'][:k - 1]], dim=0),
+                                  fields['reward'], fields['obs'][k - 1])
+    else:
+        obs, rewards, last_obs = roll.obs[:k].contiguous(), roll.rewards, roll.obs[k]
+    last = policy.forward_device(last_obs)
     result = {
-        'obs': torch.cat([obs0[None], fields['obs'][:k - 1]], dim=0),
+        'obs': obs,
         'actions': pfields['action'], 'env_actions': pfields['env_action'],
         'values': pfields['value'], 'neglogps': pfields['neglogp'],
-        'rewards': fields['reward'], 'dones': fields['done'],
-        'last_obs': fields['obs'][k - 1], 'last_values': last['value'],
+        'rewards': rewards, 'dones': fields['done'],
+        'last_obs': last_obs, 'last_values': last['value'],
     }
+    if roll is not None:
+        result['original_obs'] = torch.cat([raw0[None], fields['obs'][:k - 1]], dim=0)
+        result['original_rewards'] = fields['reward']
+        vn.end_rollout(roll, fields['obs'][k - 1], fields['reward'][k - 1])
     for name, value in fields.items():
         if name not in ('obs', 'reward', 'done', '_buffer'):
             result[name] = value

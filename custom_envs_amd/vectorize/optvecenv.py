@@ -248,12 +248,13 @@ class OptVecEnv:
         groups = self._host._broadcast('reset', None)
         return np.stack([o for group in groups for o in group])
 
-    def collect(self, policy, n_steps, noise=None):
+    def collect(self, policy, n_steps, noise=None, normalizer=None):
         """``n_steps`` closed-loop steps on the device as one engine call
         (``MultiOptEngine.rollout_policy``), one policy row per (env, agent)
         row, starting from the observation last returned; see
         ``GPUVecEnv.collect`` (``noise`` likewise: a tensor, None, False or a
-        ``rng.DeviceRng``).  Returns device tensors ``obs [K][rows][3H]``,
+        ``rng.DeviceRng``; ``normalizer`` likewise: the ``VecNormalize`` wrapped
+        around this env).  Returns device tensors ``obs [K][rows][3H]``,
         ``actions``, ``env_actions``, ``values``, ``neglogps``, ``rewards``,
         ``dones``, ``last_obs``, ``last_values``, ``info [K][E][14]`` and
         ``episode_len``.  An attached monitor sees the K records in order
@@ -266,8 +267,8 @@ class OptVecEnv:
         if self.monitor is not None:
             self.monitor.check_step()
         result, fields = run_collect(self._engine, policy, n_steps, self._last_obs, noise,
-                                     self._engine.rows)
-        self._last_obs = result['last_obs']
+                                     self._engine.rows, normalizer)
+        self._last_obs = fields['obs'][int(n_steps) - 1]     # the raw one
         if self._device_monitor:
             self.monitor.scan(fields, int(n_steps))
         elif self.monitor is not None:

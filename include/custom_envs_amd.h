@@ -934,6 +934,110 @@ int ce_monitor_set_state(ce_monitor *m, const double *ep_reward, const int32_t *
 int ce_explained_variance(int32_t k, int64_t rows, const float *values, int64_t value_stride_bytes,
                           const float *returns, double *out, void *hip_stream);
 
+/* stable-baselines' VecNormalize on the device (custom_envs_amd/vectorize/
+ * vecnormalize.py states it in NumPy as vecnormalize_numpy).  The state -- the
+ * float64 running mean, variance and count of every observation column and of
+ * the discounted returns, and the per-row return `ret` -- lives on the device
+ * between calls.  One step is ONE launch (csrc/vecnorm_kernels.h): the moments
+ * are merged with the batch first, then obs and reward are scaled with the
+ * updated moments, clipped and stored as float32.  Every sum runs in a fixed
+ * order without atomics: the same inputs give the same bits.  Rows are the
+ * engine's rows (envs x agents); the moments run per column over all rows. */
+typedef struct ce_vecnorm ce_vecnorm;
+
+typedef struct ce_vecnorm_config {
+    int32_t abi_version; /* CE_ABI_VERSION                                   */
+    int32_t device;      /* HIP device ordinal                               */
+    int64_t rows;        /* in [1, 2^24]                                     */
+    int32_t obs_dim;     /* in [1, 2^16]                                     */
+    int32_t norm_obs;    /* 0: obs_out is obs unchanged                      */
+    int32_t norm_reward; /* 0: reward_out is reward unchanged                */
+    int32_t reserved;    /* 0                                                */
+    double clip_obs;     /* > 0 (SB: 10)                                     */
+    double clip_reward;  /* > 0 (SB: 10)                                     */
+    double gamma;        /* finite (SB: 0.99)                                */
+    double epsilon;      /* >= 0 (SB: 1e-8)                                  */
+} ce_vecnorm_config;
+
+enum ce_vecnorm_flags {
+    CE_VECNORM_TRAINING = 1u << 0, /* merge this batch into the moments      */
+    CE_VECNORM_RESET = 1u << 1,    /* VecNormalize.reset: ret = 0, the obs moments
+                                      updated, no reward; reward, done and
+                                      reward_out may be NULL                 */
+    CE_VECNORM_OBS_ONLY = 1u << 2  /* obs_out only, with the moments as they are:
+                                      nothing of the state changes (not with
+                                      TRAINING or RESET); reward, done and
+                                      reward_out may be NULL                 */
+};
+
+/* The state starts at mean 0, variance 1, count 1e-4, ret 0.  The checks of
+ * cfg precede the first HIP call. */
+int ce_vecnorm_create(const ce_vecnorm_config *cfg, ce_vecnorm **out);
+void ce_vecnorm_destroy(ce_vecnorm *vn);
+/* One stream-ordered launch (device pointers; obs and obs_out [rows][obs_dim]
+ * float32, reward and reward_out [rows] float32, done [rows] bytes):
+ *   if TRAINING and norm_obs:    obs moments = update(obs moments, obs)
+ *   obs_out = clip((obs - mean) / sqrt(var + epsilon), +-clip_obs)
+ *   ret = ret * gamma + reward
+ *   if TRAINING and norm_reward: ret moments = update(ret moments, ret)
+ *   reward_out = clip(reward / sqrt(ret var + epsilon), +-clip_reward)
+ *   ret[done] = 0
+ * The quotients are formed as products with 1 / sqrt(.), one rounding away
+ * from the statement's in float64.  The checks of the pointers and flags
+ * precede the check of the handle; all precede the first HIP call. */
+int ce_vecnorm_step(ce_vecnorm *vn, const float *obs, const float *reward, const uint8_t *done,
+                    float *obs_out, float *reward_out, uint32_t flags, void *hip_stream);
+/* The state to / from host arrays: obs_mean, obs_var [obs_dim], ret [rows],
+ * the others one double each; synchronises. */
+int ce_vecnorm_get_state(ce_vecnorm *vn, double *obs_mean, double *obs_var, double *obs_count,
+                         double *ret_mean, double *ret_var, double *ret_count, double *ret,
+                         void *hip_stream);
+int ce_vecnorm_set_state(ce_vecnorm *vn, const double *obs_mean, const double *obs_var,
+                         const double *obs_count, const double *ret_mean, const double *ret_var,
+                         const double *ret_count, const double *ret, void *hip_stream);
+
+/* Where a rollout's N(0,1) noise comes from. */
+enum ce_noise_kind {
+    CE_NOISE_BLOCK = 0,    /* ptr [k][rows][A], `stride` elements apart; NULL:
+                              the deterministic policy                       */
+    CE_NOISE_GENERATED = 1 /* formed in the policy kernel: seed, draw t0 + s,
+                              global rows row0 ..                            */
+};
+typedef struct ce_rollout_noise {
+    int32_t kind;     /* ce_noise_kind                                       */
+    int32_t reserved; /* 0                                                   */
+    const float *ptr;
+    int64_t stride;
+    uint64_t seed;
+    uint32_t t0, row0;
+} ce_rollout_noise;
+
+/* ce_rollout_policy / ce_multi_rollout_policy with a third launch per step:
+ * for s = 0..k-1, on the engine's stream, (1) the policy reads normalised slot
+ * s of obs_norm ([k + 1] slots of [rows][D], obs_norm_step_bytes apart; slot 0
+ * is the caller's, already normalised) and writes policy record s; (2) the env
+ * steps into raw record s of `out`; (3) the normaliser (ce_vecnorm_step with
+ * vn_flags, TRAINING or 0) reads that record's obs, reward and done and writes
+ * normalised slot s + 1 and normalised reward record s ([k] records of [rows],
+ * reward_norm_step_bytes apart).  The raw records stay intact.  Bit-equal to
+ * the same three calls issued one by one.  Checks, in this order and all before
+ * the first HIP call: null pointers (the engine's first); k, the noise kind,
+ * vn_flags, alignment (obs_norm and both step bytes multiples of 16); then what
+ * ce_rollout_policy checks; then the normaliser's rows and obs_dim against the
+ * engine's and the step bytes against rows * D * 4 and rows * 4. */
+int ce_rollout_policy_vecnorm(ce_engine *eng, const ce_policy *p, ce_vecnorm *vn, int32_t k,
+                              float *obs_norm, int64_t obs_norm_step_bytes, float *reward_norm,
+                              int64_t reward_norm_step_bytes, uint32_t vn_flags,
+                              const ce_rollout_noise *noise, const ce_outputs *out,
+                              int64_t out_step_bytes, const ce_policy_outputs *pout,
+                              int64_t pout_step_bytes);
+int ce_multi_rollout_policy_vecnorm(ce_multi_engine *eng, const ce_policy *p, ce_vecnorm *vn,
+                                    int32_t k, float *obs_norm, int64_t obs_norm_step_bytes,
+                                    float *reward_norm, int64_t reward_norm_step_bytes,
+                                    uint32_t vn_flags, const ce_rollout_noise *noise,
+                                    const ce_multi_outputs *out, int64_t out_step_bytes,
+                                    const ce_policy_outputs *pout, int64_t pout_step_bytes);
+
 #ifdef __cplusplus
 }
 #endif
