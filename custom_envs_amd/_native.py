@@ -65,6 +65,7 @@ EXPORTS = (
     'ce_explained_variance',
     'ce_vecnorm_create', 'ce_vecnorm_destroy', 'ce_vecnorm_step', 'ce_vecnorm_get_state',
     'ce_vecnorm_set_state', 'ce_rollout_policy_vecnorm', 'ce_multi_rollout_policy_vecnorm',
+    'ce_policy_wide_n_params', 'ce_policy_create_wide', 'ce_rng_normal_wide',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -259,6 +260,9 @@ def _declare(lib):
         'ce_nn_get_state': ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_policy_n_params': ([ctypes.POINTER(CePolicyConfig)], ctypes.c_int),
         'ce_policy_create': ([ctypes.POINTER(CePolicyConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_policy_wide_n_params': ([ctypes.POINTER(CePolicyConfig)], ctypes.c_int),
+        'ce_policy_create_wide': ([ctypes.POINTER(CePolicyConfig), ctypes.POINTER(vp)],
+                                  ctypes.c_int),
         'ce_policy_destroy': ([vp], None),
         'ce_policy_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
         'ce_policy_set_bounds': ([vp, vp, vp], ctypes.c_int),
@@ -305,6 +309,7 @@ def _declare(lib):
         'ce_ddpg_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp],
                          ctypes.c_int),
         'ce_rng_normal': ([vp, i32, i64, i32, i64, u64, u32, u32, vp], ctypes.c_int),
+        'ce_rng_normal_wide': ([vp, i32, i64, i32, i64, u64, u32, u32, vp], ctypes.c_int),
         'ce_rng_u32': ([vp, i64, u64, u32, u32, vp], ctypes.c_int),
         'ce_policy_forward_rng': ([vp, vp, u64, u32, u32, i64, ctypes.POINTER(CePolicyOutputs), vp],
                                   ctypes.c_int),

@@ -54,6 +54,13 @@ int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
     c.policy = policy;
     c.plan = policy_plan(policy);
     const PolicyPlan &pa = c.plan;
+    // the gradient kernel holds a whole [in_pad][out_pad + 1] layer in LDS: a
+    // wide handle (ce_policy_create_wide) acts, it is not trained here
+    if (pa.wide)
+        return bail(fail(CE_EUNSUPPORTED,
+                         "the learners take obs_dim <= 128, act_dim <= 64: a policy from "
+                         "ce_policy_create_wide (obs_dim " + std::to_string(pa.D) + ", act_dim " +
+                             std::to_string(pa.A) + ") acts and rolls out only"));
     int wmax = 0, kmax = 0;
     for (int net = 0; net < 2; ++net)
         for (int i = 0; i <= pa.n_hidden; ++i) {

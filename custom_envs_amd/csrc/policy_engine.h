@@ -46,7 +46,8 @@ struct PolicyNoise {
     }
 };
 
-// Enqueue one policy_mlp_kernel launch (the instance `noise` selects): every
+// Enqueue one policy_mlp_kernel launch -- policy_wide_kernel for a handle from
+// ce_policy_create_wide, at every shape -- (the instance `noise` selects): every
 // pointer a device pointer, all four outputs set, rows >= 1.  Arguments are
 // NOT validated here.
 void policy_launch(const ce_policy *p, const float *obs, const PolicyNoise &noise, int64_t rows,
@@ -86,6 +87,7 @@ struct PolicyPlan {
     int n_segs;                                 // logstd is the last segment
     int seg_dst[kPlanSegs], seg_src[kPlanSegs], seg_cols[kPlanSegs], seg_cols_pad[kPlanSegs];
     int n_params, img_floats, device;
+    int wide;                                   // from ce_policy_create_wide: the learners refuse it
     float *img;
 };
 PolicyPlan policy_plan(const ce_policy *p);

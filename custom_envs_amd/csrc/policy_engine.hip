@@ -14,6 +14,7 @@
 #include "common.h"
 #include "policy_engine.h"
 #include "policy_kernels.h"
+#include "policy_wide_kernels.h"
 #include "rng_kernels.h"
 
 struct ce_policy {
@@ -22,6 +23,7 @@ struct ce_policy {
     ce::PolicyPack pack{};
     int n_params = 0, img_floats = 0;
     size_t lds_bytes = 0;
+    bool wide = false;           // created by ce_policy_create_wide: policy_wide_kernel
     float *img = nullptr;        // the padded parameter image + logstd, low, high
     float *d_flat = nullptr;     // staging of a host-pointer set_params
 };
@@ -32,8 +34,11 @@ using ce::fail;
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// shape limits (no HIP call); `who` prefixes the message
-int shape_ok(const char *who, const ce_policy_config *cfg) {
+// shape limits (no HIP call); `who` prefixes the message; `wide`: the limits
+// of policy_wide_kernel (policy_wide_kernels.h)
+int shape_ok(const char *who, const ce_policy_config *cfg, bool wide = false) {
+    const int max_d = wide ? ce::kPolWideMaxD : ce::kPolMaxD;
+    const int max_a = wide ? ce::kPolWideMaxA : ce::kPolMaxA;
     const std::string w(who);
     if (!cfg) return fail(CE_EINVAL, w + ": null config");
     if (cfg->abi_version != CE_ABI_VERSION) return fail(CE_EINVAL, w + ": ABI version mismatch");
@@ -42,12 +47,12 @@ int shape_ok(const char *who, const ce_policy_config *cfg) {
     if (cfg->n_hidden > ce::kPolMaxHidden)
         return fail(CE_EUNSUPPORTED, w + ": the policy takes 1 to 3 hidden layers, got " +
                                          std::to_string(cfg->n_hidden));
-    if (cfg->obs_dim > ce::kPolMaxD)
+    if (cfg->obs_dim > max_d)
         return fail(CE_EUNSUPPORTED, w + ": obs_dim " + std::to_string(cfg->obs_dim) +
-                                         " exceeds the limit of 128");
-    if (cfg->act_dim > ce::kPolMaxA)
+                                         " exceeds the limit of " + std::to_string(max_d));
+    if (cfg->act_dim > max_a)
         return fail(CE_EUNSUPPORTED, w + ": act_dim " + std::to_string(cfg->act_dim) +
-                                         " exceeds the limit of 64");
+                                         " exceeds the limit of " + std::to_string(max_a));
     for (int l = 0; l < cfg->n_hidden; ++l) {
         const int h = cfg->hidden[l];
         if (h <= 0) return fail(CE_EINVAL, w + ": hidden widths must be positive");
@@ -102,8 +107,10 @@ void plan(ce_policy *p) {
             a.out_pad[net][l] = op;
             a.off_w[net][l] = add(in, out, ip, op);
             a.off_b[net][l] = add(1, out, 1, op);
-            wmax = std::max(wmax, ip * op);
-            kmax = std::max(kmax, ip);
+            // one stage holds at most a 128 x 128 chunk (a wide handle's first
+            // layer and head: policy_wide_kernels.h)
+            wmax = std::max(wmax, std::min(ip, ce::kPolChunk) * std::min(op, ce::kPolChunk));
+            kmax = std::max(kmax, std::min(ip, ce::kPolChunk));
             in = out;
         }
     }
@@ -123,6 +130,57 @@ void plan(ce_policy *p) {
 // the generated instance's noise tile: 32 rows x round4(A) floats
 size_t gen_lds_bytes(int act_dim) {
     return static_cast<size_t>(ce::kPolTile) * round_up(act_dim, 4) * sizeof(float);
+}
+
+// the wide generated instance's: one head chunk of it
+size_t gen_wide_lds_bytes(int act_dim) {
+    return gen_lds_bytes(std::min(act_dim, ce::kPolChunk));
+}
+
+// what both creates do after the shape check
+int create(const char *who, const ce_policy_config *cfg, bool wide, ce_policy **out) {
+    const std::string w(who);
+    ce_policy *p = new (std::nothrow) ce_policy();
+    if (!p) return fail(CE_ENOMEM, w + ": host allocation failed");
+    p->cfg = *cfg;
+    p->wide = wide;
+    plan(p);
+    auto bail = [&](int code) {
+        ce_policy_destroy(p);
+        return code;
+    };
+    CE_TRY(hipSetDevice(cfg->device));
+    // the limits' need; the same for both kernels: a 128 x 128 stage and two
+    // 128-wide activation buffers
+    const size_t max_lds = (ce::kPolMaxWidth * ce::kPolMaxWidth +
+                            2 * ce::kPolMaxWidth * ce::kPolLd) * sizeof(float);
+    if (wide) {
+        CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_wide_kernel<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(max_lds)));
+        CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_wide_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(max_lds + gen_wide_lds_bytes(ce::kPolWideMaxA))));
+    } else {
+        CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(max_lds)));
+        CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(max_lds + gen_lds_bytes(ce::kPolMaxA))));
+    }
+    CE_TRY(hipMalloc(&p->img, p->img_floats * sizeof(float)));
+    CE_TRY(hipMalloc(&p->d_flat, p->n_params * sizeof(float)));
+    // zero parameters, unbounded actions
+    std::vector<float> init(p->img_floats, 0.0f);
+    for (int c = 0; c < cfg->act_dim; ++c) {
+        init[p->args.off_low + c] = -INFINITY;
+        init[p->args.off_high + c] = INFINITY;
+    }
+    CE_TRY(hipMemcpy(p->img, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->args.img = p->img;
+    *out = p;
+    return CE_OK;
 }
 
 bool complete(const ce_policy_outputs *o) {
@@ -164,6 +222,7 @@ PolicyPlan policy_plan(const ce_policy *p) {
     q.n_params = p->n_params;
     q.img_floats = p->img_floats;
     q.device = p->cfg.device;
+    q.wide = p->wide ? 1 : 0;
     q.img = p->img;
     return q;
 }
@@ -188,6 +247,15 @@ void policy_launch(const ce_policy *p, const float *obs, const PolicyNoise &nois
     a.neglogp = out.neglogp;
     a.value = out.value;
     const dim3 grid(static_cast<unsigned>((rows + kPolTile - 1) / kPolTile), 2);
+    if (p->wide) {
+        if (noise.generated)
+            hipLaunchKernelGGL(policy_wide_kernel<true>, grid, dim3(kPolBlock),
+                               p->lds_bytes + gen_wide_lds_bytes(a.A), stream, a);
+        else
+            hipLaunchKernelGGL(policy_wide_kernel<false>, grid, dim3(kPolBlock), p->lds_bytes,
+                               stream, a);
+        return;
+    }
     if (noise.generated)
         hipLaunchKernelGGL(policy_mlp_kernel<true>, grid, dim3(kPolBlock),
                            p->lds_bytes + gen_lds_bytes(a.A), stream, a);
@@ -272,35 +340,20 @@ int ce_policy_create(const ce_policy_config *cfg, ce_policy **out) {
     *out = nullptr;
     int rc = shape_ok("ce_policy_create", cfg);
     if (rc != CE_OK) return rc;
-    ce_policy *p = new (std::nothrow) ce_policy();
-    if (!p) return fail(CE_ENOMEM, "ce_policy_create: host allocation failed");
-    p->cfg = *cfg;
-    plan(p);
-    auto bail = [&](int code) {
-        ce_policy_destroy(p);
-        return code;
-    };
-    CE_TRY(hipSetDevice(cfg->device));
-    const size_t max_lds = (ce::kPolMaxWidth * ce::kPolMaxWidth +
-                            2 * ce::kPolMaxWidth * ce::kPolLd) * sizeof(float);
-    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(max_lds)));
-    CE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ce::policy_mlp_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(max_lds + gen_lds_bytes(ce::kPolMaxA))));
-    CE_TRY(hipMalloc(&p->img, p->img_floats * sizeof(float)));
-    CE_TRY(hipMalloc(&p->d_flat, p->n_params * sizeof(float)));
-    // zero parameters, unbounded actions
-    std::vector<float> init(p->img_floats, 0.0f);
-    for (int c = 0; c < cfg->act_dim; ++c) {
-        init[p->args.off_low + c] = -INFINITY;
-        init[p->args.off_high + c] = INFINITY;
-    }
-    CE_TRY(hipMemcpy(p->img, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
-    p->args.img = p->img;
-    *out = p;
-    return CE_OK;
+    return create("ce_policy_create", cfg, false, out);
+}
+
+int ce_policy_wide_n_params(const ce_policy_config *cfg) {
+    const int rc = shape_ok("ce_policy_wide_n_params", cfg, true);
+    return rc != CE_OK ? rc : count_params(cfg);
+}
+
+int ce_policy_create_wide(const ce_policy_config *cfg, ce_policy **out) {
+    if (!cfg || !out) return fail(CE_EINVAL, "ce_policy_create_wide: null argument");
+    *out = nullptr;
+    const int rc = shape_ok("ce_policy_create_wide", cfg, true);
+    if (rc != CE_OK) return rc;
+    return create("ce_policy_create_wide", cfg, true, out);
 }
 
 void ce_policy_destroy(ce_policy *p) {
@@ -379,14 +432,15 @@ int ce_policy_forward_rng(const ce_policy *p, const float *obs, uint64_t seed, u
 // ce_rng_normal_purpose
 static int rng_normal_entry(const char *who, float *out, int32_t k, int64_t rows, int32_t act_dim,
                             int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
-                            int64_t purpose, void *hip_stream) {
+                            int64_t purpose, void *hip_stream, int max_act = ce::kPolMaxA) {
     const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
     if (!out) return bad(": null output");
     if (k < 1) return bad(": k must be at least 1, got " + std::to_string(k));
     if (rows < 1 || rows > (int64_t(1) << 24))
         return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
-    if (act_dim < 1 || act_dim > ce::kPolMaxA)
-        return bad(": act_dim must be in [1, 64], got " + std::to_string(act_dim));
+    if (act_dim < 1 || act_dim > max_act)
+        return bad(": act_dim must be in [1, " + std::to_string(max_act) + "], got " +
+                   std::to_string(act_dim));
     if (record_stride_bytes % 4 != 0 || record_stride_bytes < rows * act_dim * 4)
         return bad(": record_stride_bytes must be a multiple of 4 of at least rows * act_dim * 4");
     if (reinterpret_cast<uintptr_t>(out) & 3) return bad(": the output must be 4-byte aligned");
@@ -417,6 +471,13 @@ int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
                   void *hip_stream) {
     return rng_normal_entry("ce_rng_normal", out, k, rows, act_dim, record_stride_bytes, seed, t0,
                             row0, -1, hip_stream);
+}
+
+int ce_rng_normal_wide(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                       int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                       void *hip_stream) {
+    return rng_normal_entry("ce_rng_normal_wide", out, k, rows, act_dim, record_stride_bytes, seed,
+                            t0, row0, -1, hip_stream, ce::kPolWideMaxA);
 }
 
 int ce_rng_normal_purpose(float *out, int32_t k, int64_t rows, int32_t act_dim,

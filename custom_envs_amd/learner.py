@@ -23,7 +23,8 @@ import numpy as np
 
 from custom_envs_amd import _native
 from custom_envs_amd._native import check
-from custom_envs_amd.policy import LOG_2PI, MlpPolicy, dict_to_flat, flat_to_dict, params_layout
+from custom_envs_amd.policy import (LOG_2PI, MlpPolicy, WideMlpPolicy, dict_to_flat, flat_to_dict,
+                                    params_layout)
 
 N_STATS = 8          # a learner's named statistics first, ||grad||^2 at GRAD_SQ, one spare
 GRAD_SQ = 6          # where ||grad||^2 sits
@@ -177,6 +178,11 @@ class Learner:
     def __init__(self, policy, **cfg):
         if not isinstance(policy, MlpPolicy):
             raise TypeError('policy must be an MlpPolicy')
+        if isinstance(policy, WideMlpPolicy):      # what ce_<x>_create answers, without the call
+            raise _native.NativeEngineError(
+                '%s_create: the learners take obs_dim <= 128, act_dim <= 64: a WideMlpPolicy '
+                '(obs_dim %d, act_dim %d) acts and rolls out only (CE_EUNSUPPORTED)'
+                % (self.PREFIX, policy.obs_dim, policy.act_dim))
         self.policy = policy
         self.device = policy.device
         self.n_params = policy.n_params

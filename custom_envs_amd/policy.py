@@ -27,9 +27,12 @@ with which the kernel forms its noise itself from the counter-based generator
 tensor written or read.
 
 Limits: 1-3 hidden layers, each width a multiple of 32 up to 128, obs_dim <=
-128, act_dim <= 64.  The reference's default 7x7-image Optimize observation
-(981 wide) is out of scope.  Anything else raises ``NativeEngineError``
-(CE_EUNSUPPORTED); there is no eager fallback.
+128, act_dim <= 64.  Anything else raises ``NativeEngineError``
+(CE_EUNSUPPORTED); there is no eager fallback.  The reference's default
+7x7-image Optimize shape (981 wide, 490 actions) takes ``WideMlpPolicy``
+(obs_dim <= 1024, act_dim <= 512; csrc/policy_wide_kernels.h): the act side --
+forwards, rollouts, ``collect``, ``VecNormalize`` -- with the same interface;
+the learners refuse it.
 """
 import ctypes
 from collections import OrderedDict
@@ -148,6 +151,9 @@ class MlpPolicy:
     """The actor-critic MLP on one GPU (see the module docstring).
     ``device=None`` builds the shape only -- ``params_layout``,
     ``forward_numpy`` and the argument checks, which need no GPU."""
+    # the two C functions a policy is created through
+    N_PARAMS_FN = 'ce_policy_n_params'
+    CREATE_FN = 'ce_policy_create'
 
     def __init__(self, obs_dim, act_dim, hidden=(64, 64), low=None, high=None, device=0):
         lib = _native.load()
@@ -161,16 +167,16 @@ class MlpPolicy:
                                          n_hidden=len(self.hidden))
         for i, h in enumerate(self.hidden):
             cfg.hidden[i] = h
-        n = lib.ce_policy_n_params(ctypes.byref(cfg))
+        n = getattr(lib, self.N_PARAMS_FN)(ctypes.byref(cfg))
         if n < 0:
-            check(n, 'ce_policy_n_params')
+            check(n, self.N_PARAMS_FN)
         self.n_params = int(n)
         self._lib, self._h = lib, None
         self.low, self.high = _bounds(low, self.act_dim), _bounds(high, self.act_dim)
         if device is None:      # shape only: layout, forward_numpy and validation, no GPU
             return
         handle = ctypes.c_void_p()
-        check(lib.ce_policy_create(ctypes.byref(cfg), ctypes.byref(handle)), 'ce_policy_create')
+        check(getattr(lib, self.CREATE_FN)(ctypes.byref(cfg), ctypes.byref(handle)), self.CREATE_FN)
         self._h = handle
         if low is not None or high is not None:
             check(lib.ce_policy_set_bounds(
@@ -345,6 +351,17 @@ class MlpPolicy:
             self.close()
         except Exception:
             pass
+
+
+class WideMlpPolicy(MlpPolicy):
+    """``MlpPolicy`` for obs_dim <= 1024 and act_dim <= 512 (hidden layers as
+    there): the reference's default ``Optimize-v0`` shape, 981 -> 490.  The
+    same interface, parameter vector and semantics, run by the wide kernel
+    (csrc/policy_wide_kernels.h), which at a shape ``MlpPolicy`` takes too
+    writes the same bits.  Act side only: ``PPO2Learner`` / ``A2CLearner``
+    raise ``NativeEngineError`` for it."""
+    N_PARAMS_FN = 'ce_policy_wide_n_params'
+    CREATE_FN = 'ce_policy_create_wide'
 
 
 def check_rng(rng, device, k, rows):

@@ -243,8 +243,10 @@ class DeviceRng:
         generator's own."""
         import torch
         k, rows, act_dim = int(k), int(rows), int(act_dim)
-        if k < 1 or rows < 1 or not 1 <= act_dim <= 64:
-            raise ValueError('k and rows must be >= 1 and act_dim in [1, 64]')
+        wide = int(purpose) == POLICY and act_dim > 64      # a WideMlpPolicy's noise
+        if k < 1 or rows < 1 or not 1 <= act_dim <= (512 if int(purpose) == POLICY else 64):
+            raise ValueError('k and rows must be >= 1 and act_dim in [1, 64] (the policy noise: '
+                             '[1, 512])')
         t = int(self.t) if t is None else int(t)
         row_offset = self.row_offset if row_offset is None else int(row_offset)
         _check_draws(t, k)
@@ -252,7 +254,11 @@ class DeviceRng:
         out = torch.empty((k, rows, act_dim), dtype=torch.float32, device=dev)
         lib = _native.load()
         with torch.cuda.device(dev):
-            if int(purpose) == POLICY:
+            if wide:
+                check(lib.ce_rng_normal_wide(out.data_ptr(), k, rows, act_dim, rows * act_dim * 4,
+                                             self.seed, t, row_offset, self._stream(stream)),
+                      'ce_rng_normal_wide')
+            elif int(purpose) == POLICY:
                 check(lib.ce_rng_normal(out.data_ptr(), k, rows, act_dim, rows * act_dim * 4,
                                         self.seed, t, row_offset, self._stream(stream)),
                       'ce_rng_normal')

@@ -72,6 +72,9 @@
  * it, run_multiagent_exp_single.py:37-49):
  *   ce_policy_create / _destroy / _n_params / _set_params / _set_bounds
  *                    the actor-critic network, its flat parameters and bounds
+ *   ce_policy_create_wide / ce_policy_wide_n_params
+ *                    the same handle for obs_dim <= 1024, act_dim <= 512 (the
+ *                    reference's 981 -> 490 default shape); act side only
  *   ce_policy_forward  one fused launch: action, env_action, neglogp, value
  *   ce_rollout_policy / ce_multi_rollout_policy
  *                    K x (policy forward, VecEnv.step) from one call, the
@@ -402,8 +405,10 @@ int ce_nn_get_state(ce_nn_engine *eng, float *theta, float *gprev, int32_t *step
  *   neglogp = 0.5 sum noise^2 + sum logstd + 0.5 A log(2 pi)   (from the noise
  *             itself, not from (action - mean) / std; sum noise^2 = 0 for NULL)
  * Limits: 1..3 hidden layers, each width a multiple of 32 up to 128,
- * obs_dim <= 128, act_dim <= 64; anything else is CE_EUNSUPPORTED (the
- * reference's default 7x7-image Optimize shape, obs_dim 981, is out of scope).
+ * obs_dim <= 128, act_dim <= 64; anything else is CE_EUNSUPPORTED.  The
+ * reference's default 7x7-image Optimize shape (obs_dim 981, act_dim 490) is
+ * served on the act side by a wide handle, ce_policy_create_wide below
+ * (obs_dim <= 1024, act_dim <= 512); the learners refuse it.
  * Every argument check of every ce_policy_* / ce_*rollout_policy call happens
  * before its first HIP call.
  */
@@ -412,8 +417,8 @@ typedef struct ce_policy ce_policy;
 typedef struct ce_policy_config {
     int32_t abi_version; /* CE_ABI_VERSION                                   */
     int32_t device;      /* HIP device ordinal                               */
-    int32_t obs_dim;     /* D <= 128                                         */
-    int32_t act_dim;     /* A <= 64                                          */
+    int32_t obs_dim;     /* D <= 128  (ce_policy_create_wide: <= 1024)       */
+    int32_t act_dim;     /* A <= 64   (ce_policy_create_wide: <= 512)        */
     int32_t n_hidden;    /* hidden layers per network, 1..3                  */
     int32_t hidden[4];   /* their widths (multiples of 32, <= 128)           */
 } ce_policy_config;
@@ -432,6 +437,18 @@ typedef struct ce_policy_outputs {
  * (kernels row-major [in][out]), or a negative ce_status.  No GPU. */
 int ce_policy_n_params(const ce_policy_config *cfg);
 int ce_policy_create(const ce_policy_config *cfg, ce_policy **out);
+/* The wide policy: the same config, parameter vector, semantics and handle
+ * type with obs_dim <= 1024 and act_dim <= 512 (hidden layers as above), run
+ * by policy_wide_kernel (policy_wide_kernels.h: the first layer in K-chunks
+ * of 128 observation columns, the head in N-chunks of 128 actions).  A wide
+ * handle always launches that kernel; at a shape ce_policy_create takes too
+ * it writes the same bits.  Every entry that takes a ce_policy takes a wide
+ * one -- set_params, set_bounds, forward, forward_rng, the rollouts and their
+ * _rng / _vecnorm forms -- except the learners: ce_ppo2_create and
+ * ce_a2c_create answer CE_EUNSUPPORTED before any allocation (they take
+ * obs_dim <= 128, act_dim <= 64). */
+int ce_policy_wide_n_params(const ce_policy_config *cfg);
+int ce_policy_create_wide(const ce_policy_config *cfg, ce_policy **out);
 void ce_policy_destroy(ce_policy *p);
 /* n must equal ce_policy_n_params.  Host pointer: synchronises before
  * returning.  CE_PTR_DEVICE: `flat` is a device pointer and the refresh is
@@ -487,6 +504,10 @@ int ce_rng_normal(float *out, int32_t k, int64_t rows, int32_t act_dim,
                   void *hip_stream);
 int ce_rng_u32(uint32_t *out, int64_t n, uint64_t seed, uint32_t purpose, uint32_t t,
                void *hip_stream);
+/* ce_rng_normal for a wide policy's noise: act_dim in [1, 512]. */
+int ce_rng_normal_wide(float *out, int32_t k, int64_t rows, int32_t act_dim,
+                       int64_t record_stride_bytes, uint64_t seed, uint32_t t0, uint32_t row0,
+                       void *hip_stream);
 /* ce_rng_normal under the caller's purpose tag (3: DDPG's action noise). */
 int ce_rng_normal_purpose(float *out, int32_t k, int64_t rows, int32_t act_dim,
                           int64_t record_stride_bytes, uint64_t seed, uint32_t purpose, uint32_t t0,
