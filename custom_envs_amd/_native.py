@@ -66,6 +66,7 @@ EXPORTS = (
     'ce_vecnorm_create', 'ce_vecnorm_destroy', 'ce_vecnorm_step', 'ce_vecnorm_get_state',
     'ce_vecnorm_set_state', 'ce_rollout_policy_vecnorm', 'ce_multi_rollout_policy_vecnorm',
     'ce_policy_wide_n_params', 'ce_policy_create_wide', 'ce_rng_normal_wide',
+    'ce_ppo2_create_wide', 'ce_a2c_create_wide',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -272,6 +273,8 @@ def _declare(lib):
         'ce_multi_rollout_policy': ([vp, vp, i32, vp, vp, i64, ctypes.POINTER(CeMultiOutputs), i64,
                                      ctypes.POINTER(CePolicyOutputs), i64], ctypes.c_int),
         'ce_ppo2_create': ([vp, ctypes.POINTER(CePpo2Config), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_ppo2_create_wide': ([vp, ctypes.POINTER(CePpo2Config), ctypes.POINTER(vp)],
+                                ctypes.c_int),
         'ce_ppo2_destroy': ([vp], None),
         'ce_ppo2_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
         'ce_ppo2_get_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
@@ -279,6 +282,8 @@ def _declare(lib):
         'ce_ppo2_grad': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp], ctypes.c_int),
         'ce_ppo2_step': ([vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp], ctypes.c_int),
         'ce_a2c_create': ([vp, ctypes.POINTER(CeA2cConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        'ce_a2c_create_wide': ([vp, ctypes.POINTER(CeA2cConfig), ctypes.POINTER(vp)],
+                               ctypes.c_int),
         'ce_a2c_destroy': ([vp], None),
         'ce_a2c_set_params': ([vp, vp, i64, u32, vp], ctypes.c_int),
         'ce_a2c_get_params': ([vp, vp, i64, u32, vp], ctypes.c_int),

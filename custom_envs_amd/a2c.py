@@ -314,3 +314,13 @@ class A2CLearner(Learner):
             self._stream(stream))
         self.policy._host_params = None
         return Stats(stats)
+
+
+class WideA2CLearner(A2CLearner):
+    """``A2CLearner`` for one ``WideMlpPolicy`` (obs_dim <= 1024, act_dim <=
+    512): ``ce_a2c_create_wide``, whose gradient runs on the chunked kernel of
+    csrc/ppo_grad_wide_tile.h.  Everything else is ``A2CLearner``'s; at a shape
+    ``A2CLearner`` takes too, gradients (but dlogstd's last place) and
+    statistics are the same bits at the same ``grid_limit`` (0 here means 64
+    workgroups per network)."""
+    WIDE = True

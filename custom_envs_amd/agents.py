@@ -109,6 +109,12 @@ class MlpPolicy:
     actor-critic MLP (``custom_envs_amd.policy.MlpPolicy``)."""
 
 
+class WideMlpPolicy:
+    """The marker of the same MLP for wide shapes (obs_dim <= 1024, act_dim <=
+    512: ``custom_envs_amd.policy.WideMlpPolicy`` and the wide learners): the
+    reference's default 7x7-image ``Optimize-v0`` is 981 -> 490."""
+
+
 class EnvSpec:
     """The shape of an env without the env: what ``load`` builds a model on
     when no env is given, and what argument checks need.  Such a model can
@@ -229,13 +235,20 @@ class BaseAgent:
     ``load``.  A subclass gives ``LEARNER``, ``OPT_INIT``, its constructor and
     ``_update``."""
     LEARNER = None
+    WIDE_LEARNER = None          # the learner of ``WideMlpPolicy``
     OPT_INIT = {}                # shape-only models: block name -> fill value
     LOG_INTERVAL = 1
     diagnostics = False          # the constructor's switch (module docstring)
 
     def _setup(self, policy, env, kwargs, seed, verbose, policy_kwargs, learner_kwargs):
-        if policy is not MlpPolicy and policy != 'MlpPolicy':
-            raise ValueError('policy must be agents.MlpPolicy, got %r' % (policy,))
+        if policy is WideMlpPolicy or policy == 'WideMlpPolicy':
+            self.policy_kind = 'WideMlpPolicy'
+        elif policy is MlpPolicy or policy == 'MlpPolicy':
+            self.policy_kind = 'MlpPolicy'
+        else:
+            raise ValueError('policy must be agents.MlpPolicy or agents.WideMlpPolicy, got %r'
+                             % (policy,))
+        wide = self.policy_kind == 'WideMlpPolicy'
         self.hidden = hidden_from_policy_kwargs(policy_kwargs)
         self.spec = env_spec(env)
         self.env = None if isinstance(env, EnvSpec) else env
@@ -248,9 +261,10 @@ class BaseAgent:
         self.n_batch = self.spec.rows * self.n_steps
         self.num_timesteps = 0
         s = self.spec
-        self.policy = _policy.MlpPolicy(s.obs_dim, s.act_dim, self.hidden, low=s.low, high=s.high,
-                                        device=s.device)
-        self.learner = self.LEARNER(self.policy, **learner_kwargs)
+        policy_cls = _policy.WideMlpPolicy if wide else _policy.MlpPolicy
+        self.policy = policy_cls(s.obs_dim, s.act_dim, self.hidden, low=s.low, high=s.high,
+                                 device=s.device)
+        self.learner = (self.WIDE_LEARNER if wide else self.LEARNER)(self.policy, **learner_kwargs)
         self.rng = DeviceRng(self.seed, s.device)
         self._host = None
         flat = init_params_numpy(self.policy.params_layout(), self.seed)
@@ -507,7 +521,8 @@ class BaseAgent:
         for key, value in self.kwargs.items():
             kwargs[key] = {'callable': True} if callable(value) else value
         s = self.spec
-        return {'format': 1, 'algorithm': type(self).__name__, 'kwargs': kwargs,
+        return {'format': 1, 'algorithm': type(self).__name__, 'policy': self.policy_kind,
+                'kwargs': kwargs,
                 'rows': s.rows, 'obs_dim': s.obs_dim, 'act_dim': s.act_dim,
                 'low': None if s.low is None else [float(v) for v in s.low],
                 'high': None if s.high is None else [float(v) for v in s.high],
@@ -565,7 +580,8 @@ class BaseAgent:
         but not ``learn``.  ``overrides`` replace constructor arguments (a
         callable ``learning_rate`` / ``cliprange`` must be given again)."""
         data, meta, kwargs, env = cls._read(load_path, env, device, overrides)
-        model = cls(MlpPolicy, env, **kwargs)
+        # a file from before the wide policy names none: MlpPolicy
+        model = cls(meta.get('policy', 'MlpPolicy'), env, **kwargs)
         s = model.spec
         if (s.obs_dim, s.act_dim, list(model.hidden)) != (meta['obs_dim'], meta['act_dim'],
                                                           meta['hidden']):
@@ -597,8 +613,8 @@ class PPO2(BaseAgent):
                  vf_coef=0.5, max_grad_norm=0.5, lam=0.95, nminibatches=4, noptepochs=4,
                  cliprange=0.2, cliprange_vf=None, verbose=0, seed=None, policy_kwargs=None,
                  diagnostics=False):
-        from custom_envs_amd.ppo2 import PPO2Learner
-        self.LEARNER = PPO2Learner
+        from custom_envs_amd.ppo2 import PPO2Learner, WidePPO2Learner
+        self.LEARNER, self.WIDE_LEARNER = PPO2Learner, WidePPO2Learner
         self.diagnostics = bool(diagnostics)
         self.n_steps, self.nminibatches = int(n_steps), int(nminibatches)
         self.noptepochs = int(noptepochs)
@@ -655,8 +671,8 @@ class A2C(BaseAgent):
                  max_grad_norm=0.5, learning_rate=7e-4, alpha=0.99, epsilon=1e-5,
                  lr_schedule='constant', verbose=0, seed=None, policy_kwargs=None,
                  diagnostics=False):
-        from custom_envs_amd.a2c import A2CLearner
-        self.LEARNER = A2CLearner
+        from custom_envs_amd.a2c import A2CLearner, WideA2CLearner
+        self.LEARNER, self.WIDE_LEARNER = A2CLearner, WideA2CLearner
         self.diagnostics = bool(diagnostics)
         self.n_steps = int(n_steps)
         if self.n_steps < 1:

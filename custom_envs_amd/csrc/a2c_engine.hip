@@ -87,8 +87,13 @@ int enqueue_grad_kernel(const ce_a2c *l, int64_t n, int64_t n_total, int64_t m,
     g.actions = actions;
     g.ret = ret;
     g.old_values = old_values;
-    hipLaunchKernelGGL(ce::a2c_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
-                       l->core.lds_bytes, stream, g);
+    // the one place the learner's kind picks its gradient kernel
+    if (l->core.wide)
+        hipLaunchKernelGGL(ce::a2c_grad_wide_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
+                           l->core.lds_bytes, stream, g);
+    else
+        hipLaunchKernelGGL(ce::a2c_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
+                           l->core.lds_bytes, stream, g);
     return g.grid;
 }
 
@@ -154,25 +159,25 @@ void enqueue_rmsprop(ce_a2c *l, float lr, const float *stats, hipStream_t stream
     ce::policy_repack(core.policy, core.params, stream);
 }
 
-}  // namespace
-
-extern "C" {
-
-int ce_a2c_create(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out) {
-    if (!out) return fail(CE_EINVAL, "ce_a2c_create: null output handle");
+// what ce_a2c_create and ce_a2c_create_wide share
+int create(const char *who, bool wide, ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out) {
+    const std::string w(who);
+    if (!out) return fail(CE_EINVAL, w + ": null output handle");
     *out = nullptr;
-    int rc = config_ok("ce_a2c_create", cfg);
+    int rc = config_ok(who, cfg);
     if (rc != CE_OK) return rc;
-    if (!policy) return fail(CE_EINVAL, "ce_a2c_create: null policy");
+    if (!policy) return fail(CE_EINVAL, w + ": null policy");
     ce_a2c *l = new (std::nothrow) ce_a2c();
-    if (!l) return fail(CE_ENOMEM, "ce_a2c_create: host allocation failed");
+    if (!l) return fail(CE_ENOMEM, w + ": host allocation failed");
     l->cfg = *cfg;
     auto bail = [&](int code) {
         ce_a2c_destroy(l);
         return code;
     };
     rc = ce::learner_core_create(l->core, policy, cfg->grid_limit,
-                                 reinterpret_cast<const void *>(ce::a2c_grad_kernel), bail);
+                                 wide ? reinterpret_cast<const void *>(ce::a2c_grad_wide_kernel)
+                                      : reinterpret_cast<const void *>(ce::a2c_grad_kernel),
+                                 bail, wide, who);
     if (rc != CE_OK) return rc;
     const int n_params = l->core.plan.n_params;
     const size_t np = static_cast<size_t>(n_params) * sizeof(float);
@@ -184,6 +189,18 @@ int ce_a2c_create(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out) {
     CE_TRY(hipDeviceSynchronize());
     *out = l;
     return CE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ce_a2c_create(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out) {
+    return create("ce_a2c_create", false, policy, cfg, out);
+}
+
+int ce_a2c_create_wide(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out) {
+    return create("ce_a2c_create_wide", true, policy, cfg, out);
 }
 
 void ce_a2c_destroy(ce_a2c *l) {

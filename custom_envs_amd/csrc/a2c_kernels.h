@@ -27,6 +27,7 @@
 
 #include "policy_engine.h"
 #include "ppo_grad_tile.h"
+#include "ppo_grad_wide_tile.h"
 
 namespace ce {
 
@@ -98,6 +99,11 @@ struct A2cGradArgs {
 
 __global__ __launch_bounds__(kPpoBlock) void a2c_grad_kernel(const A2cGradArgs g) {
     ppo_grad_tiles(g);
+}
+
+// the same heads on the chunked body of ppo_grad_wide_tile.h (ce_a2c_create_wide)
+__global__ __launch_bounds__(kPpoBlock) void a2c_grad_wide_kernel(const A2cGradArgs g) {
+    ppo_grad_wide_tiles(g);
 }
 
 // The four statistics and |grad|^2 from the partials, one workgroup:

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "policy_engine.h"
 #include "ppo_grad_tile.h"
+#include "ppo_grad_wide_tile.h"
 
 namespace ce {
 
@@ -39,21 +40,104 @@ struct LearnerCore {
     int n_sq = 0;                // blocks of ppo2_reduce_kernel
     int w_floats = 0, act_floats = 0;
     size_t lds_bytes = 0;        // of the gradient kernel for this policy's shape
+    bool wide = false;           // from ce_<x>_create_wide: the wide gradient kernel
     float *params = nullptr;     // the master flat parameters
     float *grad = nullptr, *slab = nullptr;
     double *stat_slab = nullptr, *sq = nullptr;
 };
 
+// Workgroups per network of a wide learner unless grid_limit names another
+// number: a partial is img_floats floats (0.7 MB at 981 -> 64 -> 64 -> 490,
+// 1.6 MB at the limits), the reduce reads `grid` of them every step, and the
+// first layer's and the head's dW blocks travel to the partial and back once
+// per tile: one partial per CU would be a 175 MB (410 MB) slab.
+constexpr int kLearnerWideGrid = 64;
+
+// The wide gradient kernel's limits against a plan (no HIP call).  Only the
+// first branch can be reached from outside: ce_policy_create_wide holds a wide
+// handle to the same limits (kPlanWideMaxD / A, the hidden widths); the rest
+// guards the kernel's LDS plan should the two ever part.
+inline int learner_wide_shape_ok(const char *who, const PolicyPlan &pa) {
+    const auto bad = [who](int code, const std::string &what) {
+        return fail(code, std::string(who) + what);
+    };
+    if (!pa.wide)
+        return bad(CE_EINVAL, ": the policy must come from ce_policy_create_wide (a narrow "
+                              "handle trains under the narrow create)");
+    if (pa.D > kPpoWideMaxD)
+        return bad(CE_EUNSUPPORTED, ": obs_dim " + std::to_string(pa.D) + " exceeds the limit of " +
+                                        std::to_string(kPpoWideMaxD));
+    if (pa.A > kPpoWideMaxA)
+        return bad(CE_EUNSUPPORTED, ": act_dim " + std::to_string(pa.A) + " exceeds the limit of " +
+                                        std::to_string(kPpoWideMaxA));
+    if (pa.n_hidden < 1 || pa.n_hidden > kPlanLayers - 1)
+        return bad(CE_EUNSUPPORTED, ": the learner takes 1 to 3 hidden layers, got " +
+                                        std::to_string(pa.n_hidden));
+    for (int l = 1; l <= pa.n_hidden; ++l)
+        if (pa.in_pad[l] % 32 != 0 || pa.in_pad[l] < 32 || pa.in_pad[l] > 128)
+            return bad(CE_EUNSUPPORTED, ": hidden width " + std::to_string(pa.in_pad[l]) +
+                                            " is not a multiple of 32 up to 128");
+    return CE_OK;
+}
+
+// What both kinds of learner do after their LDS plan: the device, grid_max
+// (grid_limit, else `grid_default`, else the CU count), the kernel's
+// dynamic-LDS attribute and the shared buffers, `params` zeroed.
+template <class Bail>
+int learner_core_alloc(LearnerCore &c, int grid_limit, int grid_default, const void *grad_kernel,
+                       int max_lds_bytes, Bail &&bail) {
+    const PolicyPlan &pa = c.plan;
+    c.n_sq = (pa.n_params + 255) / 256;
+    CE_TRY(hipSetDevice(pa.device));
+    hipDeviceProp_t prop;
+    CE_TRY(hipGetDeviceProperties(&prop, pa.device));
+    const int cus = std::max(1, prop.multiProcessorCount);
+    c.grid_max = grid_limit > 0 ? grid_limit : (grid_default > 0 ? std::min(grid_default, cus) : cus);
+    CE_TRY(hipFuncSetAttribute(grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               max_lds_bytes));   // the limits' need
+    const size_t np = static_cast<size_t>(pa.n_params) * sizeof(float);
+    CE_TRY(hipMalloc(&c.params, np));
+    CE_TRY(hipMalloc(&c.grad, np));
+    CE_TRY(hipMalloc(&c.slab, static_cast<size_t>(c.grid_max) * pa.img_floats * sizeof(float)));
+    CE_TRY(hipMalloc(&c.stat_slab, static_cast<size_t>(c.grid_max) * 2 * kPpoRowStats * sizeof(double)));
+    CE_TRY(hipMalloc(&c.sq, static_cast<size_t>(c.n_sq) * sizeof(double)));
+    CE_TRY(hipMemset(c.params, 0, np));
+    return CE_OK;
+}
+
 // The plan and the gradient kernel's LDS sizes, the device, grid_max, the
 // kernel's dynamic-LDS attribute and the shared buffers, `params` zeroed.  A
 // failed HIP call goes through the caller's `bail(code)`, which destroys the
 // half-built learner.  The caller synchronises after its own initialisation.
+// `wide`: called for ce_<x>_create_wide with the wide instance of the gradient
+// kernel (ppo_grad_wide_tile.h): a wide policy handle, that kernel's LDS plan,
+// and kLearnerWideGrid workgroups per network unless grid_limit says otherwise.
 template <class Bail>
 int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
-                        const void *grad_kernel, Bail &&bail) {
+                        const void *grad_kernel, Bail &&bail, bool wide = false,
+                        const char *who = "") {
     c.policy = policy;
     c.plan = policy_plan(policy);
     const PolicyPlan &pa = c.plan;
+    if (wide) {
+        const int rc = learner_wide_shape_ok(who, pa);
+        if (rc != CE_OK) return bail(rc);
+        c.wide = true;
+        int wmax = 0, kmax = 0;
+        for (int net = 0; net < 2; ++net)
+            for (int i = 0; i <= pa.n_hidden; ++i) {
+                const int ipc = std::min(pa.in_pad[i], kPpoWideChunk);
+                wmax = std::max(wmax, ipc * (std::min(pa.out_pad[net][i], kPpoWideChunk) + 1));
+                kmax = std::max(kmax, ipc);
+            }
+        c.w_floats = (wmax + 3) / 4 * 4;
+        c.act_floats = kmax * kPpoLd;
+        c.lds_bytes = static_cast<size_t>(c.w_floats + (pa.n_hidden + 1) * c.act_floats +
+                                          kPpoWideChunk * kPpoLd +
+                                          (kPpoRowStats + 2) * kPpoTile) * sizeof(float);
+        return learner_core_alloc(c, grid_limit, kLearnerWideGrid, grad_kernel,
+                                  kPpoWideMaxLdsBytes, bail);
+    }
     // the gradient kernel holds a whole [in_pad][out_pad + 1] layer in LDS: a
     // wide handle (ce_policy_create_wide) acts, it is not trained here
     if (pa.wide)
@@ -72,21 +156,7 @@ int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
     c.lds_bytes = static_cast<size_t>(c.w_floats + (pa.n_hidden + 1) * c.act_floats +
                                       kPpoMaxA * kPpoLd +
                                       (kPpoRowStats + 2) * kPpoTile) * sizeof(float);
-    c.n_sq = (pa.n_params + 255) / 256;
-    CE_TRY(hipSetDevice(pa.device));
-    hipDeviceProp_t prop;
-    CE_TRY(hipGetDeviceProperties(&prop, pa.device));
-    c.grid_max = grid_limit > 0 ? grid_limit : std::max(1, prop.multiProcessorCount);
-    CE_TRY(hipFuncSetAttribute(grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(kPpoMaxLdsBytes)));   // the limits' need
-    const size_t np = static_cast<size_t>(pa.n_params) * sizeof(float);
-    CE_TRY(hipMalloc(&c.params, np));
-    CE_TRY(hipMalloc(&c.grad, np));
-    CE_TRY(hipMalloc(&c.slab, static_cast<size_t>(c.grid_max) * pa.img_floats * sizeof(float)));
-    CE_TRY(hipMalloc(&c.stat_slab, static_cast<size_t>(c.grid_max) * 2 * kPpoRowStats * sizeof(double)));
-    CE_TRY(hipMalloc(&c.sq, static_cast<size_t>(c.n_sq) * sizeof(double)));
-    CE_TRY(hipMemset(c.params, 0, np));
-    return CE_OK;
+    return learner_core_alloc(c, grid_limit, 0, grad_kernel, kPpoMaxLdsBytes, bail);
 }
 
 inline void learner_core_destroy(LearnerCore &c) {

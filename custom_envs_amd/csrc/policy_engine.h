@@ -79,6 +79,9 @@ int policy_rollout_args_ok(const char *who, const ce_policy *p, int engine_obs_d
 // W zero-padded to [in_pad][out_pad], policy_engine.hip: plan), the segments
 // that map the flat parameter vector into the image, and the image itself.
 constexpr int kPlanLayers = 4;                  // hidden layers + the head
+// the widest plan: a wide handle's limits (policy_wide_kernels.h) and the wide
+// gradient kernel's (ppo_grad_wide_tile.h)
+constexpr int kPlanWideMaxD = 1024, kPlanWideMaxA = 512;
 constexpr int kPlanSegs = 4 * kPlanLayers + 1;  // (W, b) per layer per network + logstd
 struct PolicyPlan {
     int D, A, n_hidden;
@@ -87,7 +90,8 @@ struct PolicyPlan {
     int n_segs;                                 // logstd is the last segment
     int seg_dst[kPlanSegs], seg_src[kPlanSegs], seg_cols[kPlanSegs], seg_cols_pad[kPlanSegs];
     int n_params, img_floats, device;
-    int wide;                                   // from ce_policy_create_wide: the learners refuse it
+    int wide;                                   // from ce_policy_create_wide: ce_<x>_create refuses it,
+                                                // ce_<x>_create_wide requires it
     float *img;
 };
 PolicyPlan policy_plan(const ce_policy *p);

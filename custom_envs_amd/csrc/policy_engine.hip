@@ -198,6 +198,8 @@ void policy_dims(const ce_policy *p, int *obs_dim, int *act_dim) {
 
 PolicyPlan policy_plan(const ce_policy *p) {
     static_assert(kPlanLayers == kPolLayers && kPlanSegs == kPolSegs, "plan sizes");
+    static_assert(kPlanWideMaxD == kPolWideMaxD && kPlanWideMaxA == kPolWideMaxA,
+                  "a wide handle and a wide learner have the same limits");
     const PolicyArgs &a = p->args;
     PolicyPlan q{};
     q.D = a.D;

@@ -97,8 +97,13 @@ int enqueue_grad_kernel(const ce_ppo2 *l, int64_t n, int64_t n_total, int64_t m,
     g.old_neglogp = old_neglogp;
     g.old_values = old_values;
     g.advstat = l->advstat;
-    hipLaunchKernelGGL(ce::ppo2_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
-                       l->core.lds_bytes, stream, g);
+    // the one place the learner's kind picks its gradient kernel
+    if (l->core.wide)
+        hipLaunchKernelGGL(ce::ppo2_grad_wide_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
+                           l->core.lds_bytes, stream, g);
+    else
+        hipLaunchKernelGGL(ce::ppo2_grad_kernel, dim3(g.grid, 2), dim3(ce::kPpoBlock),
+                           l->core.lds_bytes, stream, g);
     return g.grid;
 }
 
@@ -133,25 +138,25 @@ void enqueue_adam(ce_ppo2 *l, float lr, const float *stats, hipStream_t stream) 
     ce::policy_repack(core.policy, core.params, stream);
 }
 
-}  // namespace
-
-extern "C" {
-
-int ce_ppo2_create(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out) {
-    if (!out) return fail(CE_EINVAL, "ce_ppo2_create: null output handle");
+// what ce_ppo2_create and ce_ppo2_create_wide share
+int create(const char *who, bool wide, ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out) {
+    const std::string w(who);
+    if (!out) return fail(CE_EINVAL, w + ": null output handle");
     *out = nullptr;
-    int rc = config_ok("ce_ppo2_create", cfg);
+    int rc = config_ok(who, cfg);
     if (rc != CE_OK) return rc;
-    if (!policy) return fail(CE_EINVAL, "ce_ppo2_create: null policy");
+    if (!policy) return fail(CE_EINVAL, w + ": null policy");
     ce_ppo2 *l = new (std::nothrow) ce_ppo2();
-    if (!l) return fail(CE_ENOMEM, "ce_ppo2_create: host allocation failed");
+    if (!l) return fail(CE_ENOMEM, w + ": host allocation failed");
     l->cfg = *cfg;
     auto bail = [&](int code) {
         ce_ppo2_destroy(l);
         return code;
     };
     rc = ce::learner_core_create(l->core, policy, cfg->grid_limit,
-                                 reinterpret_cast<const void *>(ce::ppo2_grad_kernel), bail);
+                                 wide ? reinterpret_cast<const void *>(ce::ppo2_grad_wide_kernel)
+                                      : reinterpret_cast<const void *>(ce::ppo2_grad_kernel),
+                                 bail, wide, who);
     if (rc != CE_OK) return rc;
     const size_t np = static_cast<size_t>(l->core.plan.n_params) * sizeof(float);
     CE_TRY(hipMalloc(&l->m, np));
@@ -162,6 +167,18 @@ int ce_ppo2_create(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out) 
     CE_TRY(hipDeviceSynchronize());
     *out = l;
     return CE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ce_ppo2_create(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out) {
+    return create("ce_ppo2_create", false, policy, cfg, out);
+}
+
+int ce_ppo2_create_wide(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out) {
+    return create("ce_ppo2_create_wide", true, policy, cfg, out);
 }
 
 void ce_ppo2_destroy(ce_ppo2 *l) {

@@ -19,6 +19,7 @@
 
 #include "policy_engine.h"
 #include "ppo_grad_tile.h"
+#include "ppo_grad_wide_tile.h"
 
 namespace ce {
 
@@ -173,6 +174,11 @@ struct Ppo2GradArgs {
 
 __global__ __launch_bounds__(kPpoBlock) void ppo2_grad_kernel(const Ppo2GradArgs g) {
     ppo_grad_tiles(g);
+}
+
+// the same heads on the chunked body of ppo_grad_wide_tile.h (ce_ppo2_create_wide)
+__global__ __launch_bounds__(kPpoBlock) void ppo2_grad_wide_kernel(const Ppo2GradArgs g) {
+    ppo_grad_wide_tiles(g);
 }
 
 // -------------------------------------------------------------------- reduce

@@ -54,6 +54,9 @@
 //
 // No floating-point atomics: the same inputs with the same G give the same
 // bits.  Different G regroup the float32 per-workgroup sums.
+//
+// ppo_grad_wide_tile.h holds a copy of this body's hidden layers, value head
+// and row code for wide shapes: a fix to either body belongs in both.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -174,11 +174,15 @@ class Learner:
     CONFIG = None
     BATCH_FIELDS = ()
     _loss_grad = None
+    WIDE = False         # a wide learner: ``ce_<x>_create_wide`` on a ``WideMlpPolicy``
 
     def __init__(self, policy, **cfg):
-        if not isinstance(policy, MlpPolicy):
+        if self.WIDE:
+            if not isinstance(policy, WideMlpPolicy):
+                raise TypeError('policy must be a WideMlpPolicy')
+        elif not isinstance(policy, MlpPolicy):
             raise TypeError('policy must be an MlpPolicy')
-        if isinstance(policy, WideMlpPolicy):      # what ce_<x>_create answers, without the call
+        elif isinstance(policy, WideMlpPolicy):    # what ce_<x>_create answers, without the call
             raise _native.NativeEngineError(
                 '%s_create: the learners take obs_dim <= 128, act_dim <= 64: a WideMlpPolicy '
                 '(obs_dim %d, act_dim %d) acts and rolls out only (CE_EUNSUPPORTED)'
@@ -193,7 +197,8 @@ class Learner:
         if policy._h is None:        # shape only
             return
         handle = ctypes.c_void_p()
-        self._call('create', policy._h, ctypes.byref(self._cfg), ctypes.byref(handle))
+        self._call('create_wide' if self.WIDE else 'create', policy._h, ctypes.byref(self._cfg),
+                   ctypes.byref(handle))
         self._h = handle
         host = getattr(policy, '_host_params', None)
         if host is not None:

@@ -422,3 +422,13 @@ class PPO2Learner(Learner):
                 all_stats.append(self.step(batch, perm[b * size:(b + 1) * size], stream=stream,
                                            lr=lr, cliprange=cliprange))
         return all_stats
+
+
+class WidePPO2Learner(PPO2Learner):
+    """``PPO2Learner`` for one ``WideMlpPolicy`` (obs_dim <= 1024, act_dim <=
+    512): ``ce_ppo2_create_wide``, whose gradient runs on the chunked kernel of
+    csrc/ppo_grad_wide_tile.h.  Everything else is ``PPO2Learner``'s; at a shape
+    ``PPO2Learner`` takes too, gradients (but dlogstd's last place) and
+    statistics are the same bits at the same ``grid_limit`` (0 here means 64
+    workgroups per network)."""
+    WIDE = True

@@ -74,7 +74,8 @@
  *                    the actor-critic network, its flat parameters and bounds
  *   ce_policy_create_wide / ce_policy_wide_n_params
  *                    the same handle for obs_dim <= 1024, act_dim <= 512 (the
- *                    reference's 981 -> 490 default shape); act side only
+ *                    reference's 981 -> 490 default shape); trained through
+ *                    ce_ppo2_create_wide / ce_a2c_create_wide
  *   ce_policy_forward  one fused launch: action, env_action, neglogp, value
  *   ce_rollout_policy / ce_multi_rollout_policy
  *                    K x (policy forward, VecEnv.step) from one call, the
@@ -408,7 +409,8 @@ int ce_nn_get_state(ce_nn_engine *eng, float *theta, float *gprev, int32_t *step
  * obs_dim <= 128, act_dim <= 64; anything else is CE_EUNSUPPORTED.  The
  * reference's default 7x7-image Optimize shape (obs_dim 981, act_dim 490) is
  * served on the act side by a wide handle, ce_policy_create_wide below
- * (obs_dim <= 1024, act_dim <= 512); the learners refuse it.
+ * (obs_dim <= 1024, act_dim <= 512); ce_ppo2_create / ce_a2c_create refuse it,
+ * ce_ppo2_create_wide / ce_a2c_create_wide train it.
  * Every argument check of every ce_policy_* / ce_*rollout_policy call happens
  * before its first HIP call.
  */
@@ -444,9 +446,10 @@ int ce_policy_create(const ce_policy_config *cfg, ce_policy **out);
  * handle always launches that kernel; at a shape ce_policy_create takes too
  * it writes the same bits.  Every entry that takes a ce_policy takes a wide
  * one -- set_params, set_bounds, forward, forward_rng, the rollouts and their
- * _rng / _vecnorm forms -- except the learners: ce_ppo2_create and
+ * _rng / _vecnorm forms -- except the narrow learners: ce_ppo2_create and
  * ce_a2c_create answer CE_EUNSUPPORTED before any allocation (they take
- * obs_dim <= 128, act_dim <= 64). */
+ * obs_dim <= 128, act_dim <= 64); ce_ppo2_create_wide and ce_a2c_create_wide
+ * take it. */
 int ce_policy_wide_n_params(const ce_policy_config *cfg);
 int ce_policy_create_wide(const ce_policy_config *cfg, ce_policy **out);
 void ce_policy_destroy(ce_policy *p);
@@ -569,6 +572,15 @@ typedef struct ce_ppo2_config {
 
 /* The policy must outlive the learner.  The master parameters start as zeros. */
 int ce_ppo2_create(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out);
+/* The same handle for a policy from ce_policy_create_wide (obs_dim <= 1024,
+ * act_dim <= 512, 1..3 hidden layers of 32..128 units): the gradient runs on
+ * the chunked kernel of csrc/ppo_grad_wide_tile.h, every other ce_ppo2_* entry
+ * takes the handle as it is.  At a shape ce_ppo2_create takes too the gradient
+ * (but dlogstd's last place) and statistics are the same bits at the same
+ * grid_limit.  A narrow policy handle is CE_EINVAL; grid_limit 0 means 64
+ * workgroups per network (at most one per CU).  The config struct is
+ * ce_ppo2_create's. */
+int ce_ppo2_create_wide(ce_policy *policy, const ce_ppo2_config *cfg, ce_ppo2 **out);
 void ce_ppo2_destroy(ce_ppo2 *l);
 /* The master parameters (n = ce_policy_n_params; host pointer: synchronises;
  * CE_PTR_DEVICE: stream-ordered).  Both also write through to the policy's
@@ -646,6 +658,8 @@ typedef struct ce_a2c_config {
 
 /* The policy must outlive the learner.  The master parameters start as zeros. */
 int ce_a2c_create(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out);
+/* As ce_ppo2_create_wide: the A2C learner of a policy from ce_policy_create_wide. */
+int ce_a2c_create_wide(ce_policy *policy, const ce_a2c_config *cfg, ce_a2c **out);
 void ce_a2c_destroy(ce_a2c *l);
 /* As ce_ppo2_set_params / _get_params (one body, csrc/learner_host.h); ms and
  * mom are kept. */
