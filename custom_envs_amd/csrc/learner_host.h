@@ -21,6 +21,7 @@
 #pragma once
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <string>
 
@@ -105,6 +106,24 @@ int learner_core_alloc(LearnerCore &c, int grid_limit, int grid_default, const v
     return CE_OK;
 }
 
+// The gradient kernel's LDS plan for c.plan (ppo_lds_floats): the weight stage
+// holds the largest layer and an activation buffer the widest input, each
+// clamped to `chunk` rows and columns; the head buffer has head_cols columns.
+inline void learner_lds_plan(LearnerCore &c, int chunk, int head_cols) {
+    const PolicyPlan &pa = c.plan;
+    int wmax = 0, kmax = 0;
+    for (int net = 0; net < 2; ++net)
+        for (int i = 0; i <= pa.n_hidden; ++i) {
+            const int ipc = std::min(pa.in_pad[i], chunk);
+            wmax = std::max(wmax, ipc * (std::min(pa.out_pad[net][i], chunk) + 1));
+            kmax = std::max(kmax, ipc);
+        }
+    c.w_floats = (wmax + 3) / 4 * 4;
+    c.act_floats = kmax * kPpoLd;
+    c.lds_bytes = static_cast<size_t>(ppo_lds_floats(c.w_floats, c.act_floats, pa.n_hidden,
+                                                     head_cols)) * sizeof(float);
+}
+
 // The plan and the gradient kernel's LDS sizes, the device, grid_max, the
 // kernel's dynamic-LDS attribute and the shared buffers, `params` zeroed.  A
 // failed HIP call goes through the caller's `bail(code)`, which destroys the
@@ -123,18 +142,7 @@ int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
         const int rc = learner_wide_shape_ok(who, pa);
         if (rc != CE_OK) return bail(rc);
         c.wide = true;
-        int wmax = 0, kmax = 0;
-        for (int net = 0; net < 2; ++net)
-            for (int i = 0; i <= pa.n_hidden; ++i) {
-                const int ipc = std::min(pa.in_pad[i], kPpoWideChunk);
-                wmax = std::max(wmax, ipc * (std::min(pa.out_pad[net][i], kPpoWideChunk) + 1));
-                kmax = std::max(kmax, ipc);
-            }
-        c.w_floats = (wmax + 3) / 4 * 4;
-        c.act_floats = kmax * kPpoLd;
-        c.lds_bytes = static_cast<size_t>(c.w_floats + (pa.n_hidden + 1) * c.act_floats +
-                                          kPpoWideChunk * kPpoLd +
-                                          (kPpoRowStats + 2) * kPpoTile) * sizeof(float);
+        learner_lds_plan(c, kPpoWideChunk, kPpoWideChunk);
         return learner_core_alloc(c, grid_limit, kLearnerWideGrid, grad_kernel,
                                   kPpoWideMaxLdsBytes, bail);
     }
@@ -145,17 +153,7 @@ int learner_core_create(LearnerCore &c, ce_policy *policy, int grid_limit,
                          "the learners take obs_dim <= 128, act_dim <= 64: a policy from "
                          "ce_policy_create_wide (obs_dim " + std::to_string(pa.D) + ", act_dim " +
                              std::to_string(pa.A) + ") acts and rolls out only"));
-    int wmax = 0, kmax = 0;
-    for (int net = 0; net < 2; ++net)
-        for (int i = 0; i <= pa.n_hidden; ++i) {
-            wmax = std::max(wmax, pa.in_pad[i] * (pa.out_pad[net][i] + 1));
-            kmax = std::max(kmax, pa.in_pad[i]);
-        }
-    c.w_floats = (wmax + 3) / 4 * 4;
-    c.act_floats = kmax * kPpoLd;
-    c.lds_bytes = static_cast<size_t>(c.w_floats + (pa.n_hidden + 1) * c.act_floats +
-                                      kPpoMaxA * kPpoLd +
-                                      (kPpoRowStats + 2) * kPpoTile) * sizeof(float);
+    learner_lds_plan(c, INT_MAX, kPpoMaxA);      // whole layers staged
     return learner_core_alloc(c, grid_limit, 0, grad_kernel, kPpoMaxLdsBytes, bail);
 }
 

@@ -55,8 +55,13 @@
 // No floating-point atomics: the same inputs with the same G give the same
 // bits.  Different G regroup the float32 per-workgroup sums.
 //
-// ppo_grad_wide_tile.h holds a copy of this body's hidden layers, value head
-// and row code for wide shapes: a fix to either body belongs in both.
+// ppo_grad_wide_tile.h walks the same steps in chunks for wide shapes.  The
+// four kernels are register-saturated, and a step is a shared function ("the
+// tile parts" below) only where calling it leaves all four kernels' device
+// assembly the text it was with the step inline; every other step both
+// bodies have stays inline in both, and a fix to it belongs in both.  Which
+// steps those are, and what was tried: DESIGN.md 3.24, "One text where the
+// code objects allow it".
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,9 +83,17 @@ __device__ __forceinline__ int ppo_acc_row(int r, int h) { return (r & 3) + 8 * 
 constexpr int kPpoStats = 8;        // loss, pg, vf, entropy, approxkl, clipfrac, |grad|^2, spare
 constexpr int kPpoRowStats = 4;     // per-row sums a workgroup keeps (pi: pg, kl, clipped; vf: vf)
 constexpr int kPpoStatBlock = 1024;
-// LDS of a gradient kernel at the shape limits (D = 128, 3 x 128 hidden, A = 64)
-constexpr int kPpoMaxLdsBytes =
-    (128 * 129 + 4 * 128 * kPpoLd + kPpoMaxA * kPpoLd + (kPpoRowStats + 2) * kPpoTile) * 4;
+// LDS floats of a gradient kernel, as both bodies carve it: the weight stage,
+// n_hidden + 1 activation buffers, the head buffer [head_cols][33], the row
+// weights, row statistics and source rows
+__host__ __device__ constexpr int ppo_lds_floats(int w_floats, int act_floats, int n_hidden,
+                                                 int head_cols) {
+    return w_floats + (n_hidden + 1) * act_floats + head_cols * kPpoLd +
+           (kPpoRowStats + 2) * kPpoTile;
+}
+// at the shape limits (D = 128, 3 x 128 hidden, A = 64)
+constexpr int kPpoMaxLdsBytes = ppo_lds_floats(128 * 129, 128 * kPpoLd, 3, kPpoMaxA) * 4;
+static_assert(kPpoMaxLdsBytes == 142848, "the header comment's LDS budget");
 constexpr float kPpoLog2PiE = 2.8378770664093453f;   // log(2 pi) + 1
 
 __device__ __forceinline__ int ppo_src_row(const int32_t *idx, long long i, int m) {
@@ -112,6 +125,16 @@ __device__ __forceinline__ float ppo_tanh_comp(float z) {
 }
 __device__ __forceinline__ float ppo_act(float u) { return copysignf(1.0f - fabsf(u), u); }
 
+// ------------------------------------------------------------ the tile parts
+// What ppo_grad_tiles and ppo_grad_wide_tiles both call.  li = tid & 31,
+// h = (tid & 63) >> 5; element r of an MFMA accumulator is row
+// ppo_acc_row(r, h), column li of its 32 x 32 block.
+
+// The two weight stagers: a whole contiguous [ip][op] layer to [ip][op + 1],
+// and rows x cw floats out of a wider matrix (row stride src_ld; cw, src_ld
+// and the offset multiples of 4) to [rows][cw + 1].  The second does the
+// first's job at src_ld = op, through other index arithmetic and so other code
+// in the narrow kernels: they keep the first.
 __device__ __forceinline__ void ppo_stage_w(float *wbuf, const float *img, int ip, int op) {
     const float4 *src = reinterpret_cast<const float4 *>(img);
     const int n4 = ip * op / 4, ld = op + 1;
@@ -125,7 +148,82 @@ __device__ __forceinline__ void ppo_stage_w(float *wbuf, const float *img, int i
         d[3] = v.w;
     }
 }
+__device__ __forceinline__ void ppo_wide_stage_w(float *wbuf, const float *src, int rows, int cw,
+                                                 int src_ld) {
+    const int c4 = cw >> 2, n4 = rows * c4, ld = cw + 1;
+    for (int i = threadIdx.x; i < n4; i += kPpoBlock) {
+        const int r = i / c4, c = 4 * (i - r * c4);
+        const float4 v = *reinterpret_cast<const float4 *>(src + static_cast<long long>(r) * src_ld + c);
+        float *d = wbuf + r * ld + c;
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+        d[3] = v.w;
+    }
+}
 
+// The policy head's row weight.  8 threads per row (thread tid: row tid >> 3)
+// come with their share `sum` of the row's sum z^2: the shares are folded, the
+// row's first thread forms neglogp (float64, see the header comment) and,
+// through pi_row, the weight w into wrow: 0 past the last row.
+template <class Args>
+__device__ __forceinline__ void ppo_row_weight(const Args &g, const int *rowsrc, float *rowstat,
+                                               float *wrow, double sum, double sum_logstd,
+                                               float inv_n) {
+    const PolicyPlan &a = g.p;
+    const int tid = threadIdx.x, r = tid >> 3, part = tid & 7;
+    sum += __shfl_xor(sum, 1);
+    sum += __shfl_xor(sum, 2);
+    sum += __shfl_xor(sum, 4);
+    const int src = rowsrc[r];
+    if (part == 0) {
+        float w = 0.0f;
+        if (src >= 0) {
+            const double nlp = 0.5 * sum + sum_logstd + 0.5 * a.A * 1.8378770664093453;
+            w = g.pi_row(src, nlp, inv_n, rowstat + r);
+        }
+        wrow[r] = w;
+    }
+}
+
+// The backward.  One 32 x 32 block of dW += X^T dZ over the tile's 32 rows
+// (the MFMA's K) on the accumulator c: xa = X + the lane's row of the block *
+// 33 + h (valid: that row exists), zb = dZ + the lane's column * 33 + h; comp:
+// X is in complement form.
+__device__ __forceinline__ ppo_f32x16 ppo_dw_mfma(ppo_f32x16 c, const float *xa, const float *zb,
+                                                  bool valid, bool comp) {
+#pragma unroll
+    for (int k = 0; k < kPpoTile; k += 2) {
+        float xv = valid ? xa[k] : 0.0f;
+        if (comp) xv = ppo_act(xv);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, zb[k], c, 0, 0, 0);
+    }
+    return c;
+}
+// db's share of the tile: one dZ column summed over the rows
+__device__ __forceinline__ float ppo_col_sum(const float *col) {
+    float sum = 0.0f;
+    for (int r = 0; r < kPpoTile; ++r) sum += col[r];
+    return sum;
+}
+// dX = dZ W^T for one wave's 32 input units, continued on acc over cw staged
+// columns: za = dZ + h * 33 + li, wb = W + the lane's unit * ld + h
+__device__ __forceinline__ ppo_f32x16 ppo_dx_mfma(ppo_f32x16 acc, const float *za, const float *wb,
+                                                  int cw) {
+    for (int k = 0; k < cw; k += 2)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[k * kPpoLd], wb[k], acc, 0, 0, 0);
+    return acc;
+}
+
+// the workgroup's statistic sums, held by threads 128 .. 131, to stat_slab
+template <class Args>
+__device__ __forceinline__ void ppo_store_stats(const Args &g, double stat_acc) {
+    const int tid = threadIdx.x, net = blockIdx.y;
+    if (tid >= 128 && tid < 128 + kPpoRowStats)
+        g.stat_slab[(static_cast<long long>(blockIdx.x) * 2 + net) * kPpoRowStats + tid - 128] = stat_acc;
+}
+
+// --------------------------------------------------------- the narrow body
 // The whole gradient kernel but its __global__ line (see the header comment).
 template <class Args>
 __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
@@ -215,15 +313,14 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) accd[r] = 0.0;
                     for (int k = 0; k < ip; k += 2) {
-                        float xv = xa[k * kPpoLd];
-                        if (l > 0) xv = ppo_act(xv);
+                        const float xv = ppo_act(xa[k * kPpoLd]);
                         const ppo_f32x16 zero = {};
                         const ppo_f32x16 c =
                             __builtin_amdgcn_mfma_f32_32x32x2f32(xv, wb[k * ld], zero, 0, 0, 0);
 #pragma unroll
                         for (int r = 0; r < 16; ++r) accd[r] += c[r];
                     }
-                    if (l == L) {
+                    if (l == L) {      // always: dropping the test moves the kernels' code
                         // the policy head: z = (action - mean) / std, zero past A
                         // and past the last row
                         const bool on = col < a.A;
@@ -243,11 +340,9 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
                     }
                 } else {
                     ppo_f32x16 acc = {};
-                    for (int k = 0; k < ip; k += 2) {
-                        float xv = xa[k * kPpoLd];
-                        if (l > 0) xv = ppo_act(xv);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, wb[k * ld], acc, 0, 0, 0);
-                    }
+                    for (int k = 0; k < ip; k += 2)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ppo_act(xa[k * kPpoLd]), wb[k * ld],
+                                                                   acc, 0, 0, 0);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) pre[r] = acc[r] + bias;
                 }
@@ -280,18 +375,7 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
                     const double z = dzh[c * kPpoLd + r];
                     s += z * z;
                 }
-                s += __shfl_xor(s, 1);
-                s += __shfl_xor(s, 2);
-                s += __shfl_xor(s, 4);
-                const int src = rowsrc[r];
-                if (part == 0) {
-                    float w = 0.0f;
-                    if (src >= 0) {
-                        const double nlp = 0.5 * s + sum_logstd + 0.5 * a.A * 1.8378770664093453;
-                        w = g.pi_row(src, nlp, inv_n, rowstat + r);
-                    }
-                    wrow[r] = w;
-                }
+                ppo_row_weight(g, rowsrc, rowstat, wrow, s, sum_logstd, inv_n);
             }
             __syncthreads();
             // dZ = -w z / std over z, column by column; dlogstd on the way
@@ -334,33 +418,18 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
                 if (b < nb) {   // wave-uniform
                     const int mi = b / nni, ni = b - mi * nni;
                     const int mrow = mi * 32 + li;
-                    const bool valid = mrow < ip;
-                    const float *xa = x + (valid ? mrow : 0) * kPpoLd + h;
-                    const float *zb = dz + (ni * 32 + li) * kPpoLd + h;
-#pragma unroll
-                    for (int k = 0; k < kPpoTile; k += 2) {
-                        float xv = valid ? xa[k] : 0.0f;
-                        if (l > 0) xv = ppo_act(xv);      // l > 0: ip is a hidden width, all valid
-                        dw[l][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, zb[k], dw[l][j], 0, 0, 0);
-                    }
+                    const bool valid = mrow < ip;      // l > 0: ip is a hidden width, all valid
+                    dw[l][j] = ppo_dw_mfma(dw[l][j], x + (valid ? mrow : 0) * kPpoLd + h,
+                                           dz + (ni * 32 + li) * kPpoLd + h, valid, l > 0);
                 }
             }
-            if (tid < op) {
-                const float *col = dz + tid * kPpoLd;
-                float s = 0.0f;
-                for (int r = 0; r < kPpoTile; ++r) s += col[r];
-                db[l] += s;
-            }
+            if (tid < op) db[l] += ppo_col_sum(dz + tid * kPpoLd);
             if (l > 0) {
                 __syncthreads();      // W_l staged
                 const int n0 = wave * 32;
                 ppo_f32x16 acc = {};
-                if (n0 < ip) {        // dX = dZ_l W_l^T, in-chunk n0 (ip is a hidden width here)
-                    const float *za = dz + h * kPpoLd + li;
-                    const float *wb = wbuf + (n0 + li) * ld + h;
-                    for (int k = 0; k < op; k += 2)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[k * kPpoLd], wb[k], acc, 0, 0, 0);
-                }
+                if (n0 < ip)          // dX = dZ_l W_l^T, in-chunk n0 (ip is a hidden width here)
+                    acc = ppo_dx_mfma(acc, dz + h * kPpoLd + li, wbuf + (n0 + li) * ld + h, op);
                 __syncthreads();      // every dW_l read of X_l is done
                 if (n0 < ip) {
                     float *col = x + (n0 + li) * kPpoLd;
@@ -398,8 +467,7 @@ __device__ __forceinline__ void ppo_grad_tiles(const Args &g) {
         if (tid < op) part[a.off_b[net][l] + tid] = db[l];
     }
     if (net == 0 && tid < a.A) part[a.off_logstd + tid] = dls;
-    if (tid >= 128 && tid < 128 + kPpoRowStats)
-        g.stat_slab[(static_cast<long long>(blockIdx.x) * 2 + net) * kPpoRowStats + tid - 128] = stat_acc;
+    ppo_store_stats(g, stat_acc);
 }
 
 // -------------------------------------------------------------------- reduce

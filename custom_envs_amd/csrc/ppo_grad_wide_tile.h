@@ -64,9 +64,10 @@
 //   the limits (1024 -> 3 x 128 -> 512): 16 512 + 4 x 4 224 + 4 224 + 192
 //                           = 37 824 floats = 151 296 B of the CU's 160 KiB
 //
-// The hidden layers' forward and backward, the value head and the head's row
-// code are ppo_grad_tile.h's text, copied and not shared so that the narrow
-// kernels' code object stays what it was: a fix to either body belongs in both.
+// The row weight, a dW block's MFMAs, the hidden and first layers' db sums, the
+// hidden layers' dX chain and the statistic store are the tile parts of
+// ppo_grad_tile.h.  The other steps the narrow body has too are written here
+// again, and a fix to one belongs in both: see that file's header comment.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,24 +83,8 @@ constexpr int kPpoWideMaxD = kPlanWideMaxD;     // observation width: a wide han
 constexpr int kPpoWideMaxA = kPlanWideMaxA;     // action width
 constexpr int kPpoWideChunk = 128;     // K-chunk of the first layer, N-chunk of the head
 // LDS of a wide gradient kernel at the shape limits
-constexpr int kPpoWideMaxLdsBytes =
-    (128 * 129 + 4 * 128 * kPpoLd + kPpoWideChunk * kPpoLd + (kPpoRowStats + 2) * kPpoTile) * 4;
-
-// rows x cw floats from `src` (row stride src_ld; cw, src_ld and the offset
-// multiples of 4) into the stage as [rows][cw + 1]
-__device__ __forceinline__ void ppo_wide_stage_w(float *wbuf, const float *src, int rows, int cw,
-                                                 int src_ld) {
-    const int c4 = cw >> 2, n4 = rows * c4, ld = cw + 1;
-    for (int i = threadIdx.x; i < n4; i += kPpoBlock) {
-        const int r = i / c4, c = 4 * (i - r * c4);
-        const float4 v = *reinterpret_cast<const float4 *>(src + static_cast<long long>(r) * src_ld + c);
-        float *d = wbuf + r * ld + c;
-        d[0] = v.x;
-        d[1] = v.y;
-        d[2] = v.z;
-        d[3] = v.w;
-    }
-}
+constexpr int kPpoWideMaxLdsBytes = ppo_lds_floats(128 * 129, 128 * kPpoLd, 3, kPpoWideChunk) * 4;
+static_assert(kPpoWideMaxLdsBytes == 151296, "the header comment's LDS budget");
 
 // columns k0 .. k0 + kc - 1 of the gathered observation tile, k-major, zero
 // past D and past the last row
@@ -117,22 +102,9 @@ __device__ __forceinline__ void ppo_wide_stage_obs(float *x, const float *obs, c
     }
 }
 
-// One 32 x 32 block of dW += X^T dZ over the tile's 32 rows: the MFMAs of the
-// narrow body on the accumulator c.
-__device__ __forceinline__ ppo_f32x16 ppo_wide_dw_mfma(ppo_f32x16 c, const float *xa,
-                                                       const float *zb, bool valid, bool comp) {
-#pragma unroll
-    for (int k = 0; k < kPpoTile; k += 2) {
-        float xv = valid ? xa[k] : 0.0f;
-        if (comp) xv = ppo_act(xv);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, zb[k], c, 0, 0, 0);
-    }
-    return c;
-}
-
-// The same block with its C operand in the workgroup's slab partial: `blk` is
-// element (0, this lane's column) of the block, `ld` its row stride, rows
-// below `rows` exist.  The first tile starts from zero without reading.
+// ppo_dw_mfma with the block's C operand in the workgroup's slab partial:
+// `blk` is element (0, this lane's column) of the block, `ld` its row stride,
+// rows below `rows` exist.  The first tile starts from zero without reading.
 __device__ __forceinline__ void ppo_wide_dw_slab(float *blk, int ld, int rows, bool first,
                                                  const float *xa, const float *zb, bool valid,
                                                  bool comp, int h) {
@@ -144,7 +116,7 @@ __device__ __forceinline__ void ppo_wide_dw_slab(float *blk, int ld, int rows, b
             if (row < rows) c[r] = blk[row * ld];
         }
     }
-    c = ppo_wide_dw_mfma(c, xa, zb, valid, comp);
+    c = ppo_dw_mfma(c, xa, zb, valid, comp);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = ppo_acc_row(r, h);
@@ -310,18 +282,7 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
                 }
                 if (!one_chunk) __syncthreads();      // the stage and z are free
             }
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            s += __shfl_xor(s, 4);
-            const int src = rowsrc[r];
-            if (pt == 0) {
-                float w = 0.0f;
-                if (src >= 0) {
-                    const double nlp = 0.5 * s + sum_logstd + 0.5 * a.A * 1.8378770664093453;
-                    w = g.pi_row(src, nlp, inv_n, rowstat + r);
-                }
-                wrow[r] = w;
-            }
+            ppo_row_weight(g, rowsrc, rowstat, wrow, s, sum_logstd, inv_n);
             __syncthreads();
         }
         // the tile's statistic sums, rows in order, one thread per statistic
@@ -377,7 +338,7 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
                                      opL, 32, first, x + (mi * 32 + li) * kPpoLd + h,
                                      dzh + (ni * 32 + li) * kPpoLd + h, true, true, h);
                 }
-                if (tid < cw) {
+                if (tid < cw) {       // ppo_col_sum's text (see ppo_grad_tile.h's header)
                     const float *col = dzh + tid * kPpoLd;
                     float s = 0.0f;
                     for (int r = 0; r < kPpoTile; ++r) s += col[r];
@@ -386,7 +347,7 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
                     v += s;
                     *at = v;
                 }
-                if (n0 < ipL) {       // this chunk's columns of the dX chain
+                if (n0 < ipL) {       // this chunk's columns of the dX chain: ppo_dx_mfma's text
                     const float *za = dzh + h * kPpoLd + li;
                     const float *wb = wbuf + (n0 + li) * ld + h;
                     for (int k = 0; k < cw; k += 2)
@@ -419,24 +380,15 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
                 const int b = wave + 4 * j;
                 if (b < nb) {   // wave-uniform
                     const int mi = b / nni, ni = b - mi * nni;
-                    dwh[l - 1][j] = ppo_wide_dw_mfma(dwh[l - 1][j], x + (mi * 32 + li) * kPpoLd + h,
-                                                     dz + (ni * 32 + li) * kPpoLd + h, true, true);
+                    dwh[l - 1][j] = ppo_dw_mfma(dwh[l - 1][j], x + (mi * 32 + li) * kPpoLd + h,
+                                                dz + (ni * 32 + li) * kPpoLd + h, true, true);
                 }
             }
-            if (tid < op) {
-                const float *col = dz + tid * kPpoLd;
-                float s = 0.0f;
-                for (int r = 0; r < kPpoTile; ++r) s += col[r];
-                db[l] += s;
-            }
+            if (tid < op) db[l] += ppo_col_sum(dz + tid * kPpoLd);
             __syncthreads();      // W_l staged
             ppo_f32x16 acc = {};
-            if (n0 < ip) {        // dX = dZ_l W_l^T
-                const float *za = dz + h * kPpoLd + li;
-                const float *wb = wbuf + (n0 + li) * ld + h;
-                for (int k = 0; k < op; k += 2)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[k * kPpoLd], wb[k], acc, 0, 0, 0);
-            }
+            if (n0 < ip)          // dX = dZ_l W_l^T
+                acc = ppo_dx_mfma(acc, dz + h * kPpoLd + li, wbuf + (n0 + li) * ld + h, op);
             __syncthreads();      // every dW_l read of X_l is done
             if (n0 < ip) {
                 float *col = x + (n0 + li) * kPpoLd;
@@ -453,12 +405,7 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
             // the slab partial
             const int ip = a.in_pad[0], op = a.out_pad[net][0];
             const float *dz = xbase + g.act_floats;
-            if (tid < op) {
-                const float *col = dz + tid * kPpoLd;
-                float s = 0.0f;
-                for (int r = 0; r < kPpoTile; ++r) s += col[r];
-                db[0] += s;
-            }
+            if (tid < op) db[0] += ppo_col_sum(dz + tid * kPpoLd);
             const int nni = op >> 5;
             for (int k0 = 0; k0 < ip; k0 += kPpoWideChunk) {
                 const int kc = ip - k0 < kPpoWideChunk ? ip - k0 : kPpoWideChunk;
@@ -501,8 +448,7 @@ __device__ __forceinline__ void ppo_grad_wide_tiles(const Args &g) {
         }
         if (tid < op) part[a.off_b[net][l] + tid] = db[l];
     }
-    if (tid >= 128 && tid < 128 + kPpoRowStats)
-        g.stat_slab[(static_cast<long long>(blockIdx.x) * 2 + net) * kPpoRowStats + tid - 128] = stat_acc;
+    ppo_store_stats(g, stat_acc);
 }
 
 }  // namespace ce
