@@ -67,6 +67,7 @@ EXPORTS = (
     'ce_vecnorm_set_state', 'ce_rollout_policy_vecnorm', 'ce_multi_rollout_policy_vecnorm',
     'ce_policy_wide_n_params', 'ce_policy_create_wide', 'ce_rng_normal_wide',
     'ce_ppo2_create_wide', 'ce_a2c_create_wide',
+    'ce_ddpg_n_params_wide', 'ce_ddpg_create_wide', 'ce_ddpg_act_rng_wide',
 )
 
 CE_FUNC_ROSENBROCK_PAIRS = 0
@@ -150,6 +151,14 @@ class CeDdpgConfig(ctypes.Structure):
         [('scale', ctypes.c_float * CE_DDPG_MAX_ACT)])
 
 
+CE_DDPG_WIDE_MAX_OBS, CE_DDPG_WIDE_MAX_ACT = 1024, 512
+
+
+class CeDdpgWideConfig(ctypes.Structure):
+    # ce_ddpg_config with scale [CE_DDPG_WIDE_MAX_ACT]
+    _fields_ = CeDdpgConfig._fields_[:-1] + [('scale', ctypes.c_float * CE_DDPG_WIDE_MAX_ACT)]
+
+
 CE_DDPG_NOISE_NORMAL, CE_DDPG_NOISE_OU = 0, 1
 
 
@@ -157,6 +166,12 @@ class CeDdpgNoise(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('theta', ctypes.c_double), ('dt', ctypes.c_double),
                 ('mean', ctypes.c_float * CE_DDPG_MAX_ACT),
                 ('sigma', ctypes.c_float * CE_DDPG_MAX_ACT)]
+
+
+class CeDdpgWideNoise(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('theta', ctypes.c_double), ('dt', ctypes.c_double),
+                ('mean', ctypes.c_float * CE_DDPG_WIDE_MAX_ACT),
+                ('sigma', ctypes.c_float * CE_DDPG_WIDE_MAX_ACT)]
 
 
 CE_MONITOR_MAX_INFO = 16
@@ -339,6 +354,11 @@ def _declare(lib):
         'ce_ddpg_partial': ([vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
         'ce_ddpg_combine': ([vp, i32, vp, i64, vp, vp, vp], ctypes.c_int),
         'ce_ddpg_apply': ([vp, i32, vp, i64, f64, f64, vp, vp], ctypes.c_int),
+        'ce_ddpg_n_params_wide': ([ctypes.POINTER(CeDdpgWideConfig)], ctypes.c_int),
+        'ce_ddpg_create_wide': ([ctypes.POINTER(CeDdpgWideConfig), ctypes.POINTER(vp)],
+                                ctypes.c_int),
+        'ce_ddpg_act_rng_wide': ([vp, vp, i64, u64, u32, u32, ctypes.POINTER(CeDdpgWideNoise), vp,
+                                  vp, vp, vp, vp], ctypes.c_int),
         'ce_monitor_record_bytes': ([i32], ctypes.c_int64),
         'ce_monitor_create': ([i32, i32, ctypes.POINTER(vp)], ctypes.c_int),
         'ce_monitor_destroy': ([vp], None),

@@ -68,7 +68,8 @@ propagate to the others).  The replicas stay bit-identical, so ``save`` works
 on any rank, and ``load`` followed by ``distribute`` at the same world
 continues bit for bit.
 
-``DDPG(ddpg.MlpPolicy, env, ...)`` is stable-baselines' cycle: per cycle one
+``DDPG(ddpg.MlpPolicy, env, ...)`` (``ddpg.WideMlpPolicy`` for an env past 128
+observations or 64 actions, up to 1024 -> 512) is stable-baselines' cycle: per cycle one
 ``env.collect_ddpg`` of ``nb_rollout_steps`` steps into the replay memory, the
 action noise (``ddpg.NormalActionNoise`` / ``ddpg.OrnsteinUhlenbeckActionNoise``)
 formed inside the act kernel, then one ``DDPGAgent.train`` call of
@@ -745,10 +746,12 @@ class DDPG(BaseAgent):
         if isinstance(env, VecNormalize):
             raise ValueError('DDPG on a VecNormalize env is not supported (collect_ddpg has no '
                              'normalised form)')
-        if policy is not ddpg.MlpPolicy and policy != 'MlpPolicy':
+        self.policy_kind = ddpg.policy_kind(policy)
+        if self.policy_kind is None:
             if getattr(policy, '__name__', policy) == 'LnMlpPolicy':
                 raise ValueError('layer_norm (LnMlpPolicy) is not supported')
-            raise ValueError('policy must be ddpg.MlpPolicy, got %r' % (policy,))
+            raise ValueError('policy must be ddpg.MlpPolicy or ddpg.WideMlpPolicy, got %r'
+                             % (policy,))
         given = dict(param_noise=param_noise, normalize_observations=normalize_observations,
                      normalize_returns=normalize_returns, enable_popart=enable_popart,
                      critic_l2_reg=critic_l2_reg, clip_norm=clip_norm, reward_scale=reward_scale,
@@ -792,9 +795,9 @@ class DDPG(BaseAgent):
         self.n_batch = s.rows * self.nb_rollout_steps        # timesteps per cycle
         self.num_timesteps = 0
         scale = 1.0 if s.low is None else np.abs(s.low)
-        self.agent = ddpg.DDPGAgent(s.obs_dim, s.act_dim, self.hidden, scale=scale, gamma=gamma,
-                                    tau=tau, actor_lr=actor_lr, critic_lr=critic_lr,
-                                    obs_range=observation_range, device=s.device)
+        self.agent = ddpg.AGENTS[self.policy_kind](
+            s.obs_dim, s.act_dim, self.hidden, scale=scale, gamma=gamma, tau=tau,
+            actor_lr=actor_lr, critic_lr=critic_lr, obs_range=observation_range, device=s.device)
         self.memory = ddpg.ReplayMemory(self.buffer_size, s.rows, s.obs_dim, s.act_dim,
                                         device=s.device)
         self.rng = DeviceRng(self.seed, s.device)
@@ -943,7 +946,8 @@ class DDPG(BaseAgent):
     # ------------------------------------------------------------ save / load
     def _meta(self):
         s = self.spec
-        return {'format': 1, 'algorithm': type(self).__name__, 'kwargs': self.kwargs,
+        return {'format': 1, 'algorithm': type(self).__name__, 'policy': self.policy_kind,
+                'kwargs': self.kwargs,
                 'action_noise': None if self.action_noise is None
                 else self.action_noise.describe(),
                 'rows': s.rows, 'obs_dim': s.obs_dim, 'act_dim': s.act_dim,
@@ -988,7 +992,7 @@ class DDPG(BaseAgent):
         data, meta, kwargs, env = cls._read(load_path, env, device, overrides)
         if 'action_noise' not in kwargs:
             kwargs['action_noise'] = ddpg.ActionNoise.from_description(meta.get('action_noise'))
-        model = cls(ddpg.MlpPolicy, env, **kwargs)
+        model = cls(meta.get('policy', 'MlpPolicy'), env, **kwargs)     # no kind: a narrow model
         s = model.spec
         if (s.obs_dim, s.act_dim, list(model.hidden)) != (meta['obs_dim'], meta['act_dim'],
                                                           meta['hidden']):

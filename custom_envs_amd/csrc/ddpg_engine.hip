@@ -17,15 +17,30 @@
 // the plain arguments precede the check of the handle, so they run without a
 // device.  Nothing is allocated on a call path (the targets y of a grad / step
 // call go into the caller's [n] buffer); status codes, never throws.
+//
+// A handle of ce_ddpg_create_wide is marked wide: its act, target and
+// gradient launches are ddpg_wide_kernels.h's (chosen in launch_act,
+// launch_act_rng, enqueue_target and enqueue_slab, nowhere else), and the
+// reduce, statistics, partial, combine, update and pack kernels serve it
+// unchanged: they work on the flat vector, the image and the slab through
+// DdpgPlan, whose members are sized by the layer count alone.  Two fixed-size
+// members cannot describe a wide shape and have wide twins here: the device
+// `scale` array (kDdpgMaxA floats; kDdpgWideMaxA on a wide handle) and the
+// by-value mean / sigma of DdpgActRng (2 x 64 floats; 2 x 512 would not go
+// through the kernel arguments, so a wide handle keeps them in device memory
+// and uploads them when a call's values differ from the previous call's).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "common.h"
 #include "ddpg_kernels.h"
+#include "ddpg_wide_kernels.h"
 #include "policy_engine.h"     // rng_replay_args_ok, rng_enqueue_replay
 
 struct ce_ddpg {
@@ -39,6 +54,12 @@ struct ce_ddpg {
     float *grad = nullptr, *slab = nullptr, *scale = nullptr;
     double *stat_slab = nullptr;
     float *d_flat = nullptr;     // staging of a host-pointer set_params
+    bool wide = false;           // ce_ddpg_create_wide's: the wide tile kernels
+    // wide only: the generated noise's [mean | sigma], 2 x kDdpgWideMaxA floats,
+    // on the device, and the values that were uploaded last
+    float *noise_dev = nullptr;
+    mutable std::vector<float> noise_host;
+    mutable bool noise_set = false;
 };
 
 namespace {
@@ -50,7 +71,8 @@ constexpr int64_t kMaxRows = int64_t(1) << 24;
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // shape limits and hyper-parameters (no HIP call); `who` prefixes the message
-int shape_ok(const char *who, const ce_ddpg_config *c) {
+int shape_ok(const char *who, const ce_ddpg_config *c, int max_d = ce::kDdpgMaxD,
+             int max_a = ce::kDdpgMaxA) {
     const std::string w(who);
     if (!c) return fail(CE_EINVAL, w + ": null config");
     if (c->abi_version != CE_ABI_VERSION) return fail(CE_EINVAL, w + ": ABI version mismatch");
@@ -59,12 +81,12 @@ int shape_ok(const char *who, const ce_ddpg_config *c) {
     if (c->n_hidden < 1 || c->n_hidden > ce::kDdpgMaxHidden)
         return fail(CE_EUNSUPPORTED, w + ": the DDPG networks take 1 or 2 hidden layers, got " +
                                          std::to_string(c->n_hidden));
-    if (c->obs_dim > ce::kDdpgMaxD)
+    if (c->obs_dim > max_d)
         return fail(CE_EUNSUPPORTED, w + ": obs_dim " + std::to_string(c->obs_dim) +
-                                         " exceeds the limit of 128");
-    if (c->act_dim > ce::kDdpgMaxA)
+                                         " exceeds the limit of " + std::to_string(max_d));
+    if (c->act_dim > max_a)
         return fail(CE_EUNSUPPORTED, w + ": act_dim " + std::to_string(c->act_dim) +
-                                         " exceeds the limit of 64");
+                                         " exceeds the limit of " + std::to_string(max_a));
     for (int l = 0; l < c->n_hidden; ++l)
         if (c->hidden[l] != 32 && c->hidden[l] != 64)
             return fail(CE_EUNSUPPORTED, w + ": hidden width " + std::to_string(c->hidden[l]) +
@@ -72,8 +94,10 @@ int shape_ok(const char *who, const ce_ddpg_config *c) {
     return CE_OK;
 }
 
-int config_ok(const char *who, const ce_ddpg_config *c) {
-    const int rc = shape_ok(who, c);
+// `scale`: the config's [act_dim] (the wide config's is longer than c->scale)
+int config_ok(const char *who, const ce_ddpg_config *c, const float *scale,
+              int max_d = ce::kDdpgMaxD, int max_a = ce::kDdpgMaxA) {
+    const int rc = shape_ok(who, c, max_d, max_a);
     if (rc != CE_OK) return rc;
     const std::string w(who);
     if (!(c->gamma >= 0.0 && c->gamma <= 1.0)) return fail(CE_EINVAL, w + ": gamma must be in [0, 1]");
@@ -86,8 +110,31 @@ int config_ok(const char *who, const ce_ddpg_config *c) {
     if (!(c->obs_lo < c->obs_hi)) return fail(CE_EINVAL, w + ": obs_lo must be below obs_hi");
     if (c->grid_limit < 0) return fail(CE_EINVAL, w + ": grid_limit must not be negative");
     for (int i = 0; i < c->act_dim; ++i)
-        if (!std::isfinite(c->scale[i])) return fail(CE_EINVAL, w + ": scale must be finite");
+        if (!std::isfinite(scale[i])) return fail(CE_EINVAL, w + ": scale must be finite");
     return CE_OK;
+}
+
+// the members a wide config shares with ce_ddpg_config (scale stays zero: a
+// wide handle reads the wide config's own array)
+ce_ddpg_config plain_config(const ce_ddpg_wide_config &w) {
+    ce_ddpg_config c{};
+    c.abi_version = w.abi_version;
+    c.device = w.device;
+    c.obs_dim = w.obs_dim;
+    c.act_dim = w.act_dim;
+    c.n_hidden = w.n_hidden;
+    for (int i = 0; i < 4; ++i) c.hidden[i] = w.hidden[i];
+    c.grid_limit = w.grid_limit;
+    c.gamma = w.gamma;
+    c.tau = w.tau;
+    c.actor_lr = w.actor_lr;
+    c.critic_lr = w.critic_lr;
+    c.beta1 = w.beta1;
+    c.beta2 = w.beta2;
+    c.eps = w.eps;
+    c.obs_lo = w.obs_lo;
+    c.obs_hi = w.obs_hi;
+    return c;
 }
 
 // the images' layout, the flat vector's segments and the LDS sizes
@@ -191,8 +238,12 @@ void enqueue_target(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, 
     g.dones = dones;
     g.y = y;
     const unsigned tiles = static_cast<unsigned>((n + ce::kDdpgTile - 1) / ce::kDdpgTile);
-    hipLaunchKernelGGL(ce::ddpg_target_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_grad,
-                       stream, g);
+    if (l->wide)
+        hipLaunchKernelGGL(ce::ddpg_target_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock),
+                           l->lds_grad, stream, g);
+    else
+        hipLaunchKernelGGL(ce::ddpg_target_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_grad,
+                           stream, g);
 }
 
 // [target, gradient] of this call's n rows with the row weight 1 / n_total
@@ -215,8 +266,12 @@ int enqueue_slab(const ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const 
     g.y = y;
     g.slab = l->slab;
     g.stat_slab = l->stat_slab;
-    hipLaunchKernelGGL(ce::ddpg_grad_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock), l->lds_grad,
-                       stream, g);
+    if (l->wide)
+        hipLaunchKernelGGL(ce::ddpg_grad_wide_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock),
+                           l->lds_grad, stream, g);
+    else
+        hipLaunchKernelGGL(ce::ddpg_grad_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock),
+                           l->lds_grad, stream, g);
     return g.grid;
 }
 
@@ -308,33 +363,47 @@ int ce_ddpg_n_params(const ce_ddpg_config *cfg) {
     return make_plan(*cfg).n_params;
 }
 
-int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out) {
-    if (!out) return fail(CE_EINVAL, "ce_ddpg_create: null output handle");
-    *out = nullptr;
-    const int rc = config_ok("ce_ddpg_create", cfg);
-    if (rc != CE_OK) return rc;
+// the handle of a checked config; `scale` [act_dim] is the config's own array
+static int ddpg_create(const ce_ddpg_config &cfg, const float *scale, bool wide, ce_ddpg **out) {
+    const std::string who = wide ? "ce_ddpg_create_wide" : "ce_ddpg_create";
     ce_ddpg *l = new (std::nothrow) ce_ddpg();
-    if (!l) return fail(CE_ENOMEM, "ce_ddpg_create: host allocation failed");
-    l->cfg = *cfg;
-    l->plan = make_plan(*cfg);
-    l->lds_grad = lds_bytes(l->plan, ce::kDdpgBufs);
-    l->lds_act = lds_bytes(l->plan, ce::kDdpgActBufs);
+    if (!l) return fail(CE_ENOMEM, who + ": host allocation failed");
+    l->cfg = cfg;
+    l->wide = wide;
+    l->plan = make_plan(cfg);
+    if (wide) {
+        l->lds_grad = l->lds_act = static_cast<size_t>(ce::ddpg_wide_lds_floats(cfg.act_dim)) * sizeof(float);
+        l->noise_host.assign(2 * ce::kDdpgWideMaxA, 0.0f);
+    } else {
+        l->lds_grad = lds_bytes(l->plan, ce::kDdpgBufs);
+        l->lds_act = lds_bytes(l->plan, ce::kDdpgActBufs);
+    }
     auto bail = [&](int code) {
         ce_ddpg_destroy(l);
         return code;
     };
     const ce::DdpgPlan &a = l->plan;
-    CE_TRY(hipSetDevice(cfg->device));
+    CE_TRY(hipSetDevice(cfg.device));
     hipDeviceProp_t prop;
-    CE_TRY(hipGetDeviceProperties(&prop, cfg->device));
-    l->grid_max = cfg->grid_limit > 0 ? cfg->grid_limit : std::max(1, prop.multiProcessorCount);
-    // the dynamic LDS of the three tile kernels, once, from the limits' need
-    for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_kernel),
-                          reinterpret_cast<const void *>(ce::ddpg_act_rng_kernel),
-                          reinterpret_cast<const void *>(ce::ddpg_target_kernel),
-                          reinterpret_cast<const void *>(ce::ddpg_grad_kernel)})
-        CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(ce::kDdpgMaxLdsBytes)));
+    CE_TRY(hipGetDeviceProperties(&prop, cfg.device));
+    const int cus = std::max(1, prop.multiProcessorCount);
+    l->grid_max = cfg.grid_limit > 0 ? cfg.grid_limit : (wide ? std::min(cus, ce::kDdpgWideGrid) : cus);
+    // the dynamic LDS of the tile kernels, once, from the limits' need
+    if (wide) {
+        for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_wide_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_act_rng_wide_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_target_wide_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_grad_wide_kernel)})
+            CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(ce::kDdpgWideMaxLdsBytes)));
+    } else {
+        for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_act_rng_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_target_kernel),
+                              reinterpret_cast<const void *>(ce::ddpg_grad_kernel)})
+            CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(ce::kDdpgMaxLdsBytes)));
+    }
     const size_t np = static_cast<size_t>(a.n_params) * sizeof(float);
     const size_t ni = static_cast<size_t>(a.img_floats) * sizeof(float);
     for (float **q : {&l->params, &l->target, &l->m, &l->v, &l->grad, &l->d_flat}) {
@@ -348,11 +417,43 @@ int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out) {
     CE_TRY(hipMalloc(&l->slab, static_cast<size_t>(l->grid_max) * ni));
     CE_TRY(hipMalloc(&l->stat_slab,
                      static_cast<size_t>(l->grid_max) * 2 * ce::kDdpgRowStats * sizeof(double)));
-    CE_TRY(hipMalloc(&l->scale, ce::kDdpgMaxA * sizeof(float)));
-    CE_TRY(hipMemcpy(l->scale, cfg->scale, ce::kDdpgMaxA * sizeof(float), hipMemcpyHostToDevice));
+    const size_t ns = (wide ? ce::kDdpgWideMaxA : ce::kDdpgMaxA) * sizeof(float);
+    CE_TRY(hipMalloc(&l->scale, ns));
+    CE_TRY(hipMemcpy(l->scale, scale, ns, hipMemcpyHostToDevice));
+    if (wide) {
+        CE_TRY(hipMalloc(&l->noise_dev, 2 * ce::kDdpgWideMaxA * sizeof(float)));
+        CE_TRY(hipMemset(l->noise_dev, 0, 2 * ce::kDdpgWideMaxA * sizeof(float)));
+    }
     CE_TRY(hipDeviceSynchronize());
     *out = l;
     return CE_OK;
+}
+
+int ce_ddpg_create(const ce_ddpg_config *cfg, ce_ddpg **out) {
+    if (!out) return fail(CE_EINVAL, "ce_ddpg_create: null output handle");
+    *out = nullptr;
+    const int rc = config_ok("ce_ddpg_create", cfg, cfg ? cfg->scale : nullptr);
+    if (rc != CE_OK) return rc;
+    return ddpg_create(*cfg, cfg->scale, false, out);
+}
+
+int ce_ddpg_n_params_wide(const ce_ddpg_wide_config *cfg) {
+    if (!cfg) return fail(CE_EINVAL, "ce_ddpg_n_params_wide: null config");
+    const ce_ddpg_config c = plain_config(*cfg);
+    const int rc = shape_ok("ce_ddpg_n_params_wide", &c, ce::kDdpgWideMaxD, ce::kDdpgWideMaxA);
+    if (rc != CE_OK) return rc;
+    return make_plan(c).n_params;
+}
+
+int ce_ddpg_create_wide(const ce_ddpg_wide_config *cfg, ce_ddpg **out) {
+    if (!out) return fail(CE_EINVAL, "ce_ddpg_create_wide: null output handle");
+    *out = nullptr;
+    if (!cfg) return fail(CE_EINVAL, "ce_ddpg_create_wide: null config");
+    const ce_ddpg_config c = plain_config(*cfg);
+    const int rc = config_ok("ce_ddpg_create_wide", &c, cfg->scale, ce::kDdpgWideMaxD,
+                             ce::kDdpgWideMaxA);
+    if (rc != CE_OK) return rc;
+    return ddpg_create(c, cfg->scale, true, out);
 }
 
 void ce_ddpg_destroy(ce_ddpg *l) {
@@ -362,7 +463,7 @@ void ce_ddpg_destroy(ce_ddpg *l) {
                     static_cast<void *>(l->img), static_cast<void *>(l->timg),
                     static_cast<void *>(l->grad), static_cast<void *>(l->slab),
                     static_cast<void *>(l->scale), static_cast<void *>(l->stat_slab),
-                    static_cast<void *>(l->d_flat)})
+                    static_cast<void *>(l->d_flat), static_cast<void *>(l->noise_dev)})
         if (q) (void)hipFree(q);
     delete l;
 }
@@ -424,16 +525,22 @@ int ce_ddpg_act(const ce_ddpg *l, const float *obs, const float *noise, int64_t 
     g.action = action;
     g.env_action = env_action;
     const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
-    hipLaunchKernelGGL(ce::ddpg_act_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
-                       static_cast<hipStream_t>(hip_stream), g);
+    if (l->wide)
+        hipLaunchKernelGGL(ce::ddpg_act_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
+                           static_cast<hipStream_t>(hip_stream), g);
+    else
+        hipLaunchKernelGGL(ce::ddpg_act_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
+                           static_cast<hipStream_t>(hip_stream), g);
     CE_HIP(hipGetLastError());
     return CE_OK;
 }
 
-int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
-                    uint32_t row0, const ce_ddpg_noise *noise, float *ou_state,
-                    const uint8_t *reset, float *action, float *env_action, void *hip_stream) {
-    const char *who = "ce_ddpg_act_rng";
+// ce_ddpg_act_rng and ce_ddpg_act_rng_wide: `mean` / `sigma` hold `cap` columns
+static int ddpg_act_rng(const char *who, const ce_ddpg *l, const float *obs, int64_t rows,
+                        uint64_t seed, uint32_t t, uint32_t row0, bool have_noise, int32_t kind,
+                        double theta, double dt, const float *mean, const float *sigma, int cap,
+                        float *ou_state, const uint8_t *reset, float *action, float *env_action,
+                        void *hip_stream) {
     const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
     if (rows < 1 || rows > kMaxRows)
         return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
@@ -442,19 +549,23 @@ int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t s
     if (!obs) return bad(": null obs");
     if (!action) return bad(": null action output");
     if (!env_action) return bad(": null env_action output");
-    if (!noise) return bad(": null noise description");
-    if (noise->kind != CE_DDPG_NOISE_NORMAL && noise->kind != CE_DDPG_NOISE_OU)
-        return bad(": unknown noise kind " + std::to_string(noise->kind));
-    const bool ou = noise->kind == CE_DDPG_NOISE_OU;
+    if (!have_noise) return bad(": null noise description");
+    if (kind != CE_DDPG_NOISE_NORMAL && kind != CE_DDPG_NOISE_OU)
+        return bad(": unknown noise kind " + std::to_string(kind));
+    const bool ou = kind == CE_DDPG_NOISE_OU;
     if (ou && !ou_state) return bad(": Ornstein-Uhlenbeck noise needs its state buffer");
-    if (ou && (!std::isfinite(noise->theta) || !std::isfinite(noise->dt) || !(noise->dt > 0.0)))
+    if (ou && (!std::isfinite(theta) || !std::isfinite(dt) || !(dt > 0.0)))
         return bad(": theta must be finite and dt positive");
     if (!l) return bad(": null learner");
-    for (int c = 0; c < l->plan.A; ++c)
-        if (!std::isfinite(noise->mean[c]) || !std::isfinite(noise->sigma[c]) ||
-            noise->sigma[c] < 0.0f)
+    const int A = l->plan.A;
+    if (A > cap)
+        return bad(": the agent has " + std::to_string(A) + " action columns and the noise " +
+                   "description " + std::to_string(cap) + ": use ce_ddpg_act_rng_wide");
+    for (int c = 0; c < A; ++c)
+        if (!std::isfinite(mean[c]) || !std::isfinite(sigma[c]) || sigma[c] < 0.0f)
             return bad(": mean must be finite and sigma finite and not negative");
     CE_CLEAR_STALE_ERROR_AT(who);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     ce::DdpgActArgs g{};
     g.p = l->plan;
     g.rows = static_cast<int>(rows);
@@ -463,30 +574,80 @@ int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t s
     g.obs = obs;
     g.action = action;
     g.env_action = env_action;
+    // OU: s = float32(sigma sqrt(dt)) formed in double
+    const auto held_sigma = [&](int c) {
+        return ou ? static_cast<float>(static_cast<double>(sigma[c]) * std::sqrt(dt)) : sigma[c];
+    };
+    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
+    if (l->wide) {
+        float held[2 * ce::kDdpgWideMaxA] = {};
+        for (int c = 0; c < A; ++c) {
+            held[c] = mean[c];
+            held[ce::kDdpgWideMaxA + c] = held_sigma(c);
+        }
+        if (!l->noise_set || std::memcmp(held, l->noise_host.data(), sizeof(held)) != 0) {
+            std::memcpy(l->noise_host.data(), held, sizeof(held));
+            CE_HIP(hipMemcpyAsync(l->noise_dev, l->noise_host.data(), sizeof(held),
+                                  hipMemcpyHostToDevice, stream));
+            CE_HIP(hipStreamSynchronize(stream));      // the host copy may change at the next call
+            l->noise_set = true;
+        }
+        ce::DdpgWideActRng n{};
+        n.seed_lo = static_cast<uint32_t>(seed);
+        n.seed_hi = static_cast<uint32_t>(seed >> 32);
+        n.t = t;
+        n.row0 = row0;
+        n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
+        n.theta = ou ? static_cast<float>(theta) : 0.0f;
+        n.dt = ou ? static_cast<float>(dt) : 0.0f;
+        n.ou = ou ? ou_state : nullptr;
+        n.reset = ou ? reset : nullptr;
+        n.mean = l->noise_dev;
+        n.sigma = l->noise_dev + ce::kDdpgWideMaxA;
+        // the tile's N(0,1) block is the plan's S region
+        hipLaunchKernelGGL(ce::ddpg_act_rng_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock),
+                           l->lds_act, stream, g, n);
+        CE_HIP(hipGetLastError());
+        return CE_OK;
+    }
     ce::DdpgActRng n{};
     n.seed_lo = static_cast<uint32_t>(seed);
     n.seed_hi = static_cast<uint32_t>(seed >> 32);
     n.t = t;
     n.row0 = row0;
     n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
-    n.theta = ou ? static_cast<float>(noise->theta) : 0.0f;
-    n.dt = ou ? static_cast<float>(noise->dt) : 0.0f;
+    n.theta = ou ? static_cast<float>(theta) : 0.0f;
+    n.dt = ou ? static_cast<float>(dt) : 0.0f;
     n.ou = ou ? ou_state : nullptr;
     n.reset = ou ? reset : nullptr;
-    for (int c = 0; c < l->plan.A; ++c) {
-        n.mean[c] = noise->mean[c];
-        n.sigma[c] = ou ? static_cast<float>(static_cast<double>(noise->sigma[c]) *
-                                             std::sqrt(noise->dt))
-                        : noise->sigma[c];
+    for (int c = 0; c < A; ++c) {
+        n.mean[c] = mean[c];
+        n.sigma[c] = held_sigma(c);
     }
-    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
     // + the tile's N(0,1) block [round4(A)][33] behind the row scalars
-    const size_t lds = l->lds_act + static_cast<size_t>(round_up(l->plan.A, 4)) * ce::kDdpgLd *
-                                        sizeof(float);
-    hipLaunchKernelGGL(ce::ddpg_act_rng_kernel, dim3(tiles), dim3(ce::kDdpgBlock), lds,
-                       static_cast<hipStream_t>(hip_stream), g, n);
+    const size_t lds = l->lds_act + static_cast<size_t>(round_up(A, 4)) * ce::kDdpgLd * sizeof(float);
+    hipLaunchKernelGGL(ce::ddpg_act_rng_kernel, dim3(tiles), dim3(ce::kDdpgBlock), lds, stream, g, n);
     CE_HIP(hipGetLastError());
     return CE_OK;
+}
+
+int ce_ddpg_act_rng(const ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
+                    uint32_t row0, const ce_ddpg_noise *noise, float *ou_state,
+                    const uint8_t *reset, float *action, float *env_action, void *hip_stream) {
+    return ddpg_act_rng("ce_ddpg_act_rng", l, obs, rows, seed, t, row0, noise != nullptr,
+                        noise ? noise->kind : 0, noise ? noise->theta : 0.0, noise ? noise->dt : 0.0,
+                        noise ? noise->mean : nullptr, noise ? noise->sigma : nullptr,
+                        ce::kDdpgMaxA, ou_state, reset, action, env_action, hip_stream);
+}
+
+int ce_ddpg_act_rng_wide(ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
+                         uint32_t row0, const ce_ddpg_wide_noise *noise, float *ou_state,
+                         const uint8_t *reset, float *action, float *env_action,
+                         void *hip_stream) {
+    return ddpg_act_rng("ce_ddpg_act_rng_wide", l, obs, rows, seed, t, row0, noise != nullptr,
+                        noise ? noise->kind : 0, noise ? noise->theta : 0.0, noise ? noise->dt : 0.0,
+                        noise ? noise->mean : nullptr, noise ? noise->sigma : nullptr,
+                        ce::kDdpgWideMaxA, ou_state, reset, action, env_action, hip_stream);
 }
 
 int ce_ddpg_target(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,

@@ -54,9 +54,14 @@ save.  ``agents.DDPG`` is the loop on top (``learn``, ``predict``, ``save``,
 auto-reset: at a done row ``obs1`` is the reset observation, and ``(1 - done)``
 masks it in ``y``.
 
-Limits: 1-2 hidden layers, each 32 or 64 wide (the widths may differ),
-obs_dim <= 128, act_dim <= 64.  Anything else raises ``NativeEngineError``
-(CE_EUNSUPPORTED); there is no eager fallback.
+Limits: 1-2 hidden layers, each 32 or 64 wide (the widths may differ);
+``DDPGAgent`` (``ddpg.MlpPolicy``) takes obs_dim <= 128 and act_dim <= 64,
+``WideDDPGAgent`` (``ddpg.WideMlpPolicy``) obs_dim <= 1024 and act_dim <= 512
+-- the reference's ``Optimize-v0`` is 981 -> 490 -- on tile kernels that walk
+the wide layers in chunks (csrc/ddpg_wide_kernels.h) and, at a shape both
+take, write the narrow agent's bits.  Anything else raises
+``NativeEngineError`` (CE_EUNSUPPORTED); there is no eager fallback.  A wide
+agent under a gradient exchange is tested at world 1 only.
 
 Out of scope: parameter noise and layer norm (``LnMlpPolicy``), observation
 and return normalisation, pop-art, ``critic_l2_reg``, ``clip_norm``, graph
@@ -82,7 +87,8 @@ import numpy as np
 
 from custom_envs_amd import _native, learner
 from custom_envs_amd import rng as _rng
-from custom_envs_amd._native import CeDdpgConfig, CeDdpgNoise, check
+from custom_envs_amd._native import (CeDdpgConfig, CeDdpgNoise, CeDdpgWideConfig, CeDdpgWideNoise,
+                                     check)
 from custom_envs_amd.learner import N_STATS
 from custom_envs_amd.policy import MlpPolicy as _DevicePolicy
 from custom_envs_amd.policy import dict_to_flat, flat_to_dict, layout_size
@@ -351,6 +357,23 @@ class MlpPolicy:
     (``ddpg.MlpPolicy``): the relu actor and critic of this module."""
 
 
+class WideMlpPolicy:
+    """``ddpg.MlpPolicy`` at wide shapes (obs_dim <= 1024, act_dim <= 512):
+    ``agents.DDPG`` builds a ``WideDDPGAgent``."""
+
+
+POLICY_KINDS = {'MlpPolicy': MlpPolicy, 'WideMlpPolicy': WideMlpPolicy}
+
+
+def policy_kind(policy):
+    """``'MlpPolicy'`` or ``'WideMlpPolicy'`` of a marker class or its name;
+    None for anything else."""
+    for kind, marker in POLICY_KINDS.items():
+        if policy is marker or (isinstance(policy, str) and policy == kind):
+            return kind
+    return None
+
+
 def _noise_params(mean, sigma, act_dim):
     """``mean`` and ``sigma`` as float32 ``[A]`` (a scalar broadcasts)."""
     out = []
@@ -412,14 +435,19 @@ class ActionNoise:
     def params(self, act_dim):
         return _noise_params(self.mean, self.sigma, act_dim)
 
-    def struct(self, act_dim):
-        """The ``ce_ddpg_noise`` of this object at ``act_dim`` (built once)."""
-        if self._struct is None or self._struct[0] != act_dim:
+    def struct(self, act_dim, wide=False):
+        """The ``ce_ddpg_noise`` (``wide``: the ``ce_ddpg_wide_noise``) of this
+        object at ``act_dim`` (built once)."""
+        if self._struct is None or self._struct[0] != (act_dim, wide):
             mean, sigma = self.params(act_dim)
-            c = CeDdpgNoise(kind=self.KIND, theta=float(self.theta), dt=float(self.dt))
+            c = (CeDdpgWideNoise if wide else CeDdpgNoise)(
+                kind=self.KIND, theta=float(self.theta), dt=float(self.dt))
+            if act_dim > len(c.mean):
+                raise ValueError('the noise description holds %d columns, act_dim is %d'
+                                 % (len(c.mean), act_dim))
             for i in range(act_dim):
                 c.mean[i], c.sigma[i] = float(mean[i]), float(sigma[i])
-            self._struct = (act_dim, c)
+            self._struct = ((act_dim, wide), c)
         return self._struct[1]
 
     def reset(self):
@@ -510,14 +538,14 @@ class OrnsteinUhlenbeckActionNoise(ActionNoise):
         self._pending = (x, dones)
 
 
-def check_generated_noise(noise, rows=None, act_dim=None):
+def check_generated_noise(noise, rows=None, act_dim=None, wide=False):
     """``noise=(action_noise, device_rng)``: the pair's form.  Returns it."""
     if not isinstance(noise, tuple) or len(noise) != 2 \
             or not isinstance(noise[0], ActionNoise) or not isinstance(noise[1], _rng.DeviceRng):
         raise ValueError('noise must be a float32 tensor, None or (ActionNoise, DeviceRng), got %r'
                          % (noise,))
     if act_dim is not None:
-        noise[0].struct(act_dim)         # validates the columns once, then cached
+        noise[0].struct(act_dim, wide)   # validates the columns once, then cached
     if rows is not None and noise[1].row_offset + rows > 2 ** 32:
         raise ValueError('rows row_offset .. row_offset + rows - 1 must stay below 2^32')
     return noise
@@ -563,6 +591,8 @@ class DDPGAgent:
     which needs no GPU.  ``scale`` (``[A]`` or a scalar): what the normalised
     action is multiplied by for the env, SB's ``abs(action_space.low)``.
     ``grid_limit`` 0 means one workgroup per CU per branch."""
+    MAX_OBS, MAX_ACT = 128, _native.CE_DDPG_MAX_ACT
+    WIDE = False                 # the wide create entry, config and noise structs
 
     def __init__(self, obs_dim, act_dim, hidden=(64, 64), scale=1.0, gamma=0.99, tau=0.001,
                  actor_lr=1e-4, critic_lr=1e-3, obs_range=(-5.0, 5.0), beta1=0.9, beta2=0.999,
@@ -573,15 +603,17 @@ class DDPGAgent:
         self.device = 0 if device is None else int(device)
         if not 1 <= len(self.hidden) <= 2:
             raise _native.NativeEngineError('the DDPG networks take 1 or 2 hidden layers')
-        if not 1 <= self.act_dim <= 64:
-            raise _native.NativeEngineError('act_dim must be in [1, 64], got %d' % self.act_dim)
+        if not 1 <= self.act_dim <= self.MAX_ACT:
+            raise _native.NativeEngineError('act_dim must be in [1, %d], got %d'
+                                            % (self.MAX_ACT, self.act_dim))
         self.gamma, self.tau = float(gamma), float(tau)
         self.actor_lr, self.critic_lr = float(actor_lr), float(critic_lr)
         self.obs_range = (float(obs_range[0]), float(obs_range[1]))
         self.hp = HyperParams(self.gamma, *self.obs_range)
         self.scale = np.ascontiguousarray(
             np.broadcast_to(np.asarray(scale, np.float32), (self.act_dim,)))
-        self._cfg = cfg = CeDdpgConfig(
+        suffix = '_wide' if self.WIDE else ''
+        self._cfg = cfg = (CeDdpgWideConfig if self.WIDE else CeDdpgConfig)(
             abi_version=_native.ABI_VERSION, device=self.device, obs_dim=self.obs_dim,
             act_dim=self.act_dim, n_hidden=len(self.hidden), grid_limit=int(grid_limit),
             gamma=self.gamma, tau=self.tau, actor_lr=self.actor_lr, critic_lr=self.critic_lr,
@@ -591,9 +623,9 @@ class DDPGAgent:
             cfg.hidden[i] = h
         for i, s in enumerate(self.scale):
             cfg.scale[i] = float(s)
-        n = lib.ce_ddpg_n_params(ctypes.byref(cfg))
+        n = getattr(lib, 'ce_ddpg_n_params' + suffix)(ctypes.byref(cfg))
         if n < 0:
-            check(n, 'ce_ddpg_n_params')
+            check(n, 'ce_ddpg_n_params' + suffix)
         self.n_params = int(n)
         self.n_actor = n_actor_params(self.obs_dim, self.act_dim, self.hidden)
         self._lib, self._h = lib, None
@@ -605,7 +637,8 @@ class DDPGAgent:
                               'v': np.zeros(self.n_params, np.float32), 'step': 0}
             return
         handle = ctypes.c_void_p()
-        check(lib.ce_ddpg_create(ctypes.byref(cfg), ctypes.byref(handle)), 'ce_ddpg_create')
+        check(getattr(lib, 'ce_ddpg_create' + suffix)(ctypes.byref(cfg), ctypes.byref(handle)),
+              'ce_ddpg_create' + suffix)
         self._h = handle
 
     _stream = staticmethod(_DevicePolicy._stream)
@@ -707,7 +740,7 @@ class DDPGAgent:
         check_tensor('obs', obs, torch.float32, (max(rows, 1), self.obs_dim))
         generated = isinstance(noise, tuple)
         if generated:
-            check_generated_noise(noise, max(rows, 1), self.act_dim)
+            check_generated_noise(noise, max(rows, 1), self.act_dim, self.WIDE)
         elif noise is not None:
             check_tensor('noise', noise, torch.float32, (rows, self.act_dim))
         if out is not None:
@@ -768,8 +801,9 @@ class DDPGAgent:
         if out is None:
             out = {n: torch.empty((rows, self.act_dim), dtype=torch.float32, device=obs.device)
                    for n in ('action', 'env_action')}
-        self._call('act_rng', self._h, obs.data_ptr(), rows, gen.seed, t, gen.row_offset,
-                   ctypes.byref(action_noise.struct(self.act_dim)), state_ptr, reset_ptr,
+        self._call('act_rng_wide' if self.WIDE else 'act_rng', self._h, obs.data_ptr(), rows,
+                   gen.seed, t, gen.row_offset,
+                   ctypes.byref(action_noise.struct(self.act_dim, self.WIDE)), state_ptr, reset_ptr,
                    out['action'].data_ptr(), out['env_action'].data_ptr(), self._stream(stream))
         return out
 
@@ -1090,6 +1124,19 @@ class DDPGAgent:
             self.close()
         except Exception:
             pass
+
+
+class WideDDPGAgent(DDPGAgent):
+    """``DDPGAgent`` at obs_dim <= 1024 and act_dim <= 512, through
+    ``ce_ddpg_create_wide``: the act, target and gradient kernels walk the wide
+    layers in chunks (csrc/ddpg_wide_kernels.h); every other entry and kernel
+    is the narrow agent's.  ``grid_limit`` 0 means at most 64 workgroups per
+    branch (a gradient partial is about 0.8 MB at 981 -> 490)."""
+    MAX_OBS, MAX_ACT = _native.CE_DDPG_WIDE_MAX_OBS, _native.CE_DDPG_WIDE_MAX_ACT
+    WIDE = True
+
+
+AGENTS = {'MlpPolicy': DDPGAgent, 'WideMlpPolicy': WideDDPGAgent}
 
 
 # ---------------------------------------------------------------------- memory

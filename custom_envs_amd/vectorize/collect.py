@@ -113,7 +113,7 @@ def check_collect_ddpg(agent, memory, n_steps, noise, rows, obs_dim, act_dim):
         raise ValueError('n_steps must be >= 1, got %d' % k)
     if isinstance(noise, tuple):
         from custom_envs_amd.ddpg import check_generated_noise
-        check_generated_noise(noise, rows, act_dim)
+        check_generated_noise(noise, rows, act_dim, agent.WIDE)
         noise[1].check_draws(k)
     elif noise is not None:
         if not hasattr(noise, 'dim') or noise.dim() != 3 or noise.shape[0] < k:

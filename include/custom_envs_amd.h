@@ -907,6 +907,53 @@ int ce_ddpg_combine(ce_ddpg *l, int32_t world, const double *records, int64_t n_
 int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_total,
                   double actor_lr, double critic_lr, float *stats, void *hip_stream);
 
+/* The wide DDPG agent: the same learner at obs_dim <= 1024, act_dim <= 512
+ * (1..2 hidden layers of 32 or 64 units), on tile kernels that walk the wide
+ * layers in chunks (csrc/ddpg_wide_kernels.h); the reference's Optimize-v0
+ * spec is 981 -> 490.  ce_ddpg_create_wide returns a ce_ddpg marked wide, and
+ * every other ce_ddpg_* entry takes it as it is; ce_ddpg_act_rng reads 64
+ * columns of noise, so a handle with act_dim > 64 takes its generated noise
+ * through ce_ddpg_act_rng_wide (which serves any handle).  grid_limit 0: at
+ * most 64 workgroups per branch.  CE_EUNSUPPORTED past the limits, before any
+ * HIP call.  ce_ddpg_create keeps its own limits (128, 64). */
+#define CE_DDPG_WIDE_MAX_OBS 1024
+#define CE_DDPG_WIDE_MAX_ACT 512
+typedef struct ce_ddpg_wide_config {
+    int32_t abi_version; /* CE_ABI_VERSION                                   */
+    int32_t device;      /* HIP device ordinal                               */
+    int32_t obs_dim;     /* D <= 1024                                        */
+    int32_t act_dim;     /* A <= 512                                         */
+    int32_t n_hidden;    /* hidden layers per network, 1..2                  */
+    int32_t hidden[4];   /* their widths (32 or 64)                          */
+    int32_t grid_limit;  /* workgroups per branch of the gradient; 0: <= 64  */
+    double gamma;
+    double tau;
+    double actor_lr;
+    double critic_lr;
+    double beta1;
+    double beta2;
+    double eps;
+    double obs_lo;
+    double obs_hi;
+    float scale[CE_DDPG_WIDE_MAX_ACT]; /* env_action = action * scale, [A]   */
+} ce_ddpg_wide_config;
+typedef struct ce_ddpg_wide_noise {
+    int32_t kind;        /* CE_DDPG_NOISE_*                                  */
+    double theta;
+    double dt;
+    float mean[CE_DDPG_WIDE_MAX_ACT];  /* [A]                                */
+    float sigma[CE_DDPG_WIDE_MAX_ACT]; /* [A], >= 0                          */
+} ce_ddpg_wide_noise;
+/* Host-only, as ce_ddpg_n_params. */
+int ce_ddpg_n_params_wide(const ce_ddpg_wide_config *cfg);
+int ce_ddpg_create_wide(const ce_ddpg_wide_config *cfg, ce_ddpg **out);
+/* ce_ddpg_act_rng with up to 512 columns of noise.  The columns' mean and
+ * sigma are kept in the handle's device memory: a call whose values differ
+ * from the previous call's uploads them and synchronises the stream once. */
+int ce_ddpg_act_rng_wide(ce_ddpg *l, const float *obs, int64_t rows, uint64_t seed, uint32_t t,
+                         uint32_t row0, const ce_ddpg_wide_noise *noise, float *ou_state,
+                         const uint8_t *reset, float *action, float *env_action, void *hip_stream);
+
 /* The episode monitor on the device: utils_logging.VecMonitor's bookkeeping
  * (custom_envs/utils/utils_logging.py:98-116 per env) over K-step rollout
  * records where the rollout left them.  The carry -- per env ep_reward

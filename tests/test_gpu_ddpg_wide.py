@@ -1,0 +1,623 @@
+"""The wide DDPG agent on the device (``ce_ddpg_create_wide``,
+csrc/ddpg_wide_kernels.h) against the NumPy statements of
+custom_envs_amd/ddpg.py in float64, and against the narrow agent bit for bit.
+
+Every bound is ``max(1e-5, 2 e32)`` per array, ``e32`` the error of the float32
+statement in the kernels' order (``ddpg_wide_cases``), computed by NumPy alone.
+
+1.  ``act``, ``target`` and gradient parity at the seven cases.
+2.  The narrow agent's bits at ``ddpg_cases.CASES[2:6]``: ``act``, ``y``, every
+    gradient block and every statistic.
+3.  An ``idx`` subset is bit-equal to the gathered copy; the same call twice is
+    bit-identical; a partial never shows what an earlier call with another
+    batch left (grid_limit 1 and 2).
+4.  grid_limit 1 / 2 / 0 agree within the bound at the 97-row case.
+5.  Three ``step`` calls at stable-baselines' rates follow ``train_step_numpy``
+    at the reference's shape.
+6.  Generated Normal and Ornstein-Uhlenbeck noise are bit-equal to the explicit
+    instance fed the statement's numbers.
+7.  ``train`` is bit-equal to the same ``sample`` + ``step`` calls.
+8.  The closed loop at 981 -> 490 on a small engine: ``collect_ddpg`` fills the
+    ring with what ``step_device`` and ``act`` give one by one, and collect ->
+    sample -> step -> collect replays bit-identically.
+9.  ``agents.DDPG(ddpg.WideMlpPolicy, env)``: ``learn`` equals the hand-written
+    loop, ``save`` -> ``load`` -> ``learn`` continues a run, ``predict``.
+10. The gradient exchange at world 1 leaves the bits of ``step``.
+"""
+import numpy as np
+import pytest
+
+import ddpg_cases as dc
+import ddpg_wide_cases as wc
+from custom_envs_amd import ddpg, rng
+from custom_envs_amd.agents import DDPG
+from custom_envs_amd.ddpg import DDPGAgent, ReplayMemory, WideDDPGAgent
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = wc.FIELDS
+SEED = (7 << 32) | 123
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _need_gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a ROCm device')
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _cuda(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _dev(inputs):
+    return {n: _cuda(inputs[n]) for n in FIELDS}
+
+
+def _scale(A):
+    return (0.5 + np.arange(A) / 7.0).astype(np.float32)
+
+
+def _agent(case, inputs, cls=WideDDPGAgent, grid_limit=None, **over):
+    _, D, hidden, A, limit = case
+    agent = cls(D, A, hidden, scale=_scale(A),
+                grid_limit=limit if grid_limit is None else grid_limit, **over)
+    agent.set_params(inputs['params'])
+    agent.set_params(inputs['target_params'], target_only=True)
+    return agent
+
+
+def _assert_within(errs, bounds, e32, what):
+    for name, err in errs.items():
+        print('%s %-16s kernel %.3g  e32 %.3g  bound %.3g' % (what, name, err, e32[name], bounds[name]))
+    for name, err in errs.items():
+        assert err <= bounds[name], (what, name, err, bounds[name])
+
+
+# --------------------------------------------------------------- 1. parity
+@pytest.mark.parametrize('case', wc.CASES, ids=wc.case_id)
+def test_act_target_and_gradient_parity(case):
+    import torch
+    inputs, ref = wc.draw_case(case), wc.reference(case)
+    agent = _agent(case, inputs)
+    N, D, hidden, A, _ = case
+    assert np.array_equal(agent.get_params(), inputs['params'])
+    assert np.array_equal(agent.get_params(target=True), inputs['target_params'])
+    obs, batch = _cuda(inputs['obs0']), _dev(inputs)
+    # one guard row behind the outputs: the kernel's tile is 32 rows
+    buf = {n: torch.full((N + 1, A), 777.0, dtype=torch.float32, device='cuda')
+           for n in ('action', 'env_action')}
+    out = agent.act(obs, out={n: v[:N] for n, v in buf.items()})
+    act = _np(out['action'])
+    assert np.abs(act).max() <= 1.0
+    assert np.array_equal(_np(out['env_action']), act * _scale(A)[None, :])
+    for v in buf.values():
+        assert np.all(_np(v[N]) == 777.0)
+    noise = np.random.RandomState(7).normal(0, 0.4, (N, A)).astype(np.float32)
+    noisy = _np(agent.act(obs, _cuda(noise))['action'])
+    ref_noisy = ddpg.actor_numpy(inputs['params'], inputs['obs0'], noise, hidden)
+    y = _np(agent.target(batch))
+    done = inputs['dones'] != 0
+    assert np.array_equal(y[done], inputs['rewards'][done])
+    idx = np.random.RandomState(3).randint(0, N, 2 * N + 3).astype(np.int32)
+    yi = _np(agent.target(batch, _cuda(idx)))
+    grad, stats = agent.grad(batch)
+    grad = _np(grad)
+    assert np.abs(grad[:agent.n_actor]).max() > 0 and np.abs(grad[agent.n_actor:]).max() > 0
+    host = _np(stats.tensor)
+    assert host[4] == 0.0 and host[5] == 0.0
+    errs = {'act': dc.rel_err(act, ref['act']), 'y': dc.rel_err(y, ref['y'])}
+    errs.update(wc.gradient_errs(case, grad, stats.stats()))
+    _assert_within(errs, ref['bound'], ref['e32'], wc.case_id(case))
+    assert dc.rel_err(noisy, ref_noisy) <= ref['bound']['act']
+    assert dc.rel_err(yi, ref['y'][idx]) <= ref['bound']['y']
+    agent.close()
+
+
+# ------------------------------------------------- 2. the narrow agent's bits
+@pytest.mark.parametrize('case', wc.NARROW_CASES, ids=str)
+def test_the_narrow_agents_bits(case):
+    inputs = dc.draw_case(case)
+    N, D, hidden, A, _ = case
+    wide, narrow = _agent(case, inputs), _agent(case, inputs, cls=DDPGAgent)
+    obs, batch = _cuda(inputs['obs0']), _dev(inputs)
+    noise = _cuda(np.random.RandomState(7).normal(0, 0.4, (N, A)).astype(np.float32))
+    for nz in (None, noise):
+        a, b = wide.act(obs, nz), narrow.act(obs, nz)
+        assert _same(_np(a['action']), _np(b['action']))
+        assert _same(_np(a['env_action']), _np(b['env_action']))
+    idx = _cuda(np.random.RandomState(3).randint(0, N, N + 5).astype(np.int32))
+    for ix in (None, idx):
+        assert _same(_np(wide.target(batch, ix)), _np(narrow.target(batch, ix)))
+        gw, sw = wide.grad(batch, ix)
+        gn, sn = narrow.grad(batch, ix)
+        layout = wide.params_layout()
+        gw, gn = _np(gw), _np(gn)
+        for name, (off, shape) in layout.items():
+            n = int(np.prod(shape))
+            assert _same(gw[off:off + n], gn[off:off + n]), name
+        assert _same(_np(sw.tensor), _np(sn.tensor))
+        assert _same(_np(sw.y), _np(sn.y))
+    # and a step leaves the same parameters, targets and moments
+    wide.step(batch)
+    narrow.step(batch)
+    assert _same(wide.get_params(), narrow.get_params())
+    assert _same(wide.get_params(target=True), narrow.get_params(target=True))
+    assert _same(wide.get_opt_state()['v'], narrow.get_opt_state()['v'])
+    wide.close()
+    narrow.close()
+
+
+# ------------------------------------------ 3. idx, determinism, a clean partial
+def test_idx_subset_is_bit_equal_to_the_gathered_copy():
+    case = wc.CASES[3]
+    inputs = wc.draw_case(case)
+    agent = _agent(case, inputs)
+    N = case[0]
+    idx = np.random.RandomState(5).permutation(N)[:41].astype(np.int32)
+    batch = _dev(inputs)
+    g_idx, s_idx = agent.grad(batch, _cuda(idx))
+    y_idx = agent.target(batch, _cuda(idx))
+    gathered = {n: _cuda(inputs[n][idx]) for n in FIELDS}
+    g_cp, s_cp = agent.grad(gathered)
+    assert _same(_np(g_idx), _np(g_cp))
+    assert _same(_np(s_idx.tensor), _np(s_cp.tensor))
+    assert _same(_np(y_idx), _np(agent.target(gathered)))
+    # out-of-range indices are clamped, never read out of bounds
+    wild, clamped = idx.copy(), idx.copy()
+    wild[0], wild[1] = -5, N + 100
+    clamped[0], clamped[1] = 0, N - 1
+    assert _same(_np(agent.grad(batch, _cuda(wild))[0]), _np(agent.grad(batch, _cuda(clamped))[0]))
+    agent.close()
+
+
+def test_same_call_twice_is_bit_identical():
+    case = wc.REFERENCE_SHAPE
+    inputs = wc.draw_case(case)
+    agent = _agent(case, inputs)
+    batch = _dev(inputs)
+    g0, s0 = agent.grad(batch)
+    g1, s1 = agent.grad(batch)
+    assert _same(_np(g0), _np(g1)) and _same(_np(s0.tensor), _np(s1.tensor))
+    agent.close()
+
+
+@pytest.mark.parametrize('grid_limit', [1, 2])
+def test_a_partial_never_shows_an_earlier_call(grid_limit):
+    """The dW blocks live in the slab between tiles: a call after another
+    batch (more rows, other values) gives the bits of a fresh agent's call."""
+    case = wc.ROWS97
+    inputs = wc.draw_case(case)
+    batch = _dev(inputs)
+    small = _cuda(np.arange(33, dtype=np.int32))
+    fresh = _agent(case, inputs, grid_limit=grid_limit)
+    want_g, want_s = fresh.grad(batch, small)
+    used = _agent(case, inputs, grid_limit=grid_limit)
+    other = {n: (v * 3 if v.dtype.is_floating_point else v) for n, v in batch.items()}
+    used.grad(other)
+    got_g, got_s = used.grad(batch, small)
+    assert _same(_np(got_g), _np(want_g)) and _same(_np(got_s.tensor), _np(want_s.tensor))
+    fresh.close()
+    used.close()
+
+
+# --------------------------------------------------------- 4. grid independence
+@pytest.mark.parametrize('grid_limit', [1, 2, 0])
+def test_grid_independence(grid_limit):
+    case = wc.ROWS97
+    inputs, ref = wc.draw_case(case), wc.reference(case)
+    agent = _agent(case, inputs, grid_limit=grid_limit)
+    grad, stats = agent.grad(_dev(inputs))
+    errs = wc.gradient_errs(case, _np(grad), stats.stats())
+    _assert_within(errs, ref['bound'], ref['e32'], 'grid %d' % grid_limit)
+    agent.close()
+
+
+# ----------------------------------------------------------------- 5. step
+def test_three_steps_against_the_statement():
+    case = wc.REFERENCE_SHAPE
+    inputs = wc.draw_case(case)
+    N, D, hidden, A, _ = case
+    hyper = dict(tau=0.01, actor_lr=1e-4, critic_lr=1e-3)
+    agent = _agent(case, inputs, **hyper)
+    batch, host = _dev(inputs), wc.batch_of(inputs)
+    p = inputs['params'].astype(np.float64)
+    tp = inputs['target_params'].astype(np.float64)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    p32, tp32 = inputs['params'].copy(), inputs['target_params'].copy()
+    m32, v32 = np.zeros_like(p32), np.zeros_like(p32)
+    for t in (1, 2, 3):
+        before_t = agent.get_params(target=True)
+        stats = agent.step(batch)
+        p, tp, m, v, ref_stats = ddpg.train_step_numpy(p, tp, m, v, t, host, agent.n_actor,
+                                                       hp=wc.HP, hidden=hidden, **hyper)
+        p32, tp32, m32, v32, s32 = wc.train_step_ordered_f32(
+            p32, tp32, m32, v32, t, host, agent.n_actor, A, hidden, **hyper)
+        assert p32.dtype == np.float32 and tp32.dtype == np.float32
+        got_p, got_t = agent.get_params(), agent.get_params(target=True)
+        e32 = {'params': dc.rel_err(p32, p), 'targets': dc.rel_err(tp32, tp)}
+        e32.update(wc.stat_errs(s32, ref_stats))
+        errs = {'params': dc.rel_err(got_p, p), 'targets': dc.rel_err(got_t, tp)}
+        got_stats = stats.stats()
+        errs.update({n: abs(got_stats[n] - float(ref_stats[n])) / abs(float(ref_stats[n]))
+                     for n in ddpg.STAT_NAMES})
+        _assert_within(errs, {k: wc.bound(e32[k]) for k in errs}, e32, 'step %d' % t)
+        assert _same(got_t, ddpg.soft_update_numpy(before_t, got_p, hyper['tau']))
+    # the images follow: act uses the new parameters
+    act = _np(agent.act(_cuda(inputs['obs0']))['action'])
+    bound = wc.reference(case)['bound']['act']
+    assert dc.rel_err(act, ddpg.actor_numpy(got_p, inputs['obs0'], hidden=hidden)) <= bound
+    agent.close()
+
+
+# ------------------------------------------------------- 6. generated noise
+def _columns(A):
+    return (np.linspace(-0.1, 0.1, A).astype(np.float32),
+            np.linspace(0.05, 0.4, A).astype(np.float32))
+
+
+def _device_z(g, N, A, t):
+    """The generator's float32 N(0,1) block ``[N][A]`` of ``ACTION_NOISE`` at
+    draw ``t``.  ``DeviceRng.normal`` serves 64 columns under that purpose, so
+    the block is read off an agent with all-zero parameters: its action is
+    ``0 + (0 + 2^-4 z)``, every step exact, hence ``z = 16 action``.  Held here
+    to ``DeviceRng.normal``'s bits on the first 64 columns and to the float64
+    statement of the stream everywhere."""
+    import torch
+    probe = WideDDPGAgent(4, A, (32,))
+    sixteenth = ddpg.NormalActionNoise(np.zeros(A), np.full(A, 2.0 ** -4))
+    out = probe.act(torch.zeros((N, 4), device='cuda'), noise=(sixteenth, g), t=t)
+    z = _np(out['action']) * np.float32(16)
+    probe.close()
+    head = min(A, 64)
+    assert _same(z[:, :head], _np(g.normal(1, N, head, purpose=rng.ACTION_NOISE, t=t)[0]))
+    z64 = rng.normal_numpy(g.seed, t, N, A, g.row_offset, np.float64, rng.ACTION_NOISE)
+    assert np.abs(z).max() < 16 and dc.rel_err(z, z64) <= wc.FLOOR
+    return z
+
+
+@pytest.mark.parametrize('case', [wc.REFERENCE_SHAPE, wc.CASES[0]], ids=wc.case_id)
+def test_generated_noise_is_bit_equal_to_the_explicit_instance(case):
+    import torch
+    inputs = wc.draw_case(case)
+    agent = _agent(case, inputs)
+    N, D, hidden, A, _ = case
+    obs = _cuda(inputs['obs0'])
+    mean, sigma = _columns(A)
+    f = np.float32
+    row0 = 1000
+    g = rng.DeviceRng(SEED, 0, row_offset=row0)
+    # Normal
+    normal = ddpg.NormalActionNoise(mean, sigma)
+    for t in (0, 7):
+        z = _device_z(g, N, A, t)
+        want = agent.act(obs, _cuda(ddpg.normal_noise_numpy(mean, sigma, z, f)))
+        buf = {n: torch.full((N + 1, A), 777.0, dtype=torch.float32, device='cuda')
+               for n in ('action', 'env_action')}
+        got = agent.act(obs, noise=(normal, g), t=t, out={n: v[:N] for n, v in buf.items()})
+        for name in ('action', 'env_action'):
+            assert _same(_np(got[name]), _np(want[name])), ('normal', t, name)
+            assert np.all(_np(buf[name][N]) == 777.0)
+        assert not _same(_np(got['action']), _np(agent.act(obs)['action']))
+    # Ornstein-Uhlenbeck over three draws, the second with restarted rows
+    ou = ddpg.OrnsteinUhlenbeckActionNoise(mean, sigma, theta=0.15, dt=1e-2)
+    mask = (np.arange(N) % 3 == 1).astype(np.uint8)
+    x = np.zeros((N, A), f)
+    for j, t in enumerate((5, 6, 7)):
+        z = _device_z(g, N, A, t)
+        reset = mask if j == 1 else None
+        x = ddpg.ou_noise_numpy(x, mean, sigma, z, 0.15, 1e-2, reset, f)
+        assert x.dtype == f
+        want = agent.act(obs, _cuda(x))
+        got = agent.act(obs, noise=(ou, g), t=t, reset=None if reset is None else _cuda(reset))
+        for name in ('action', 'env_action'):
+            assert _same(_np(got[name]), _np(want[name])), ('ou', t, name)
+        assert _same(_np(ou.state), x), t
+    # the noise columns change between calls: the upload follows
+    other = ddpg.NormalActionNoise(mean, 2 * sigma)
+    z = _device_z(g, N, A, 0)
+    want = agent.act(obs, _cuda(ddpg.normal_noise_numpy(mean, 2 * sigma, z, f)))
+    assert _same(_np(agent.act(obs, noise=(other, g), t=0)['action']), _np(want['action']))
+    agent.close()
+
+
+# ------------------------------------------------------------------- 7. train
+def _filled_memory(D, A, rows=8, steps=8):
+    import torch
+    rs = np.random.RandomState(100)
+    mem = ReplayMemory(rows * steps, rows, D, A)
+    C = mem.capacity
+    mem.obs0.copy_(_cuda((2 * rs.normal(0, 1, (C, D))).astype(np.float32)))
+    mem.obs1.copy_(_cuda((2 * rs.normal(0, 1, (C, D))).astype(np.float32)))
+    mem.actions.copy_(_cuda(np.clip(rs.normal(0, 0.5, (C, A)), -1, 1).astype(np.float32)))
+    mem.rewards.copy_(_cuda(rs.normal(0, 1, C).astype(np.float32)))
+    mem.dones.copy_(_cuda((rs.uniform(0, 1, C) < 0.2).astype(np.uint8)))
+    for _ in range(steps):
+        mem.advance()
+    torch.cuda.synchronize()
+    return mem
+
+
+def _agent_state(agent):
+    opt = agent.get_opt_state()
+    return {'params': agent.get_params(), 'target': agent.get_params(target=True),
+            'm': opt['m'], 'v': opt['v'], 'step': np.array(opt['step'])}
+
+
+def _assert_same_state(a, b, what=''):
+    for key in a:
+        assert _same(a[key], b[key]), (what, key)
+
+
+def test_train_equals_step_calls():
+    import torch
+    case = wc.REFERENCE_SHAPE
+    inputs = wc.draw_case(case)
+    _, D, hidden, A, _ = case
+    mem = _filled_memory(D, A)
+    one, many = _agent(case, inputs, tau=0.01), _agent(case, inputs, tau=0.01)
+    g_one, g_many = rng.DeviceRng(SEED, 0), rng.DeviceRng(SEED, 0)
+    g_one.replay_t = g_many.replay_t = 3
+    stats = one.train(mem, 3, 40, g_one)
+    idx = g_many.replay_indices(3, 40, mem.size)
+    rows = [many.step(mem.as_batch(), idx[s]) for s in range(3)]
+    torch.cuda.synchronize()
+    _assert_same_state(_agent_state(one), _agent_state(many))
+    assert not _same(one.get_params(), inputs['params'])
+    for s in range(3):
+        assert _same(_np(stats[s]), _np(rows[s].tensor)), s
+    assert g_one.replay_t == 6 and one.get_opt_state()['step'] == 3
+    one.close()
+    many.close()
+
+
+# ------------------------------------------------------------ 8. closed loop
+def _env():
+    from custom_envs_amd.vectorize.gpuvecenv import GPUVecEnv
+    env = GPUVecEnv(wc.ENVS, data_set=wc.dataset(), max_steps=4, seed=list(wc.ENV_SEEDS),
+                    precision='f64')
+    assert env.engine.obs_dim == wc.OBS_DIM == 981 and env.engine.act_dim == wc.ACT_DIM == 490
+    return env
+
+
+def _twin():
+    from custom_envs_amd.engine import OptimizeEngine
+    features, targets = wc.dataset()
+    eng = OptimizeEngine(features, targets, num_envs=wc.ENVS, batch_size=None, max_steps=4,
+                         precision='f64')
+    eng.seed(list(wc.ENV_SEEDS))
+    return eng
+
+
+def _loop_agent(seed=0):
+    rs = np.random.RandomState(900 + seed)
+    agent = WideDDPGAgent(wc.OBS_DIM, wc.ACT_DIM, wc.HIDDEN, scale=0.01, tau=0.01)
+    agent.set_params(ddpg.dict_to_flat(dc.draw_params(rs, wc.OBS_DIM, wc.ACT_DIM, wc.HIDDEN),
+                                       agent.params_layout()))
+    return agent
+
+
+def test_collect_ddpg_fills_the_ring():
+    env, twin, agent = _env(), _twin(), _loop_agent()
+    rows, D, A, K, cap_steps = wc.ENVS, wc.OBS_DIM, wc.ACT_DIM, wc.ROLLOUT_K, 6
+    memory = ReplayMemory(cap_steps * rows, rows, D, A)
+    noise = _cuda(np.random.RandomState(12).normal(0, 0.3, (K, rows, A)).astype(np.float32))
+    first = np.asarray(env.reset(), np.float32)
+    out = twin.alloc_device_outputs()
+    twin.reset_device(out)
+    twin.wait()
+    assert np.array_equal(_np(out['obs']), first)
+    prev_obs, t, any_done = first, 0, False
+    for k_call in (K // 2, K - K // 2):
+        result = env.collect_ddpg(agent, memory, k_call, noise[t:t + k_call])
+        for j in range(k_call):
+            slot = slice(((t + j) % cap_steps) * rows, ((t + j) % cap_steps + 1) * rows)
+            obs0 = memory.obs0[slot]
+            assert np.array_equal(_np(obs0), prev_obs), (t + j, 'obs0')
+            again = agent.act(obs0, noise[t + j])
+            assert _same(_np(memory.actions[slot]), _np(again['action']))
+            assert _same(_np(result['env_actions'][j]), _np(again['env_action']))
+            twin.step_device(result['env_actions'][j].contiguous(), out)
+            twin.wait()
+            assert _same(_np(memory.obs1[slot]), _np(out['obs'])), (t + j, 'obs1')
+            assert _same(_np(memory.rewards[slot]), _np(out['reward']))
+            assert _same(_np(memory.dones[slot]), _np(out['done']))
+            any_done = any_done or bool(_np(out['done']).any())
+            prev_obs = _np(out['obs'])
+        t += k_call
+        assert np.array_equal(_np(result['last_obs']), prev_obs)
+    assert any_done and memory.size == cap_steps * rows
+    env.close()
+    twin.close()
+    agent.close()
+
+
+def _training_run():
+    import torch
+    env, agent = _env(), _loop_agent(seed=1)
+    rows = wc.ENVS
+    memory = ReplayMemory(8 * rows, rows, wc.OBS_DIM, wc.ACT_DIM)
+    gen = torch.Generator(device='cuda').manual_seed(17)
+    noise = _cuda(np.random.RandomState(13).normal(0, 0.3, (8, rows, wc.ACT_DIM)).astype(np.float32))
+    env.reset()
+    stats = []
+    env.collect_ddpg(agent, memory, 4, noise[:4])
+    stats.append(_np(agent.step(memory.as_batch(), memory.sample(40, generator=gen)).tensor))
+    env.collect_ddpg(agent, memory, 4, noise[4:])
+    stats.append(_np(agent.step(memory.as_batch(), memory.sample(40, generator=gen)).tensor))
+    out = [agent.get_params(), agent.get_params(target=True)] + stats
+    out += [_np(getattr(memory, n)) for n in FIELDS]
+    env.close()
+    agent.close()
+    return out
+
+
+def test_collect_sample_step_collect_replays_bit_identically():
+    first, second = _training_run(), _training_run()
+    for a, b in zip(first, second):
+        assert np.all(np.isfinite(a.astype(np.float64)))
+        assert _same(a, b)
+    assert not _same(first[0], first[1])          # the targets trail the parameters
+    assert first[2][6] > 0 and first[2][7] > 0
+
+
+# ------------------------------------------------------------ 9. agents.DDPG
+ROLLOUT, TRAIN, BATCH = 4, 2, 16
+
+
+def _noise(kind, A):
+    if kind == 'normal':
+        return ddpg.NormalActionNoise(np.zeros(A), 0.2 * np.ones(A))
+    return ddpg.OrnsteinUhlenbeckActionNoise(np.zeros(A), 0.3 * np.ones(A))
+
+
+def _model(env, noise, policy=ddpg.WideMlpPolicy):
+    kw = dict(gamma=0.9, nb_rollout_steps=ROLLOUT, nb_train_steps=TRAIN, batch_size=BATCH,
+              buffer_size=2 * ROLLOUT * wc.ENVS, action_noise=_noise(noise, wc.ACT_DIM), tau=0.01,
+              actor_lr=1e-3, critic_lr=1e-2, seed=SEED)
+    return DDPG(policy, env, **kw)
+
+
+def _model_state(model):
+    import torch
+    torch.cuda.synchronize()
+    out = _agent_state(model.agent)
+    mem = model.memory
+    for name in mem.FIELDS:
+        out['mem_' + name] = _np(getattr(mem, name))
+    out['mem'] = np.array([mem.size, mem.pos])
+    g = model.rng.state()
+    out['rng'] = np.array([g[k] for k in sorted(g)], np.uint64)
+    ou = getattr(model.action_noise, 'state', None)
+    if ou is not None:
+        out['ou'], out['ou_dones'] = _np(ou), _np(model.action_noise.last_dones)
+    return out
+
+
+def _learned(noise_kind, cycles=3):
+    env = _env()
+    model = _model(env, noise_kind)
+    assert type(model.agent) is WideDDPGAgent and model.policy_kind == 'WideMlpPolicy'
+    model.learn(cycles * model.n_batch)
+    state = _model_state(model)
+    env.close()
+    model.agent.close()
+    return state
+
+
+@pytest.mark.parametrize('noise_kind', ['normal', 'ou'])
+def test_learn_equals_the_hand_written_loop(noise_kind):
+    from custom_envs_amd.agents import env_spec
+    learned = _learned(noise_kind)
+    env = _env()
+    s = env_spec(env)
+    agent = WideDDPGAgent(s.obs_dim, s.act_dim, (64, 64), scale=np.abs(s.low), gamma=0.9, tau=0.01,
+                          actor_lr=1e-3, critic_lr=1e-2)
+    agent.set_params(ddpg.init_params_numpy(s.obs_dim, s.act_dim, (64, 64), SEED & 0xffffffff))
+    memory = ReplayMemory(2 * ROLLOUT * s.rows, s.rows, s.obs_dim, s.act_dim)
+    g = rng.DeviceRng(SEED, 0)
+    noise = _noise(noise_kind, s.act_dim)
+    env.reset()
+    for cycle in range(3):
+        env.collect_ddpg(agent, memory, ROLLOUT, noise=(noise, g))
+        if memory.size >= BATCH:
+            agent.train(memory, TRAIN, BATCH, g)
+    hand = _agent_state(agent)
+    for name in memory.FIELDS:
+        hand['mem_' + name] = _np(getattr(memory, name))
+    for key, value in hand.items():
+        assert _same(learned[key], value), key
+    assert not _same(hand['params'], ddpg.init_params_numpy(s.obs_dim, s.act_dim, (64, 64),
+                                                            SEED & 0xffffffff))
+    assert learned['mem'].tolist() == [memory.size, memory.pos]
+    state = g.state()
+    assert learned['rng'].tolist() == [state[k] for k in sorted(state)]
+    if noise_kind == 'ou':
+        assert _same(learned['ou'], _np(noise.state))
+    env.close()
+    agent.close()
+
+
+@pytest.mark.parametrize('memory', [True, False])
+def test_resume_through_save_and_load(tmp_path, memory):
+    env = _env()
+    model = _model(env, 'ou')
+    model.learn(2 * model.n_batch)
+    path = str(tmp_path / 'ddpg')
+    model.save(path, memory=memory)
+    model.agent.close()
+    back = DDPG.load(path, env=env)
+    assert type(back.agent) is WideDDPGAgent and back.policy_kind == 'WideMlpPolicy'
+    assert back.num_timesteps == 2 * back.n_batch
+    # 12 records a cycle: the first cycle cannot fill a batch of 16 and trains nothing
+    assert back.get_opt_state()['step'] == TRAIN and back.rng.replay_t == TRAIN
+    if memory:          # the whole run, continued bit for bit
+        assert back.memory.size == back.memory.capacity
+        back.learn(back.n_batch, reset_num_timesteps=False)
+        whole, resumed = _learned('ou'), _model_state(back)
+        for key in whole:
+            assert _same(whole[key], resumed[key]), key
+    else:               # the memory starts empty and the model still learns
+        assert (back.memory.size, back.memory.pos) == (0, 0)
+        before = back.get_parameters()
+        back.learn(2 * back.n_batch, reset_num_timesteps=False)
+        after = back.get_parameters()
+        assert np.all(np.isfinite(after)) and not _same(before, after)
+    env.close()
+    back.agent.close()
+
+
+def test_predict():
+    env = _env()
+    model = _model(env, 'normal')
+    s = model.spec
+    obs = (3 * np.random.RandomState(5).normal(0, 1, (5, s.obs_dim))).astype(np.float32)
+    scale = np.abs(s.low)
+    params = model.get_parameters()
+    want = ddpg.actor_numpy(params, obs, None, (64, 64)) * scale[None, :]
+    e32 = dc.rel_err(wc.actor_ordered_f32(params, obs, s.act_dim, (64, 64)) * scale[None, :], want)
+    got, state = model.predict(obs)
+    assert state is None and isinstance(got, np.ndarray) and got.shape == (5, s.act_dim)
+    print('predict err %.3g e32 %.3g' % (dc.rel_err(got, want), e32))
+    assert dc.rel_err(got, want) <= wc.bound(e32)
+    one, _ = model.predict(obs[2])
+    assert one.shape == (s.act_dim,) and np.array_equal(one, got[2])
+    before = model.rng.state()
+    a, _ = model.predict(obs, deterministic=False)
+    b, _ = model.predict(obs, deterministic=False)
+    assert not np.array_equal(a, b) and not np.array_equal(a, got)
+    assert model.rng.state()['predict_t'] == before['predict_t'] + 2
+    z = rng.normal_numpy(SEED, before['predict_t'], 5, s.act_dim, 0, np.float64, rng.PREDICT)
+    ref = ddpg.actor_numpy(params, obs, model.action_noise.noise_numpy(z), (64, 64)) * scale[None, :]
+    assert dc.rel_err(a, ref) <= wc.bound(e32)
+    env.close()
+    model.agent.close()
+
+
+# ---------------------------------------------------- 10. the exchange, world 1
+def test_the_exchange_at_world_one_leaves_the_bits_of_step():
+    from custom_envs_amd.distributed import GradientExchange
+    case = wc.REFERENCE_SHAPE
+    inputs = wc.draw_case(case)
+    batch = _dev(inputs)
+    plain, shared, by_hand = (_agent(case, inputs) for _ in range(3))
+    want = plain.step(batch)
+    records = by_hand.partial(batch)[None]
+    got_hand = by_hand.apply(records, case[0])
+    GradientExchange(shared, 0, 1)
+    got = shared.step(batch)
+    for agent, stats in ((by_hand, got_hand), (shared, got)):
+        _assert_same_state(_agent_state(plain), _agent_state(agent))
+        assert _same(_np(stats.tensor), _np(want.tensor))
+    for agent in (plain, shared, by_hand):
+        agent.close()
