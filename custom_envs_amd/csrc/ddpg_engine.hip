@@ -18,17 +18,22 @@
 // device.  Nothing is allocated on a call path (the targets y of a grad / step
 // call go into the caller's [n] buffer); status codes, never throws.
 //
-// A handle of ce_ddpg_create_wide is marked wide: its act, target and
-// gradient launches are ddpg_wide_kernels.h's (chosen in launch_act,
-// launch_act_rng, enqueue_target and enqueue_slab, nowhere else), and the
-// reduce, statistics, partial, combine, update and pack kernels serve it
-// unchanged: they work on the flat vector, the image and the slab through
-// DdpgPlan, whose members are sized by the layer count alone.  Two fixed-size
-// members cannot describe a wide shape and have wide twins here: the device
-// `scale` array (kDdpgMaxA floats; kDdpgWideMaxA on a wide handle) and the
-// by-value mean / sigma of DdpgActRng (2 x 64 floats; 2 x 512 would not go
-// through the kernel arguments, so a wide handle keeps them in device memory
-// and uploads them when a call's values differ from the previous call's).
+// The checks DDPG shares with the PPO2 and A2C learners (rows, a partial's
+// record, the gathered records, the parameter vector, Adam's blocks) are
+// learner_checks.h's: one text per refusal.
+//
+// A handle's kind is chosen once: ddpg_create fills the handle's DdpgKind
+// (ddpg_kind) from ce_ddpg_create or ce_ddpg_create_wide, and every launch of
+// an act, target or gradient kernel goes through that table; a wide handle's
+// entries are ddpg_wide_kernels.h's.  The reduce, statistics, partial, combine,
+// update and pack kernels serve both kinds unchanged: they work on the flat
+// vector, the image and the slab through DdpgPlan, whose members are sized by
+// the layer count alone.  Two fixed-size members cannot describe a wide shape
+// and have wide twins: the device `scale` array (the table's scale_cap floats)
+// and the by-value mean / sigma of DdpgActRng (2 x 64 floats; 2 x 512 would
+// not go through the kernel arguments, so a wide handle keeps them in device
+// memory and uploads them when a call's values differ from the previous
+// call's).  That last difference is what ddpg_act_rng still asks the kind for.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,20 +46,33 @@
 #include "common.h"
 #include "ddpg_kernels.h"
 #include "ddpg_wide_kernels.h"
+#include "learner_checks.h"
 #include "policy_engine.h"     // rng_replay_args_ok, rng_enqueue_replay
+
+// What a handle's kind decides (ddpg_kind): the tile kernels and their sizes.
+struct DdpgKind {
+    bool wide = false;           // ce_ddpg_create_wide's
+    void (*act)(ce::DdpgActArgs) = nullptr;
+    void (*target)(ce::DdpgTargetArgs) = nullptr;
+    void (*grad)(ce::DdpgGradArgs) = nullptr;
+    const void *act_rng = nullptr;      // its second argument differs: launch_act_rng
+    size_t lds_grad = 0, lds_act = 0;
+    int max_lds_bytes = 0;       // the four kernels' dynamic-LDS limit
+    int grid_default = 0;        // workgroups per branch at grid_limit 0 (0: one per CU)
+    int scale_cap = 0;           // floats of the device `scale` array
+};
 
 struct ce_ddpg {
     ce_ddpg_config cfg{};
     ce::DdpgPlan plan{};
+    DdpgKind kind{};
     int grid_max = 0;            // workgroups per branch the slab holds
     long long t = 0;             // Adam's step count, shared by both blocks
-    size_t lds_grad = 0, lds_act = 0;
     float *params = nullptr, *target = nullptr, *m = nullptr, *v = nullptr;
     float *img = nullptr, *timg = nullptr;
     float *grad = nullptr, *slab = nullptr, *scale = nullptr;
     double *stat_slab = nullptr;
     float *d_flat = nullptr;     // staging of a host-pointer set_params
-    bool wide = false;           // ce_ddpg_create_wide's: the wide tile kernels
     // wide only: the generated noise's [mean | sigma], 2 x kDdpgWideMaxA floats,
     // on the device, and the values that were uploaded last
     float *noise_dev = nullptr;
@@ -65,8 +83,6 @@ struct ce_ddpg {
 namespace {
 
 using ce::fail;
-
-constexpr int64_t kMaxRows = int64_t(1) << 24;
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -188,29 +204,84 @@ size_t lds_bytes(const ce::DdpgPlan &a, int bufs) {
            sizeof(float);
 }
 
-int params_ok(const char *who, const ce_ddpg *l, const void *flat, int64_t n, const char *got) {
-    if (!flat) return fail(CE_EINVAL, std::string(who) + ": null parameter vector");
-    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
-    if (n != l->plan.n_params)
-        return fail(CE_EINVAL, std::string(who) + got + std::to_string(n) +
-                                   " parameters, the agent has " + std::to_string(l->plan.n_params));
-    return CE_OK;
+// the table of a handle's kind: the one place where it is chosen
+DdpgKind ddpg_kind(bool wide, const ce::DdpgPlan &a) {
+    DdpgKind k{};
+    k.wide = wide;
+    if (wide) {
+        k.act = ce::ddpg_act_wide_kernel;
+        k.act_rng = reinterpret_cast<const void *>(ce::ddpg_act_rng_wide_kernel);
+        k.target = ce::ddpg_target_wide_kernel;
+        k.grad = ce::ddpg_grad_wide_kernel;
+        k.lds_grad = k.lds_act = static_cast<size_t>(ce::ddpg_wide_lds_floats(a.A)) * sizeof(float);
+        k.max_lds_bytes = ce::kDdpgWideMaxLdsBytes;
+        k.grid_default = ce::kDdpgWideGrid;
+        k.scale_cap = ce::kDdpgWideMaxA;
+    } else {
+        k.act = ce::ddpg_act_kernel;
+        k.act_rng = reinterpret_cast<const void *>(ce::ddpg_act_rng_kernel);
+        k.target = ce::ddpg_target_kernel;
+        k.grad = ce::ddpg_grad_kernel;
+        k.lds_grad = lds_bytes(a, ce::kDdpgBufs);
+        k.lds_act = lds_bytes(a, ce::kDdpgActBufs);
+        k.max_lds_bytes = ce::kDdpgMaxLdsBytes;
+        k.scale_cap = ce::kDdpgMaxA;
+    }
+    return k;
 }
 
-// n rows gathered by idx (null: the first n) out of an m-row batch
-int rows_ok(const char *who, int64_t n, int64_t m, const int32_t *idx) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (n < 1) return bad(": n must be at least 1, got " + std::to_string(n));
-    if (m < 1 || m > kMaxRows) return bad(": m must be in [1, 2^24], got " + std::to_string(m));
-    if (n > kMaxRows) return bad(": n must be at most 2^24");
-    if (!idx && n > m) return bad(": n exceeds m and there is no idx to gather by");
-    return CE_OK;
+int n_params_of(const ce_ddpg *l) { return l ? l->plan.n_params : -1; }
+
+unsigned tiles_of(int64_t rows) {
+    return static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
+}
+
+ce::DdpgActArgs act_args(const ce_ddpg *l, const float *obs, const float *noise, int64_t rows,
+                         float *action, float *env_action) {
+    ce::DdpgActArgs g{};
+    g.p = l->plan;
+    g.rows = static_cast<int>(rows);
+    g.img = l->img;
+    g.scale = l->scale;
+    g.obs = obs;
+    g.noise = noise;
+    g.action = action;
+    g.env_action = env_action;
+    return g;
+}
+
+// what DdpgActRng and DdpgWideActRng share; mean and sigma are the caller's
+template <class Rng>
+Rng act_rng_args(uint64_t seed, uint32_t t, uint32_t row0, bool ou, double theta, double dt,
+                 float *ou_state, const uint8_t *reset) {
+    Rng n{};
+    n.seed_lo = static_cast<uint32_t>(seed);
+    n.seed_hi = static_cast<uint32_t>(seed >> 32);
+    n.t = t;
+    n.row0 = row0;
+    n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
+    n.theta = ou ? static_cast<float>(theta) : 0.0f;
+    n.dt = ou ? static_cast<float>(dt) : 0.0f;
+    n.ou = ou ? ou_state : nullptr;
+    n.reset = ou ? reset : nullptr;
+    return n;
+}
+
+// the generated-noise act kernel of the handle's kind, `noise_lds` bytes for
+// the tile's N(0,1) block on top of the act kernel's
+template <class Rng>
+void launch_act_rng(const ce_ddpg *l, const ce::DdpgActArgs &g, const Rng &n, size_t noise_lds,
+                    hipStream_t stream) {
+    const auto kernel = reinterpret_cast<void (*)(ce::DdpgActArgs, Rng)>(
+        const_cast<void *>(l->kind.act_rng));
+    hipLaunchKernelGGL(kernel, dim3(tiles_of(g.rows)), dim3(ce::kDdpgBlock),
+                       l->kind.lds_act + noise_lds, stream, g, n);
 }
 
 int batch_ok(const char *who, const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx,
              const float *obs0, const float *actions, const float *rewards, const float *obs1,
              const uint8_t *dones, const float *y, const float *stats) {
-    const int rc = rows_ok(who, n, m, idx);
+    const int rc = ce::learner_rows_ok(who, n, m, idx);
     if (rc != CE_OK) return rc;
     const auto null = [who](const char *what) { return fail(CE_EINVAL, std::string(who) + ": null " + what); };
     if (!obs0) return null("obs0");
@@ -237,13 +308,8 @@ void enqueue_target(const ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, 
     g.rewards = rewards;
     g.dones = dones;
     g.y = y;
-    const unsigned tiles = static_cast<unsigned>((n + ce::kDdpgTile - 1) / ce::kDdpgTile);
-    if (l->wide)
-        hipLaunchKernelGGL(ce::ddpg_target_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock),
-                           l->lds_grad, stream, g);
-    else
-        hipLaunchKernelGGL(ce::ddpg_target_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_grad,
-                           stream, g);
+    hipLaunchKernelGGL(l->kind.target, dim3(tiles_of(n)), dim3(ce::kDdpgBlock), l->kind.lds_grad,
+                       stream, g);
 }
 
 // [target, gradient] of this call's n rows with the row weight 1 / n_total
@@ -266,12 +332,8 @@ int enqueue_slab(const ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const 
     g.y = y;
     g.slab = l->slab;
     g.stat_slab = l->stat_slab;
-    if (l->wide)
-        hipLaunchKernelGGL(ce::ddpg_grad_wide_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock),
-                           l->lds_grad, stream, g);
-    else
-        hipLaunchKernelGGL(ce::ddpg_grad_kernel, dim3(g.grid, 2), dim3(ce::kDdpgBlock),
-                           l->lds_grad, stream, g);
+    hipLaunchKernelGGL(l->kind.grad, dim3(g.grid, 2), dim3(ce::kDdpgBlock), l->kind.lds_grad,
+                       stream, g);
     return g.grid;
 }
 
@@ -305,24 +367,6 @@ void enqueue_combine(const ce_ddpg *l, int32_t world, const double *records, int
     hipLaunchKernelGGL(ce::ddpg_stats_kernel, dim3(1), dim3(256), 0, stream,
                        static_cast<int>(n_total), world, q.record_doubles, np, l->plan.n_actor,
                        records + np, grad, stats);
-}
-
-constexpr int64_t kMaxTotalRows = int64_t(1) << 30;
-constexpr int kMaxWorld = 1 << 16;
-
-// world, the gathered records, n_total and stats of an apply / combine call
-int records_ok(const char *who, const ce_ddpg *l, int32_t world, const double *records,
-               int64_t n_total, const float *stats) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (world < 1 || world > kMaxWorld)
-        return bad(": world must be in [1, 2^16], got " + std::to_string(world));
-    if (n_total < 1 || n_total > kMaxTotalRows)
-        return bad(": n_total must be in [1, 2^30], got " + std::to_string(n_total));
-    if (!records) return bad(": null records");
-    if (reinterpret_cast<uintptr_t>(records) & 7) return bad(": the records must be 8-byte aligned");
-    if (!stats) return bad(": null stats");
-    if (!l) return bad(": null learner");
-    return CE_OK;
 }
 
 // [update] from l->grad: Adam on both blocks, one more step; soft update; images.
@@ -369,15 +413,10 @@ static int ddpg_create(const ce_ddpg_config &cfg, const float *scale, bool wide,
     ce_ddpg *l = new (std::nothrow) ce_ddpg();
     if (!l) return fail(CE_ENOMEM, who + ": host allocation failed");
     l->cfg = cfg;
-    l->wide = wide;
     l->plan = make_plan(cfg);
-    if (wide) {
-        l->lds_grad = l->lds_act = static_cast<size_t>(ce::ddpg_wide_lds_floats(cfg.act_dim)) * sizeof(float);
-        l->noise_host.assign(2 * ce::kDdpgWideMaxA, 0.0f);
-    } else {
-        l->lds_grad = lds_bytes(l->plan, ce::kDdpgBufs);
-        l->lds_act = lds_bytes(l->plan, ce::kDdpgActBufs);
-    }
+    l->kind = ddpg_kind(wide, l->plan);
+    const DdpgKind &k = l->kind;
+    if (wide) l->noise_host.assign(2 * ce::kDdpgWideMaxA, 0.0f);
     auto bail = [&](int code) {
         ce_ddpg_destroy(l);
         return code;
@@ -387,23 +426,13 @@ static int ddpg_create(const ce_ddpg_config &cfg, const float *scale, bool wide,
     hipDeviceProp_t prop;
     CE_TRY(hipGetDeviceProperties(&prop, cfg.device));
     const int cus = std::max(1, prop.multiProcessorCount);
-    l->grid_max = cfg.grid_limit > 0 ? cfg.grid_limit : (wide ? std::min(cus, ce::kDdpgWideGrid) : cus);
+    l->grid_max = cfg.grid_limit > 0 ? cfg.grid_limit
+                                     : (k.grid_default > 0 ? std::min(cus, k.grid_default) : cus);
     // the dynamic LDS of the tile kernels, once, from the limits' need
-    if (wide) {
-        for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_wide_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_act_rng_wide_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_target_wide_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_grad_wide_kernel)})
-            CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(ce::kDdpgWideMaxLdsBytes)));
-    } else {
-        for (const void *k : {reinterpret_cast<const void *>(ce::ddpg_act_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_act_rng_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_target_kernel),
-                              reinterpret_cast<const void *>(ce::ddpg_grad_kernel)})
-            CE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(ce::kDdpgMaxLdsBytes)));
-    }
+    for (const void *f : {reinterpret_cast<const void *>(k.act), k.act_rng,
+                          reinterpret_cast<const void *>(k.target),
+                          reinterpret_cast<const void *>(k.grad)})
+        CE_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, k.max_lds_bytes));
     const size_t np = static_cast<size_t>(a.n_params) * sizeof(float);
     const size_t ni = static_cast<size_t>(a.img_floats) * sizeof(float);
     for (float **q : {&l->params, &l->target, &l->m, &l->v, &l->grad, &l->d_flat}) {
@@ -417,7 +446,7 @@ static int ddpg_create(const ce_ddpg_config &cfg, const float *scale, bool wide,
     CE_TRY(hipMalloc(&l->slab, static_cast<size_t>(l->grid_max) * ni));
     CE_TRY(hipMalloc(&l->stat_slab,
                      static_cast<size_t>(l->grid_max) * 2 * ce::kDdpgRowStats * sizeof(double)));
-    const size_t ns = (wide ? ce::kDdpgWideMaxA : ce::kDdpgMaxA) * sizeof(float);
+    const size_t ns = static_cast<size_t>(k.scale_cap) * sizeof(float);
     CE_TRY(hipMalloc(&l->scale, ns));
     CE_TRY(hipMemcpy(l->scale, scale, ns, hipMemcpyHostToDevice));
     if (wide) {
@@ -470,7 +499,7 @@ void ce_ddpg_destroy(ce_ddpg *l) {
 
 int ce_ddpg_set_params(ce_ddpg *l, const float *flat, int64_t n, uint32_t flags, void *hip_stream) {
     const char *who = "ce_ddpg_set_params";
-    const int rc = params_ok(who, l, flat, n, ": got ");
+    const int rc = ce::learner_params_ok(who, n_params_of(l), "agent", flat, n, ": got ");
     if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -492,7 +521,8 @@ int ce_ddpg_set_params(ce_ddpg *l, const float *flat, int64_t n, uint32_t flags,
 
 int ce_ddpg_get_params(ce_ddpg *l, float *flat, int64_t n, uint32_t flags, void *hip_stream) {
     const char *who = "ce_ddpg_get_params";
-    const int rc = params_ok(who, l, flat, n, ": got room for ");
+    const int rc =
+        ce::learner_params_ok(who, n_params_of(l), "agent", flat, n, ": got room for ");
     if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -508,29 +538,16 @@ int ce_ddpg_act(const ce_ddpg *l, const float *obs, const float *noise, int64_t 
                 float *action, float *env_action, void *hip_stream) {
     const char *who = "ce_ddpg_act";
     const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (rows < 1 || rows > kMaxRows)
+    if (rows < 1 || rows > ce::kLearnerMaxRows)
         return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
     if (!obs) return bad(": null obs");
     if (!action) return bad(": null action output");
     if (!env_action) return bad(": null env_action output");
     if (!l) return bad(": null learner");
     CE_CLEAR_STALE_ERROR_AT(who);
-    ce::DdpgActArgs g{};
-    g.p = l->plan;
-    g.rows = static_cast<int>(rows);
-    g.img = l->img;
-    g.scale = l->scale;
-    g.obs = obs;
-    g.noise = noise;
-    g.action = action;
-    g.env_action = env_action;
-    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
-    if (l->wide)
-        hipLaunchKernelGGL(ce::ddpg_act_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
-                           static_cast<hipStream_t>(hip_stream), g);
-    else
-        hipLaunchKernelGGL(ce::ddpg_act_kernel, dim3(tiles), dim3(ce::kDdpgBlock), l->lds_act,
-                           static_cast<hipStream_t>(hip_stream), g);
+    hipLaunchKernelGGL(l->kind.act, dim3(tiles_of(rows)), dim3(ce::kDdpgBlock), l->kind.lds_act,
+                       static_cast<hipStream_t>(hip_stream),
+                       act_args(l, obs, noise, rows, action, env_action));
     CE_HIP(hipGetLastError());
     return CE_OK;
 }
@@ -542,7 +559,7 @@ static int ddpg_act_rng(const char *who, const ce_ddpg *l, const float *obs, int
                         float *ou_state, const uint8_t *reset, float *action, float *env_action,
                         void *hip_stream) {
     const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (rows < 1 || rows > kMaxRows)
+    if (rows < 1 || rows > ce::kLearnerMaxRows)
         return bad(": rows must be in [1, 2^24], got " + std::to_string(rows));
     if (static_cast<uint64_t>(row0) + static_cast<uint64_t>(rows) > (uint64_t(1) << 32))
         return bad(": rows row0 .. row0 + rows - 1 must stay below 2^32");
@@ -566,20 +583,12 @@ static int ddpg_act_rng(const char *who, const ce_ddpg *l, const float *obs, int
             return bad(": mean must be finite and sigma finite and not negative");
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    ce::DdpgActArgs g{};
-    g.p = l->plan;
-    g.rows = static_cast<int>(rows);
-    g.img = l->img;
-    g.scale = l->scale;
-    g.obs = obs;
-    g.action = action;
-    g.env_action = env_action;
+    const ce::DdpgActArgs g = act_args(l, obs, nullptr, rows, action, env_action);
     // OU: s = float32(sigma sqrt(dt)) formed in double
     const auto held_sigma = [&](int c) {
         return ou ? static_cast<float>(static_cast<double>(sigma[c]) * std::sqrt(dt)) : sigma[c];
     };
-    const unsigned tiles = static_cast<unsigned>((rows + ce::kDdpgTile - 1) / ce::kDdpgTile);
-    if (l->wide) {
+    if (l->kind.wide) {
         float held[2 * ce::kDdpgWideMaxA] = {};
         for (int c = 0; c < A; ++c) {
             held[c] = mean[c];
@@ -592,41 +601,20 @@ static int ddpg_act_rng(const char *who, const ce_ddpg *l, const float *obs, int
             CE_HIP(hipStreamSynchronize(stream));      // the host copy may change at the next call
             l->noise_set = true;
         }
-        ce::DdpgWideActRng n{};
-        n.seed_lo = static_cast<uint32_t>(seed);
-        n.seed_hi = static_cast<uint32_t>(seed >> 32);
-        n.t = t;
-        n.row0 = row0;
-        n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
-        n.theta = ou ? static_cast<float>(theta) : 0.0f;
-        n.dt = ou ? static_cast<float>(dt) : 0.0f;
-        n.ou = ou ? ou_state : nullptr;
-        n.reset = ou ? reset : nullptr;
+        auto n = act_rng_args<ce::DdpgWideActRng>(seed, t, row0, ou, theta, dt, ou_state, reset);
         n.mean = l->noise_dev;
         n.sigma = l->noise_dev + ce::kDdpgWideMaxA;
-        // the tile's N(0,1) block is the plan's S region
-        hipLaunchKernelGGL(ce::ddpg_act_rng_wide_kernel, dim3(tiles), dim3(ce::kDdpgBlock),
-                           l->lds_act, stream, g, n);
-        CE_HIP(hipGetLastError());
-        return CE_OK;
+        launch_act_rng(l, g, n, 0, stream);      // the tile's N(0,1) block is the plan's S region
+    } else {
+        auto n = act_rng_args<ce::DdpgActRng>(seed, t, row0, ou, theta, dt, ou_state, reset);
+        for (int c = 0; c < A; ++c) {
+            n.mean[c] = mean[c];
+            n.sigma[c] = held_sigma(c);
+        }
+        // + the tile's N(0,1) block [round4(A)][33] behind the row scalars
+        launch_act_rng(l, g, n, static_cast<size_t>(round_up(A, 4)) * ce::kDdpgLd * sizeof(float),
+                       stream);
     }
-    ce::DdpgActRng n{};
-    n.seed_lo = static_cast<uint32_t>(seed);
-    n.seed_hi = static_cast<uint32_t>(seed >> 32);
-    n.t = t;
-    n.row0 = row0;
-    n.kind = ou ? ce::kDdpgNoiseOu : ce::kDdpgNoiseNormal;
-    n.theta = ou ? static_cast<float>(theta) : 0.0f;
-    n.dt = ou ? static_cast<float>(dt) : 0.0f;
-    n.ou = ou ? ou_state : nullptr;
-    n.reset = ou ? reset : nullptr;
-    for (int c = 0; c < A; ++c) {
-        n.mean[c] = mean[c];
-        n.sigma[c] = held_sigma(c);
-    }
-    // + the tile's N(0,1) block [round4(A)][33] behind the row scalars
-    const size_t lds = l->lds_act + static_cast<size_t>(round_up(A, 4)) * ce::kDdpgLd * sizeof(float);
-    hipLaunchKernelGGL(ce::ddpg_act_rng_kernel, dim3(tiles), dim3(ce::kDdpgBlock), lds, stream, g, n);
     CE_HIP(hipGetLastError());
     return CE_OK;
 }
@@ -653,7 +641,7 @@ int ce_ddpg_act_rng_wide(ce_ddpg *l, const float *obs, int64_t rows, uint64_t se
 int ce_ddpg_target(ce_ddpg *l, int64_t n, int64_t m, const int32_t *idx, const float *obs1,
                    const float *rewards, const uint8_t *dones, float *y, void *hip_stream) {
     const char *who = "ce_ddpg_target";
-    const int rc = rows_ok(who, n, m, idx);
+    const int rc = ce::learner_rows_ok(who, n, m, idx);
     if (rc != CE_OK) return rc;
     const auto null = [who](const char *what) { return fail(CE_EINVAL, std::string(who) + ": null " + what); };
     if (!obs1) return null("obs1");
@@ -737,14 +725,9 @@ int ce_ddpg_partial(ce_ddpg *l, int64_t n, int64_t n_total, int64_t m, const int
                     const float *obs1, const uint8_t *dones, float *y, double *record,
                     void *hip_stream) {
     const char *who = "ce_ddpg_partial";
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    int rc = rows_ok(who, n, m, idx);
+    int rc = ce::learner_rows_ok(who, n, m, idx);
     if (rc != CE_OK) return rc;
-    if (n_total < n || n_total > kMaxTotalRows)
-        return bad(": n_total must be in [n, 2^30], got " + std::to_string(n_total) + " for n = " +
-                   std::to_string(n));
-    if (!record) return bad(": null record");
-    if (reinterpret_cast<uintptr_t>(record) & 7) return bad(": the record must be 8-byte aligned");
+    if ((rc = ce::learner_partial_ok(who, n, n_total, record)) != CE_OK) return rc;
     // `record` stands in for stats in the null checks the entry points share
     rc = batch_ok(who, l, n, m, idx, obs0, actions, rewards, obs1, dones, y,
                   reinterpret_cast<const float *>(record));
@@ -768,8 +751,9 @@ int ce_ddpg_combine(ce_ddpg *l, int32_t world, const double *records, int64_t n_
                     float *grad, float *stats, void *hip_stream) {
     const char *who = "ce_ddpg_combine";
     if (!grad) return fail(CE_EINVAL, std::string(who) + ": null grad");
-    const int rc = records_ok(who, l, world, records, n_total, stats);
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
     if (rc != CE_OK) return rc;
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
     CE_CLEAR_STALE_ERROR_AT(who);
     enqueue_combine(l, world, records, n_total, grad, stats, static_cast<hipStream_t>(hip_stream));
     CE_HIP(hipGetLastError());
@@ -781,8 +765,9 @@ int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_to
     const char *who = "ce_ddpg_apply";
     if (std::isnan(actor_lr) || std::isnan(critic_lr))
         return fail(CE_EINVAL, std::string(who) + ": a learning rate is not a number");
-    const int rc = records_ok(who, l, world, records, n_total, stats);
+    const int rc = ce::learner_apply_ok(who, world, records, n_total, stats);
     if (rc != CE_OK) return rc;
+    if (!l) return fail(CE_EINVAL, std::string(who) + ": null learner");
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     enqueue_combine(l, world, records, n_total, l->grad, stats, stream);
@@ -791,31 +776,11 @@ int ce_ddpg_apply(ce_ddpg *l, int32_t world, const double *records, int64_t n_to
     return CE_OK;
 }
 
-// Adam's two blocks to (`set` false) or from the caller's; every check first
+// Adam's two blocks to (`set` false) or from the caller's
 static int ddpg_opt_state(const char *who, ce_ddpg *l, void *m, void *v, int64_t n, bool set,
                           uint32_t flags, void *hip_stream) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (!m) return bad(": null m");
-    if (!v) return bad(": null v");
-    if (!l) return bad(": null learner");
-    if (n != l->plan.n_params)
-        return bad(": got " + std::to_string(n) + " entries per block, the agent has " +
-                   std::to_string(l->plan.n_params) + " parameters");
-    CE_CLEAR_STALE_ERROR_AT(who);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const bool dev = (flags & CE_PTR_DEVICE) != 0;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(float);
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice
-                                   : (set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
-    if (set) {
-        CE_HIP(hipMemcpyAsync(l->m, m, bytes, kind, stream));
-        CE_HIP(hipMemcpyAsync(l->v, v, bytes, kind, stream));
-    } else {
-        CE_HIP(hipMemcpyAsync(m, l->m, bytes, kind, stream));
-        CE_HIP(hipMemcpyAsync(v, l->v, bytes, kind, stream));
-    }
-    if (!dev) CE_HIP(hipStreamSynchronize(stream));   // the host blocks may be pageable
-    return CE_OK;
+    return ce::learner_opt_state(who, n_params_of(l), "agent", l ? l->m : nullptr,
+                                 l ? l->v : nullptr, "m", "v", m, v, n, set, flags, hip_stream);
 }
 
 int ce_ddpg_get_opt_state(ce_ddpg *l, float *m, float *v, int64_t n, int64_t *step,

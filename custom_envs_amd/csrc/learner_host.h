@@ -18,6 +18,11 @@
 // Dispatch is static (a kernel that differs is a template parameter); nothing
 // here allocates on a call path, and every argument check precedes the first
 // HIP call.
+//
+// The checks that need neither a PolicyPlan nor a kernel (rows, a partial's
+// record, the gathered records, the parameter vector, the optimiser's blocks)
+// are learner_checks.h's, which the DDPG learner (ddpg_engine.hip) shares; what
+// is left here is bound to a policy.
 #pragma once
 
 #include <algorithm>
@@ -26,13 +31,12 @@
 #include <string>
 
 #include "common.h"
+#include "learner_checks.h"
 #include "policy_engine.h"
 #include "ppo_grad_tile.h"
 #include "ppo_grad_wide_tile.h"
 
 namespace ce {
-
-constexpr int64_t kLearnerMaxRows = int64_t(1) << 24;
 
 struct LearnerCore {
     ce_policy *policy = nullptr;
@@ -166,20 +170,12 @@ inline void learner_core_destroy(LearnerCore &c) {
 
 // ---- the parameter entry points (`core` null: a null learner) ---------------
 
-inline int learner_params_ok(const char *who, const LearnerCore *core, const void *flat,
-                             int64_t n, const char *got) {
-    if (!flat) return fail(CE_EINVAL, std::string(who) + ": null parameter vector");
-    if (!core) return fail(CE_EINVAL, std::string(who) + ": null learner");
-    if (n != core->plan.n_params)
-        return fail(CE_EINVAL, std::string(who) + got + std::to_string(n) +
-                                   " parameters, the policy has " + std::to_string(core->plan.n_params));
-    return CE_OK;
-}
+inline int learner_n_params(const LearnerCore *core) { return core ? core->plan.n_params : -1; }
 
 // `flat` into the master parameters and through to the policy's image.
 inline int learner_set_params(const char *who, LearnerCore *core, const float *flat, int64_t n,
                               uint32_t flags, void *hip_stream) {
-    const int rc = learner_params_ok(who, core, flat, n, ": got ");
+    const int rc = learner_params_ok(who, learner_n_params(core), "policy", flat, n, ": got ");
     if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -195,7 +191,8 @@ inline int learner_set_params(const char *who, LearnerCore *core, const float *f
 
 inline int learner_get_params(const char *who, LearnerCore *core, float *flat, int64_t n,
                               uint32_t flags, void *hip_stream) {
-    const int rc = learner_params_ok(who, core, flat, n, ": got room for ");
+    const int rc = learner_params_ok(who, learner_n_params(core), "policy", flat, n,
+                                     ": got room for ");
     if (rc != CE_OK) return rc;
     CE_CLEAR_STALE_ERROR_AT(who);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -208,51 +205,16 @@ inline int learner_get_params(const char *who, LearnerCore *core, float *flat, i
     return CE_OK;
 }
 
-// ---- the optimiser's state in and out ----------------------------------------
-// A learner names its two [n_params] float32 blocks once (PPO2: Adam's m and
-// v; A2C: RMSProp's ms and mom) and its step counter; these copy them to
-// (`set` false) or from (`set` true) the caller's `a` and `b`: host pointers
-// (synchronises) or, under CE_PTR_DEVICE, device pointers (stream-ordered).
-// `core` null: a null learner.
+// ---- the optimiser's state in and out (learner_checks.h; `core` null: a null
+// learner) -------------------------------------------------------------------
 inline int learner_opt_state(const char *who, const LearnerCore *core, float *dev_a, float *dev_b,
                              const char *name_a, const char *name_b, void *a, void *b, int64_t n,
                              bool set, uint32_t flags, void *hip_stream) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (!a) return bad(std::string(": null ") + name_a);
-    if (!b) return bad(std::string(": null ") + name_b);
-    if (!core) return bad(": null learner");
-    if (n != core->plan.n_params)
-        return bad(": got " + std::to_string(n) + " entries per block, the policy has " +
-                   std::to_string(core->plan.n_params) + " parameters");
-    CE_CLEAR_STALE_ERROR_AT(who);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const bool dev = (flags & CE_PTR_DEVICE) != 0;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(float);
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice
-                                   : (set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
-    if (set) {
-        CE_HIP(hipMemcpyAsync(dev_a, a, bytes, kind, stream));
-        CE_HIP(hipMemcpyAsync(dev_b, b, bytes, kind, stream));
-    } else {
-        CE_HIP(hipMemcpyAsync(a, dev_a, bytes, kind, stream));
-        CE_HIP(hipMemcpyAsync(b, dev_b, bytes, kind, stream));
-    }
-    if (!dev) CE_HIP(hipStreamSynchronize(stream));   // the host blocks may be pageable
-    return CE_OK;
+    return learner_opt_state(who, learner_n_params(core), "policy", dev_a, dev_b, name_a, name_b, a,
+                             b, n, set, flags, hip_stream);
 }
 
 // ---- argument checks --------------------------------------------------------
-
-// n rows gathered by idx (null: the first n) out of an m-row batch
-inline int learner_rows_ok(const char *who, int64_t n, int64_t m, const int32_t *idx) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (n < 1) return bad(": n must be at least 1, got " + std::to_string(n));
-    if (m < 1 || m > kLearnerMaxRows)
-        return bad(": m must be in [1, 2^24], got " + std::to_string(m));
-    if (n > kLearnerMaxRows) return bad(": n must be at most 2^24");
-    if (!idx && n > m) return bad(": n exceeds m and there is no idx to gather by");
-    return CE_OK;
-}
 
 // the record stride of a [k][rows] float view (`name`: "reward", "value")
 inline int learner_stride_ok(const char *who, const char *name, int64_t stride_bytes,
@@ -358,34 +320,6 @@ void learner_enqueue_reduce_finish(const LearnerCore &c, int n, int grid, float 
 //   apply     [combine, finish, optimiser, repack] from the W records
 // Every rank adds the same float64 values in rank order, so every rank gets
 // the same bits; at W = 1 they are the bits of [gradient, reduce, finish].
-
-constexpr int64_t kLearnerMaxTotalRows = int64_t(1) << 30;
-constexpr int kLearnerMaxWorld = 1 << 16;
-
-// n_total and the record of a partial call (after learner_rows_ok)
-inline int learner_partial_ok(const char *who, int64_t n, int64_t n_total, const void *record) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (n_total < n || n_total > kLearnerMaxTotalRows)
-        return bad(": n_total must be in [n, 2^30], got " + std::to_string(n_total) + " for n = " +
-                   std::to_string(n));
-    if (!record) return bad(": null record");
-    if (reinterpret_cast<uintptr_t>(record) & 7) return bad(": the record must be 8-byte aligned");
-    return CE_OK;
-}
-
-// world, the gathered records, n_total and stats of an apply / combine call
-inline int learner_apply_ok(const char *who, int32_t world, const void *records, int64_t n_total,
-                            const void *stats) {
-    const auto bad = [who](const std::string &what) { return fail(CE_EINVAL, who + what); };
-    if (world < 1 || world > kLearnerMaxWorld)
-        return bad(": world must be in [1, 2^16], got " + std::to_string(world));
-    if (n_total < 1 || n_total > kLearnerMaxTotalRows)
-        return bad(": n_total must be in [1, 2^30], got " + std::to_string(n_total));
-    if (!records) return bad(": null records");
-    if (reinterpret_cast<uintptr_t>(records) & 7) return bad(": the records must be 8-byte aligned");
-    if (!stats) return bad(": null stats");
-    return CE_OK;
-}
 
 // [partial reduce] after a gradient kernel of `grid` workgroups per network
 // over this rank's n rows: the slab and the statistic sums into `record`.

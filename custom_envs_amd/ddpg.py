@@ -90,7 +90,6 @@ from custom_envs_amd import rng as _rng
 from custom_envs_amd._native import (CeDdpgConfig, CeDdpgNoise, CeDdpgWideConfig, CeDdpgWideNoise,
                                      check)
 from custom_envs_amd.learner import N_STATS
-from custom_envs_amd.policy import MlpPolicy as _DevicePolicy
 from custom_envs_amd.policy import dict_to_flat, flat_to_dict, layout_size
 from custom_envs_amd.ppo2 import adam_step_numpy
 
@@ -585,12 +584,17 @@ def check_tensor(name, t, dtype, shape):
         raise ValueError('%s must be contiguous' % name)
 
 
-class DDPGAgent:
+class DDPGAgent(learner.LearnerBase):
     """DDPG's actor, critic, targets and optimiser on one GPU (see the module
-    docstring).  ``device=None`` gives the shape-and-validation-only form,
-    which needs no GPU.  ``scale`` (``[A]`` or a scalar): what the normalised
+    docstring), on the learners' shared shell (``learner.LearnerBase``); its
+    own are the shape-only store, the targets, ``Stats.y``, ``stats=`` in
+    ``apply`` and the two learning rates.  ``device=None`` gives the
+    shape-and-validation-only form, which needs no GPU.  ``scale`` (``[A]`` or a scalar): what the normalised
     action is multiplied by for the env, SB's ``abs(action_space.low)``.
     ``grid_limit`` 0 means one workgroup per CU per branch."""
+    PREFIX = 'ce_ddpg'
+    BATCH_FIELDS = BATCH_FIELDS
+    STATS = Stats
     MAX_OBS, MAX_ACT = 128, _native.CE_DDPG_MAX_ACT
     WIDE = False                 # the wide create entry, config and noise structs
 
@@ -641,18 +645,12 @@ class DDPGAgent:
               'ce_ddpg_create' + suffix)
         self._h = handle
 
-    _stream = staticmethod(_DevicePolicy._stream)
-
     def params_layout(self):
         return params_layout(self.obs_dim, self.act_dim, self.hidden)
 
-    def _call(self, entry, *args):
-        name = 'ce_ddpg_' + entry
-        check(getattr(self._lib, name)(*args), name)
-
-    def check_device(self, name, t):
-        if t.device.type != 'cuda' or t.device.index != self.device:
-            raise ValueError('%s must be on device cuda:%d, got %s' % (name, self.device, t.device))
+    def _need_handle(self):
+        if self._h is None:
+            raise _native.NativeEngineError('a shape-only agent has no device')
 
     # -------------------------------------------------------------- parameters
     def set_params(self, params, stream=None, target_only=False):
@@ -707,29 +705,24 @@ class DDPGAgent:
 
     # --------------------------------------------------------- optimiser state
     OPT_BLOCKS = ('m', 'v')
-    check_opt_state = learner.Learner.check_opt_state
 
+    # get_opt_state / set_opt_state differ from the base's for the shape-only
+    # agent alone, which keeps what was set on the host (zeros at first)
     def get_opt_state(self, stream=None):
         """Adam's state as a dict: ``m`` and ``v`` (new float32 numpy vectors
         in the flat layout) and ``step``, the shared step count.
         Synchronises.  The shape-only agent returns what was set (zeros)."""
         if self._h is None:
             return {k: (v.copy() if hasattr(v, 'copy') else v) for k, v in self._host_opt.items()}
-        m, v = (np.empty(self.n_params, np.float32) for _ in self.OPT_BLOCKS)
-        step = ctypes.c_int64(0)
-        self._call('get_opt_state', self._h, m.ctypes.data, v.ctypes.data, self.n_params,
-                   ctypes.byref(step), 0, self._stream(stream))
-        return {'m': m, 'v': v, 'step': int(step.value)}
+        return super().get_opt_state(stream)
 
     def set_opt_state(self, state, stream=None):
         """Install a ``get_opt_state`` dict (validated first).  The
         parameters and the targets are kept."""
+        if self._h is not None:
+            return super().set_opt_state(state, stream)
         m, v, step = self.check_opt_state(state)
-        if self._h is None:
-            self._host_opt = {'m': m.copy(), 'v': v.copy(), 'step': step}
-            return
-        self._call('set_opt_state', self._h, m.ctypes.data, v.ctypes.data, self.n_params, step, 0,
-                   self._stream(stream))
+        self._host_opt = {'m': m.copy(), 'v': v.copy(), 'step': step}
 
     # --------------------------------------------------------------------- act
     def check_act(self, obs, noise=None, out=None):
@@ -789,8 +782,7 @@ class DDPGAgent:
         t = int(gen.t) if t is None else int(t)
         if not 0 <= t < 2 ** 32:
             raise ValueError('the draw t must be in [0, 2^32), got %d' % t)
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        self._need_handle()
         state_ptr = reset_ptr = None
         if action_noise.KIND == _native.CE_DDPG_NOISE_OU:
             state_ptr = action_noise.ensure_state(rows, self.act_dim, obs.device).data_ptr()
@@ -828,16 +820,7 @@ class DDPGAgent:
         for name in BATCH_FIELDS:
             check_tensor(name, batch[name], torch.uint8 if name == 'dones' else torch.float32,
                          shapes.get(name, (M,)))
-        N = M
-        if idx is not None:
-            if not hasattr(idx, 'data_ptr') or idx.dtype != torch.int32:
-                raise ValueError('idx must have dtype int32, got %s'
-                                 % getattr(idx, 'dtype', type(idx).__name__))
-            if idx.dim() != 1 or idx.shape[0] < 1:
-                raise ValueError('idx must have shape [N >= 1], got %s' % (tuple(idx.shape),))
-            if not idx.is_contiguous():
-                raise ValueError('idx must be contiguous')
-            N = int(idx.shape[0])
+        N = M if idx is None else self.check_idx(idx)
         if self._h is not None:
             for name in BATCH_FIELDS:
                 self.check_device(name, batch[name])
@@ -847,8 +830,7 @@ class DDPGAgent:
 
     def _head(self, batch, idx):
         M, N = self.check_batch(batch, idx)
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        self._need_handle()
         ptrs = [batch[n].data_ptr() for n in BATCH_FIELDS]
         return [self._h, N, M, None if idx is None else idx.data_ptr()] + ptrs, N
 
@@ -887,26 +869,13 @@ class DDPGAgent:
     # ``[W][record]`` buffer, ``apply`` (combine in rank order, statistics,
     # Adam x2 + soft update).  Every rank computes the same bits; at W = 1 they
     # are ``step``'s.
-    exchange = None      # a distributed.GradientExchange attaches itself here
-
-    @property
-    def record_doubles(self):
-        return learner.record_doubles(self.n_params)
-
     def check_record_tensor(self, name, t, shape):
-        """A float64 tensor the exchange kernels read or write: dtype, shape,
-        contiguity, then (with a handle) the device."""
+        """The base's check with ``check_tensor``'s texts, as every other
+        tensor of this module is refused."""
         import torch
         check_tensor(name, t, torch.float64, shape)
         if self._h is not None:
             self.check_device(name, t)
-
-    check_total = staticmethod(learner.Learner.check_total)
-
-    @staticmethod
-    def _rows_of(batch, idx):
-        t = idx if idx is not None else batch.get('obs0')
-        return int(t.shape[0]) if hasattr(t, 'dim') and t.dim() >= 1 else 0
 
     def partial(self, batch, idx=None, n_total=None, out=None, stream=None, y=None):
         """This rank's share of a train step of ``n_total`` rows (None: its
@@ -926,8 +895,7 @@ class DDPGAgent:
         M, N = self.check_batch(batch, idx)
         if y is not None:
             check_tensor('y', y, torch.float32, (N,))
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        self._need_handle()
         dev = batch['obs0'].device
         if y is None:
             y = torch.empty(N, dtype=torch.float32, device=dev)
@@ -941,34 +909,18 @@ class DDPGAgent:
         return out, y
 
     def _records_head(self, records, n_total, stats=None):
-        """The checked leading arguments of ``combine`` / ``apply`` and the
-        statistics tensor the call writes."""
+        """The base's, except that a shape-only agent is refused here and
+        that ``apply``'s ``stats`` (checked) is written instead of a new
+        tensor."""
         import torch
-        if not hasattr(records, 'dim') or records.dim() != 2:
-            raise ValueError('records must have shape [world][%d]' % self.record_doubles)
-        world = int(records.shape[0])
-        self.check_record_tensor('records', records, (world, self.record_doubles))
-        n_total = int(n_total)
-        if world < 1 or n_total < 1:
-            raise ValueError('records of %d ranks and n_total = %d' % (world, n_total))
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        world, n_total = self.check_gathered(records, n_total)
+        self._need_handle()
         if stats is None:
             stats = torch.empty(N_STATS, dtype=torch.float32, device=records.device)
         else:
             check_tensor('stats', stats, torch.float32, (N_STATS,))
             self.check_device('stats', stats)
         return [self._h, world, records.data_ptr(), n_total], stats
-
-    def combine(self, records, n_total, stream=None):
-        """The gradient and statistics of all ``n_total`` rows from the ranks'
-        records ``[world][record_doubles]``, no update.  Returns (grad,
-        ``Stats``)."""
-        import torch
-        head, stats = self._records_head(records, n_total)
-        grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
-        self._call('combine', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
-        return grad, Stats(stats)
 
     def apply(self, records, n_total, actor_lr=None, critic_lr=None, stream=None, stats=None):
         """Combine, statistics, then ``step``'s update (Adam on both blocks,
@@ -1063,8 +1015,7 @@ class DDPGAgent:
                                         stream)
         actor_lr, critic_lr = self._rate('actor_lr', actor_lr), self._rate('critic_lr', critic_lr)
         steps, n = self.check_train(memory, steps, batch_size, rng)
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        self._need_handle()
         self.check_device('memory', memory.obs0)
         dev = memory.obs0.device
         sc = self._train_scratch
@@ -1089,8 +1040,7 @@ class DDPGAgent:
         steps, n = self.check_train(memory, steps, batch_size, rng)
         total = ex.world * n
         rng.check_replay(steps, total, memory.size)
-        if self._h is None:
-            raise _native.NativeEngineError('a shape-only agent has no device')
+        self._need_handle()
         self.check_device('memory', memory.obs0)
         dev = memory.obs0.device
         sc = self._train_scratch
@@ -1113,17 +1063,6 @@ class DDPGAgent:
         """``loss_grad_numpy`` with this agent's shape and hyper-parameters."""
         return loss_grad_numpy(params, target_params, *[batch[n] for n in BATCH_FIELDS],
                                hp=self.hp, hidden=self.hidden, dtype=dtype)
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.ce_ddpg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class WideDDPGAgent(DDPGAgent):

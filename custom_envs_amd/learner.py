@@ -1,5 +1,8 @@
-"""What the device-side learners (ppo2.py, a2c.py) share: the pieces of their
-NumPy statements that are the same text, and the ``Learner`` base class.
+"""What the device-side learners share: ``LearnerBase`` (ppo2.py, a2c.py and
+ddpg.py: the handle's calls, the optimiser's state, the gradient exchange from
+the gathered records on), and for the two that train an ``MlpPolicy`` (ppo2.py,
+a2c.py) the pieces of their NumPy statements that are the same text and the
+``Learner`` class.
 
 The statement helpers are expressions moved whole out of the two
 ``loss_grad_numpy`` and the two optimiser statements; float32 runs of the
@@ -165,44 +168,16 @@ class Stats:
         return out
 
 
-class Learner:
-    """The handle, the master parameters and the tensor validation of a
-    learner for one ``MlpPolicy``.  A subclass names its entry points
-    (``PREFIX``: ``ce_<x>_create`` ...), its config struct (``CONFIG``), its
-    flattened batch (``BATCH_FIELDS``) and its statement (``_loss_grad``)."""
+class LearnerBase:
+    """What a device-side learner is whatever it trains: the calls on its
+    handle (``PREFIX``: ``ce_<x>_create`` ...), the optimiser's state in and
+    out, the validation of ``idx``, the gradient exchange from the gathered
+    records on, and ``close``.  ``Learner`` binds it to an ``MlpPolicy``;
+    ``ddpg.DDPGAgent``, which owns its networks, derives from it directly.  A
+    subclass has ``_lib``, ``_h`` (None: shape only), ``device`` and
+    ``n_params``, and names its flattened batch (``BATCH_FIELDS``)."""
     PREFIX = None
-    CONFIG = None
     BATCH_FIELDS = ()
-    _loss_grad = None
-    WIDE = False         # a wide learner: ``ce_<x>_create_wide`` on a ``WideMlpPolicy``
-
-    def __init__(self, policy, **cfg):
-        if self.WIDE:
-            if not isinstance(policy, WideMlpPolicy):
-                raise TypeError('policy must be a WideMlpPolicy')
-        elif not isinstance(policy, MlpPolicy):
-            raise TypeError('policy must be an MlpPolicy')
-        elif isinstance(policy, WideMlpPolicy):    # what ce_<x>_create answers, without the call
-            raise _native.NativeEngineError(
-                '%s_create: the learners take obs_dim <= 128, act_dim <= 64: a WideMlpPolicy '
-                '(obs_dim %d, act_dim %d) acts and rolls out only (CE_EUNSUPPORTED)'
-                % (self.PREFIX, policy.obs_dim, policy.act_dim))
-        self.policy = policy
-        self.device = policy.device
-        self.n_params = policy.n_params
-        self.gamma, self.lr = float(cfg['gamma']), float(cfg['lr'])
-        self.max_grad_norm = float(cfg['max_grad_norm'])
-        self._cfg = self.CONFIG(**cfg)
-        self._lib, self._h = policy._lib, None
-        if policy._h is None:        # shape only
-            return
-        handle = ctypes.c_void_p()
-        self._call('create_wide' if self.WIDE else 'create', policy._h, ctypes.byref(self._cfg),
-                   ctypes.byref(handle))
-        self._h = handle
-        host = getattr(policy, '_host_params', None)
-        if host is not None:
-            self.set_params(host)
 
     _stream = staticmethod(MlpPolicy._stream)
 
@@ -210,41 +185,23 @@ class Learner:
         name = '%s_%s' % (self.PREFIX, entry)
         check(getattr(self._lib, name)(*args), name)
 
-    def loss_grad_numpy(self, params, batch, dtype=np.float64):
-        """``loss_grad_numpy`` with this learner's hyper-parameters."""
-        return self._loss_grad(params, *[batch[n] for n in self.BATCH_FIELDS], hp=self.hp,
-                               hidden=self.policy.hidden, dtype=dtype)
+    def check_device(self, name, t):
+        if t.device.type != 'cuda' or t.device.index != self.device:
+            raise ValueError('%s must be on device cuda:%d, got %s' % (name, self.device, t.device))
 
-    # -------------------------------------------------------------- parameters
-    def set_params(self, params, stream=None):
-        """The master parameters (flat vector or ``params_layout`` dict, numpy
-        or a float32 device tensor), written through to the policy's image.
-        The optimiser's state is kept."""
-        if isinstance(params, dict):
-            params = dict_to_flat(params, self.policy.params_layout())
-        if hasattr(params, 'data_ptr'):
-            self.policy.check_input('params', params, (self.n_params,))
-            self._call('set_params', self._h, params.data_ptr(), self.n_params,
-                       _native.CE_PTR_DEVICE, self._stream(stream))
-            self.policy._host_params = None
-            return
-        flat = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        if flat.size != self.n_params:
-            raise ValueError('got %d parameters, the policy has %d' % (flat.size, self.n_params))
-        self._call('set_params', self._h, flat.ctypes.data, flat.size, 0, self._stream(stream))
-        self.policy._host_params = flat.copy()
-
-    def get_params(self, out=None, stream=None):
-        """The master parameters: into the float32 device tensor ``out``
-        (stream-ordered), or as a new numpy vector (synchronises)."""
-        if out is not None:
-            self.policy.check_input('out', out, (self.n_params,))
-            self._call('get_params', self._h, out.data_ptr(), self.n_params,
-                       _native.CE_PTR_DEVICE, self._stream(stream))
-            return out
-        flat = np.empty(self.n_params, np.float32)
-        self._call('get_params', self._h, flat.ctypes.data, flat.size, 0, self._stream(stream))
-        return flat
+    @staticmethod
+    def check_idx(idx):
+        """The form of ``idx`` (int32 ``[N >= 1]``, contiguous; the device comes
+        last, with the caller).  Returns N."""
+        import torch
+        if not hasattr(idx, 'data_ptr') or idx.dtype != torch.int32:
+            raise ValueError('idx must have dtype int32, got %s'
+                             % getattr(idx, 'dtype', type(idx).__name__))
+        if idx.dim() != 1 or idx.shape[0] < 1:
+            raise ValueError('idx must have shape [N >= 1], got %s' % (tuple(idx.shape),))
+        if not idx.is_contiguous():
+            raise ValueError('idx must be contiguous')
+        return int(idx.shape[0])
 
     # --------------------------------------------------------- optimiser state
     OPT_BLOCKS = ()      # the names of the optimiser's two [n_params] blocks
@@ -290,6 +247,167 @@ class Learner:
         self._call('set_opt_state', self._h, a.ctypes.data, b.ctypes.data, self.n_params, step, 0,
                    self._stream(stream))
 
+    # ------------------------------------------------------- gradient exchange
+    # Each learner has its ``partial`` (the rows of this rank into its record);
+    # what starts from the gathered records is the same for all.
+    exchange = None      # a distributed.GradientExchange attaches itself here
+    STATS = Stats        # what ``combine`` / ``apply`` return
+
+    @property
+    def record_doubles(self):
+        return record_doubles(self.n_params)
+
+    @classmethod
+    def _rows_of(cls, batch, idx):
+        """The rows of a call before anything else is checked."""
+        t = idx if idx is not None else batch.get(cls.BATCH_FIELDS[0])
+        return int(t.shape[0]) if hasattr(t, 'dim') and t.dim() >= 1 else 0
+
+    @staticmethod
+    def check_total(n, n_total):
+        """``n_total`` (None: ``n``) as an int no smaller than ``n``."""
+        n_total = int(n) if n_total is None else int(n_total)
+        if n_total < n:
+            raise ValueError('n_total = %d is less than the %d rows of this call' % (n_total, n))
+        return n_total
+
+    def check_record_tensor(self, name, t, shape):
+        """A float64 tensor the exchange kernels read or write: dtype, shape,
+        contiguity, then (with a handle) the device."""
+        import torch
+        if not hasattr(t, 'data_ptr') or t.dtype != torch.float64:
+            raise ValueError('%s must be a float64 tensor, got %s'
+                             % (name, getattr(t, 'dtype', type(t).__name__)))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s must have shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+        if self._h is not None:
+            self.check_device(name, t)
+
+    def _record_out(self, out, like):
+        """The record a ``partial`` call writes: ``out`` checked, or a new one."""
+        import torch
+        if out is None:
+            return torch.zeros(self.record_doubles, dtype=torch.float64, device=like.device)
+        self.check_record_tensor('out', out, (self.record_doubles,))
+        return out
+
+    def check_gathered(self, records, n_total):
+        """The form of the gathered records ``[world][record_doubles]`` and of
+        ``n_total``.  Returns (world, n_total)."""
+        if not hasattr(records, 'dim') or records.dim() != 2:
+            raise ValueError('records must have shape [world][%d]' % self.record_doubles)
+        world = int(records.shape[0])
+        self.check_record_tensor('records', records, (world, self.record_doubles))
+        n_total = int(n_total)
+        if world < 1 or n_total < 1:
+            raise ValueError('records of %d ranks and n_total = %d' % (world, n_total))
+        return world, n_total
+
+    def _records_head(self, records, n_total):
+        """The checked leading arguments of ``combine`` / ``apply`` and the
+        statistics tensor the call writes."""
+        import torch
+        world, n_total = self.check_gathered(records, n_total)
+        stats = torch.empty(N_STATS, dtype=torch.float32, device=records.device)
+        return [self._h, world, records.data_ptr(), n_total], stats
+
+    def combine(self, records, n_total, stream=None):
+        """The gradient and statistics of all ``n_total`` rows from the ranks'
+        records ``[world][record_doubles]``, no update.  Returns (grad,
+        ``Stats``)."""
+        import torch
+        head, stats = self._records_head(records, n_total)
+        grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
+        self._call('combine', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
+        return grad, self.STATS(stats)
+
+    def close(self):
+        if getattr(self, '_h', None):
+            getattr(self._lib, self.PREFIX + '_destroy')(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Learner(LearnerBase):
+    """The handle, the master parameters and the tensor validation of a
+    learner for one ``MlpPolicy``.  A subclass names its entry points
+    (``PREFIX``: ``ce_<x>_create`` ...), its config struct (``CONFIG``), its
+    flattened batch (``BATCH_FIELDS``) and its statement (``_loss_grad``)."""
+    CONFIG = None
+    _loss_grad = None
+    WIDE = False         # a wide learner: ``ce_<x>_create_wide`` on a ``WideMlpPolicy``
+
+    def __init__(self, policy, **cfg):
+        if self.WIDE:
+            if not isinstance(policy, WideMlpPolicy):
+                raise TypeError('policy must be a WideMlpPolicy')
+        elif not isinstance(policy, MlpPolicy):
+            raise TypeError('policy must be an MlpPolicy')
+        elif isinstance(policy, WideMlpPolicy):    # what ce_<x>_create answers, without the call
+            raise _native.NativeEngineError(
+                '%s_create: the learners take obs_dim <= 128, act_dim <= 64: a WideMlpPolicy '
+                '(obs_dim %d, act_dim %d) acts and rolls out only (CE_EUNSUPPORTED)'
+                % (self.PREFIX, policy.obs_dim, policy.act_dim))
+        self.policy = policy
+        self.device = policy.device
+        self.n_params = policy.n_params
+        self.gamma, self.lr = float(cfg['gamma']), float(cfg['lr'])
+        self.max_grad_norm = float(cfg['max_grad_norm'])
+        self._cfg = self.CONFIG(**cfg)
+        self._lib, self._h = policy._lib, None
+        if policy._h is None:        # shape only
+            return
+        handle = ctypes.c_void_p()
+        self._call('create_wide' if self.WIDE else 'create', policy._h, ctypes.byref(self._cfg),
+                   ctypes.byref(handle))
+        self._h = handle
+        host = getattr(policy, '_host_params', None)
+        if host is not None:
+            self.set_params(host)
+
+    def loss_grad_numpy(self, params, batch, dtype=np.float64):
+        """``loss_grad_numpy`` with this learner's hyper-parameters."""
+        return self._loss_grad(params, *[batch[n] for n in self.BATCH_FIELDS], hp=self.hp,
+                               hidden=self.policy.hidden, dtype=dtype)
+
+    # -------------------------------------------------------------- parameters
+    def set_params(self, params, stream=None):
+        """The master parameters (flat vector or ``params_layout`` dict, numpy
+        or a float32 device tensor), written through to the policy's image.
+        The optimiser's state is kept."""
+        if isinstance(params, dict):
+            params = dict_to_flat(params, self.policy.params_layout())
+        if hasattr(params, 'data_ptr'):
+            self.policy.check_input('params', params, (self.n_params,))
+            self._call('set_params', self._h, params.data_ptr(), self.n_params,
+                       _native.CE_PTR_DEVICE, self._stream(stream))
+            self.policy._host_params = None
+            return
+        flat = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        if flat.size != self.n_params:
+            raise ValueError('got %d parameters, the policy has %d' % (flat.size, self.n_params))
+        self._call('set_params', self._h, flat.ctypes.data, flat.size, 0, self._stream(stream))
+        self.policy._host_params = flat.copy()
+
+    def get_params(self, out=None, stream=None):
+        """The master parameters: into the float32 device tensor ``out``
+        (stream-ordered), or as a new numpy vector (synchronises)."""
+        if out is not None:
+            self.policy.check_input('out', out, (self.n_params,))
+            self._call('get_params', self._h, out.data_ptr(), self.n_params,
+                       _native.CE_PTR_DEVICE, self._stream(stream))
+            return out
+        flat = np.empty(self.n_params, np.float32)
+        self._call('get_params', self._h, flat.ctypes.data, flat.size, 0, self._stream(stream))
+        return flat
+
     # ----------------------------------------------------------------- records
     @staticmethod
     def rollout_shape(rewards):
@@ -325,7 +443,6 @@ class Learner:
         """The form of a flattened batch (``BATCH_FIELDS``: obs ``[M][D]``,
         actions ``[M][A]``, the rest ``[M]``, float32, contiguous) and of
         ``idx`` (int32 ``[N]``), then where each lives.  Returns (M, N)."""
-        import torch
         for name in self.BATCH_FIELDS:
             if batch.get(name) is None:
                 raise ValueError('batch lacks %r' % name)
@@ -339,19 +456,11 @@ class Learner:
         shapes = {'obs': (M, self.policy.obs_dim), 'actions': (M, self.policy.act_dim)}
         for name in self.BATCH_FIELDS:
             self.policy.check_input(name, batch[name], shapes.get(name, (M,)), placement=False)
-        N = M
-        if idx is not None:
-            if idx.dtype != torch.int32:
-                raise ValueError('idx must have dtype int32, got %s' % idx.dtype)
-            if idx.dim() != 1 or idx.shape[0] < 1:
-                raise ValueError('idx must have shape [N >= 1], got %s' % (tuple(idx.shape),))
-            if not idx.is_contiguous():
-                raise ValueError('idx must be contiguous')
-            N = int(idx.shape[0])
+        N = M if idx is None else self.check_idx(idx)
         for name in self.BATCH_FIELDS:
-            self.policy.check_device(name, batch[name])
+            self.check_device(name, batch[name])
         if idx is not None:
-            self.policy.check_device('idx', idx)
+            self.check_device('idx', idx)
         return M, N
 
     def _head(self, batch, idx):
@@ -365,75 +474,6 @@ class Learner:
         return head, stats
 
     # ------------------------------------------------------- gradient exchange
-    # Each learner has its ``partial`` (the rows of this rank into its record);
-    # what starts from the gathered records is the same for both.
-    exchange = None      # a distributed.GradientExchange attaches itself here
-    STATS = Stats
-
-    @property
-    def record_doubles(self):
-        return record_doubles(self.n_params)
-
-    @staticmethod
-    def _rows_of(batch, idx):
-        """The rows of a call before anything else is checked."""
-        t = idx if idx is not None else batch.get('obs')
-        return int(t.shape[0]) if t is not None and t.dim() >= 1 else 0
-
-    @staticmethod
-    def check_total(n, n_total):
-        """``n_total`` (None: ``n``) as an int no smaller than ``n``."""
-        n_total = int(n) if n_total is None else int(n_total)
-        if n_total < n:
-            raise ValueError('n_total = %d is less than the %d rows of this call' % (n_total, n))
-        return n_total
-
-    def check_record_tensor(self, name, t, shape):
-        """A float64 tensor the exchange kernels read or write: dtype, shape,
-        contiguity, then (with a handle) the device."""
-        import torch
-        if not hasattr(t, 'data_ptr') or t.dtype != torch.float64:
-            raise ValueError('%s must be a float64 tensor, got %s'
-                             % (name, getattr(t, 'dtype', type(t).__name__)))
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError('%s must have shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous' % name)
-        if self._h is not None:
-            self.policy.check_device(name, t)
-
-    def _record_out(self, out, like):
-        """The record a ``partial`` call writes: ``out`` checked, or a new one."""
-        import torch
-        if out is None:
-            return torch.zeros(self.record_doubles, dtype=torch.float64, device=like.device)
-        self.check_record_tensor('out', out, (self.record_doubles,))
-        return out
-
-    def _records_head(self, records, n_total):
-        """The checked leading arguments of ``combine`` / ``apply`` and the
-        statistics tensor the call writes."""
-        import torch
-        if not hasattr(records, 'dim') or records.dim() != 2:
-            raise ValueError('records must have shape [world][%d]' % self.record_doubles)
-        world = int(records.shape[0])
-        self.check_record_tensor('records', records, (world, self.record_doubles))
-        n_total = int(n_total)
-        if world < 1 or n_total < 1:
-            raise ValueError('records of %d ranks and n_total = %d' % (world, n_total))
-        stats = torch.empty(N_STATS, dtype=torch.float32, device=records.device)
-        return [self._h, world, records.data_ptr(), n_total], stats
-
-    def combine(self, records, n_total, stream=None):
-        """The gradient and statistics of all ``n_total`` rows from the ranks'
-        records ``[world][record_doubles]``, no update.  Returns (grad,
-        ``Stats``)."""
-        import torch
-        head, stats = self._records_head(records, n_total)
-        grad = torch.empty(self.n_params, dtype=torch.float32, device=stats.device)
-        self._call('combine', *head, grad.data_ptr(), stats.data_ptr(), self._stream(stream))
-        return grad, self.STATS(stats)
-
     def apply(self, records, n_total, lr=None, stream=None):
         """Combine, finish, the optimiser's step (one) and the repack from the
         ranks' records.  ``lr`` overrides the learner's for this call: None
@@ -445,14 +485,3 @@ class Learner:
                    self._stream(stream))
         self.policy._host_params = None
         return self.STATS(stats)
-
-    def close(self):
-        if getattr(self, '_h', None):
-            getattr(self._lib, self.PREFIX + '_destroy')(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

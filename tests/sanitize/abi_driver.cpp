@@ -180,6 +180,76 @@ static void learner_checks() {
     REFUSED(ce_a2c_update(nullptr, 2, 4, a, a, 32, a, 16, a, 16, d, 4, a, -1.0f, a, nullptr), "null learner");
 }
 
+// The refusals of ce_ddpg_* that run through the checks it shares with the two
+// learners above (csrc/learner_checks.h), with a NULL handle: the same words,
+// and the all-valid call refused for the handle alone.
+static void ddpg_checks() {
+    std::vector<double> rec(64, 0.0);
+    double *r = rec.data();
+    double *off = reinterpret_cast<double *>(reinterpret_cast<char *>(r) + 4);
+    float *a = reinterpret_cast<float *>(r);
+    const uint8_t *d = reinterpret_cast<const uint8_t *>(r);
+    const int32_t *ix = reinterpret_cast<const int32_t *>(r);
+    const int64_t big = int64_t(1) << 24, total = int64_t(1) << 30;
+    int64_t step = 0;
+
+    REFUSED(ce_ddpg_set_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_ddpg_set_params(nullptr, a, 8, 0, nullptr), "null learner");
+    REFUSED(ce_ddpg_get_params(nullptr, nullptr, 8, 0, nullptr), "null parameter vector");
+    REFUSED(ce_ddpg_get_params(nullptr, a, 8, 0, nullptr), "null learner");
+    REFUSED(ce_ddpg_get_opt_state(nullptr, a, a, 8, nullptr, 0, nullptr), "null step");
+    REFUSED(ce_ddpg_get_opt_state(nullptr, nullptr, a, 8, &step, 0, nullptr), "null m");
+    REFUSED(ce_ddpg_get_opt_state(nullptr, a, nullptr, 8, &step, 0, nullptr), "null v");
+    REFUSED(ce_ddpg_get_opt_state(nullptr, a, a, 8, &step, 0, nullptr), "null learner");
+    REFUSED(ce_ddpg_set_opt_state(nullptr, a, a, 8, -1, 0, nullptr), "step must not be negative");
+    REFUSED(ce_ddpg_set_opt_state(nullptr, nullptr, a, 8, 0, 0, nullptr), "null m");
+    REFUSED(ce_ddpg_set_opt_state(nullptr, a, nullptr, 8, 0, 0, nullptr), "null v");
+    REFUSED(ce_ddpg_set_opt_state(nullptr, a, a, 8, 0, 0, nullptr), "null learner");
+
+    // ---- ce_ddpg_target(l, n, m, idx, obs1, rewards, dones, y, stream)
+    REFUSED(ce_ddpg_target(nullptr, 0, 4, nullptr, a, a, d, a, nullptr), "n must");
+    REFUSED(ce_ddpg_target(nullptr, 4, big + 1, nullptr, a, a, d, a, nullptr), "m must");
+    REFUSED(ce_ddpg_target(nullptr, big + 1, 4, ix, a, a, d, a, nullptr), "n must");
+    REFUSED(ce_ddpg_target(nullptr, 5, 4, nullptr, a, a, d, a, nullptr), "n exceeds m");
+    REFUSED(ce_ddpg_target(nullptr, 4, 4, nullptr, a, a, d, a, nullptr), "null learner");
+    REFUSED(ce_ddpg_target(nullptr, 8, 4, ix, a, a, d, a, nullptr), "null learner");
+
+    // ---- ce_ddpg_grad(l, n, m, idx, obs0, actions, rewards, obs1, dones, y, grad, stats, stream)
+    REFUSED(ce_ddpg_grad(nullptr, 0, 4, nullptr, a, a, a, a, d, a, a, a, nullptr), "n must");
+    REFUSED(ce_ddpg_grad(nullptr, 5, 4, nullptr, a, a, a, a, d, a, a, a, nullptr), "n exceeds m");
+    REFUSED(ce_ddpg_grad(nullptr, 4, 4, nullptr, a, a, a, a, d, a, nullptr, a, nullptr), "null grad");
+    REFUSED(ce_ddpg_grad(nullptr, 4, 4, nullptr, a, a, a, a, d, a, a, a, nullptr), "null learner");
+
+    // ---- ce_ddpg_partial(l, n, n_total, m, idx, obs0, actions, rewards, obs1, dones, y, record, stream)
+    REFUSED(ce_ddpg_partial(nullptr, 0, 4, 4, nullptr, a, a, a, a, d, a, r, nullptr), "n must");
+    REFUSED(ce_ddpg_partial(nullptr, 5, 5, 4, nullptr, a, a, a, a, d, a, r, nullptr), "n exceeds m");
+    REFUSED(ce_ddpg_partial(nullptr, 4, 3, 4, nullptr, a, a, a, a, d, a, r, nullptr), "n_total must");
+    REFUSED(ce_ddpg_partial(nullptr, 4, total + 1, 4, nullptr, a, a, a, a, d, a, r, nullptr), "n_total must");
+    REFUSED(ce_ddpg_partial(nullptr, 4, 4, 4, nullptr, a, a, a, a, d, a, nullptr, nullptr), "null record");
+    REFUSED(ce_ddpg_partial(nullptr, 4, 4, 4, nullptr, a, a, a, a, d, a, off, nullptr), "8-byte aligned");
+    REFUSED(ce_ddpg_partial(nullptr, 4, 4, 4, nullptr, a, a, a, a, d, nullptr, r, nullptr), "null y buffer");
+    REFUSED(ce_ddpg_partial(nullptr, 4, total, 4, nullptr, a, a, a, a, d, a, r, nullptr), "null learner");
+
+    // ---- ce_ddpg_combine(l, world, records, n_total, grad, stats, stream): grad comes first
+    REFUSED(ce_ddpg_combine(nullptr, 0, r, 8, nullptr, a, nullptr), "null grad");
+    REFUSED(ce_ddpg_combine(nullptr, 0, r, 8, a, a, nullptr), "world must");
+    REFUSED(ce_ddpg_combine(nullptr, (1 << 16) + 1, r, 8, a, a, nullptr), "world must");
+    REFUSED(ce_ddpg_combine(nullptr, 2, r, 0, a, a, nullptr), "n_total must");
+    REFUSED(ce_ddpg_combine(nullptr, 2, r, total + 1, a, a, nullptr), "n_total must");
+    REFUSED(ce_ddpg_combine(nullptr, 2, nullptr, 8, a, a, nullptr), "null records");
+    REFUSED(ce_ddpg_combine(nullptr, 2, off, 8, a, a, nullptr), "8-byte aligned");
+    REFUSED(ce_ddpg_combine(nullptr, 2, r, 8, a, nullptr, nullptr), "null stats");
+    REFUSED(ce_ddpg_combine(nullptr, 2, r, 8, a, a, nullptr), "null learner");
+
+    // ---- ce_ddpg_apply(l, world, records, n_total, actor_lr, critic_lr, stats, stream)
+    REFUSED(ce_ddpg_apply(nullptr, 0, r, 8, -1.0, -1.0, a, nullptr), "world must");
+    REFUSED(ce_ddpg_apply(nullptr, 2, r, 0, -1.0, -1.0, a, nullptr), "n_total must");
+    REFUSED(ce_ddpg_apply(nullptr, 2, nullptr, 8, -1.0, -1.0, a, nullptr), "null records");
+    REFUSED(ce_ddpg_apply(nullptr, 2, off, 8, -1.0, -1.0, a, nullptr), "8-byte aligned");
+    REFUSED(ce_ddpg_apply(nullptr, 2, r, 8, -1.0, -1.0, nullptr, nullptr), "null stats");
+    REFUSED(ce_ddpg_apply(nullptr, 2, r, 8, -1.0, -1.0, a, nullptr), "null learner");
+}
+
 // The library's test hooks (csrc/engine.hip; not part of the public header).
 extern "C" int ce_test_plan(const ce_config *cfg, const int32_t *labels, char *step_name,
                             char *many_name, int32_t cap);
@@ -355,6 +425,7 @@ int main() {
     EXPECT(ce_nn_create(nullptr, nullptr, nullptr, nullptr) == CE_EINVAL);
     ce_nn_destroy(nullptr);
     learner_checks();
+    ddpg_checks();
     plan_checks();
     std::printf("failures %d\n", failures);
     return failures ? 1 : 0;

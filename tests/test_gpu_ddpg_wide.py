@@ -7,7 +7,9 @@ statement in the kernels' order (``ddpg_wide_cases``), computed by NumPy alone.
 
 1.  ``act``, ``target`` and gradient parity at the seven cases.
 2.  The narrow agent's bits at ``ddpg_cases.CASES[2:6]``: ``act``, ``y``, every
-    gradient block and every statistic.
+    gradient block and every statistic.  A narrow and a wide agent alive
+    together, their calls alternating on one stream (tensor noise, generated
+    noise, target, grad, two steps), stay bit-equal.
 3.  An ``idx`` subset is bit-equal to the gathered copy; the same call twice is
     bit-identical; a partial never shows what an earlier call with another
     batch left (grid_limit 1 and 2).
@@ -156,6 +158,75 @@ def test_the_narrow_agents_bits(case):
     assert _same(wide.get_opt_state()['v'], narrow.get_opt_state()['v'])
     wide.close()
     narrow.close()
+
+
+# The smallest shape (one hidden layer, one wave's columns) and unequal layers
+# with the action count one column past a 32-column block; 33 rows are two
+# tiles with one live row in the second.
+ALTERNATING_SHAPES = [(5, (32,), 3), (37, (32, 64), 33)]
+
+
+@pytest.mark.parametrize('shape', ALTERNATING_SHAPES, ids=str)
+def test_a_narrow_and_a_wide_agent_alternate_on_one_stream(shape):
+    """Both kinds of handle alive together, the same parameters, grid_limit 2,
+    their calls alternating on one stream: each handle launches its own kind's
+    kernels, and every output and the parameters after the second step are
+    bit-equal between the two."""
+    import torch
+    D, hidden, A = shape
+    N = 33
+    rs = np.random.RandomState(2600 + D)
+    flat = ddpg.dict_to_flat(dc.draw_params(rs, D, A, hidden), ddpg.params_layout(D, A, hidden))
+    target = (flat + 0.02 * rs.normal(0, 1, flat.shape)).astype(np.float32)
+    mult = np.where(np.arange(N) % 7 == 0, 50.0, 1.0)[:, None]       # the clip bites
+    inputs = {'obs0': (2.0 * rs.normal(0, 1, (N, D)) * mult).astype(np.float32),
+              'actions': np.clip(rs.normal(0, 0.5, (N, A)), -1, 1).astype(np.float32),
+              'rewards': rs.normal(0, 1, N).astype(np.float32),
+              'obs1': (2.0 * rs.normal(0, 1, (N, D))).astype(np.float32),
+              'dones': (rs.uniform(0, 1, N) < 0.2).astype(np.uint8)}
+    obs, batch = _cuda(inputs['obs0']), _dev(inputs)
+    noise = _cuda(rs.normal(0, 0.4, (N, A)).astype(np.float32))
+    normal = ddpg.NormalActionNoise(*_columns(A))
+    g = rng.DeviceRng(SEED, 0, row_offset=1000)
+    agents = [cls(D, A, hidden, scale=_scale(A), grid_limit=2) for cls in (DDPGAgent, WideDDPGAgent)]
+    for agent in agents:
+        agent.set_params(flat)
+        agent.set_params(target, target_only=True)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    got = ({}, {})
+    with torch.cuda.stream(stream):
+        for name, call in (
+                ('act', lambda a: a.act(obs, noise, stream=stream.cuda_stream)),
+                ('act_rng', lambda a: a.act(obs, noise=(normal, g), t=3, stream=stream.cuda_stream)),
+                ('target', lambda a: {'y': a.target(batch, stream=stream.cuda_stream)}),
+                ('grad', lambda a: a.grad(batch, stream=stream.cuda_stream)),
+                ('step1', lambda a: a.step(batch, stream=stream.cuda_stream)),
+                ('step2', lambda a: a.step(batch, stream=stream.cuda_stream))):
+            for out, agent in zip(got, agents):          # narrow, wide, narrow, wide, ...
+                out[name] = call(agent)
+    stream.synchronize()
+    narrow, wide = got
+    for name in ('act', 'act_rng'):
+        for field in ('action', 'env_action'):
+            assert _same(_np(narrow[name][field]), _np(wide[name][field])), (name, field)
+    assert not _same(_np(narrow['act']['action']), _np(narrow['act_rng']['action']))
+    assert _same(_np(narrow['target']['y']), _np(wide['target']['y']))
+    assert _same(_np(narrow['grad'][0]), _np(wide['grad'][0]))
+    for name, stats in (('grad', (narrow['grad'][1], wide['grad'][1])),
+                        ('step1', (narrow['step1'], wide['step1'])),
+                        ('step2', (narrow['step2'], wide['step2']))):
+        assert _same(_np(stats[0].tensor), _np(stats[1].tensor)), name
+        assert _same(_np(stats[0].y), _np(stats[1].y)), name
+    assert not _same(_np(narrow['step1'].tensor), _np(narrow['step2'].tensor))
+    assert _same(agents[0].get_params(), agents[1].get_params())
+    assert _same(agents[0].get_params(target=True), agents[1].get_params(target=True))
+    for block in ('m', 'v'):
+        assert _same(agents[0].get_opt_state()[block], agents[1].get_opt_state()[block])
+    assert agents[0].get_opt_state()['step'] == agents[1].get_opt_state()['step'] == 2
+    assert not _same(agents[0].get_params(), flat)
+    for agent in agents:
+        agent.close()
 
 
 # ------------------------------------------ 3. idx, determinism, a clean partial
